@@ -5,11 +5,13 @@ One "step" = one denoising step of the named model = every attention layer of th
 (x forwards per step), each layer being ONE routed-attention op (router dispatch is given, experts:
 full / coreset / sliding tile) on synthetic post-RoPE Q/K/V already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config hunyuan-129f] [--mix uniform]
+    python bench.py [--gpus N --steps K --warmup W] [--config hunyuan-129f] [--mix uniform] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N>1: Ulysses over RCCL)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` and, at N=1,
-`cpu_baseline`.
+Prints ONE JSON line on rank 0 carrying `ms_per_step` and `roofline` (from per-launch events of the timed steps).  A plain run
+sets up, warms up, times the steps and prints; --full adds, at N=1, the measurements that take runs of their own after the
+timed region: the library GEMM ceiling, the library kernels the reference borrows, and `cpu_baseline`.
+--dump-outputs DIR writes every output the last timed step computed (DIR/<name>.npy, float32; a seeded row sample when large).
 """
 import argparse
 import json
@@ -281,9 +283,9 @@ def processor_level(cfg, mix, dev, dt, fp8):
         proc = WanAttnProcessorTripleEval()
     sink = []
 
-    def one_step():
+    def one_step(capture=None):
         plan.compute(temb, tau)
-        for _ in range(cfg["fwd_per_step"]):
+        for f in range(cfg["fwd_per_step"]):
             for l in range(L):
                 if hy:
                     a = dual_attn if l < n_dual else single_attn
@@ -291,6 +293,8 @@ def processor_level(cfg, mix, dev, dt, fp8):
                 else:
                     out = proc(single_attn, hidden, None, None, rope, routing_score=plan.scores(l),
                                head_routing=plan.routing(l), **kw)
+                if capture is not None:  # (dual-stream blocks return (video, text): the video stream's rows)
+                    capture(f * L + l, out[0] if isinstance(out, tuple) else out)
         sink[:] = [out]
 
     def fingerprint_tensor():
@@ -569,6 +573,33 @@ def stub_worker(args, rank: int, world: int, attempt: int) -> int:
     return 0
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes written at most
+
+
+class OutputSample:
+    """--dump-outputs: what every call of the last timed step returned.  Each output is read as rows of `row_len` values; the
+    same rows of every call are gathered on the device right after the call into one preallocated buffer -- all valid rows
+    when they fit in DUMP_BYTES, else a fixed seeded sample of them.  `rows_of` maps valid-row numbers to rows of the tensor
+    (skips the padding text rows of a Hunyuan output)."""
+
+    def __init__(self, name, calls, n_rows, row_len, dev, dtype, rows_of=lambda r: r):
+        per_call = max(1, DUMP_BYTES // (4 * row_len * calls))
+        rows = (np.arange(n_rows) if per_call >= n_rows else
+                np.sort(np.random.default_rng(1234).choice(n_rows, per_call, replace=False)))
+        self.name, self.row_len = name, row_len
+        self.idx = torch.as_tensor(rows_of(rows), dtype=torch.int64, device=dev)
+        self.buf = torch.empty((calls, len(rows), row_len), device=dev, dtype=dtype)
+
+    def __call__(self, i, t):
+        torch.index_select(t.reshape(-1, self.row_len), 0, self.idx, out=self.buf[i])
+
+    def write(self, directory):
+        os.makedirs(directory, exist_ok=True)
+        path = os.path.join(directory, self.name + ".npy")
+        np.save(path, self.buf.float().cpu().numpy())
+        print(f"[bench] {path}: {tuple(self.buf.shape)} float32 (calls of the last timed step x rows x values)", file=sys.stderr)
+
+
 def main():
     # the host driver only supports dmabuf IPC: must be in the environment before HIP / HSA initialise
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -618,9 +649,17 @@ def main():
     ap.add_argument("--no-v-wire", action="store_true",
                     help="N>1 with --dtype fp8: exchange v in 16 bits and convert it on the receive side (A/B; default: v "
                          "is converted on the send side and crosses the links as e4m3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the timed region also measure the context figures that take runs of their own -- the "
+                         "library GEMM ceiling, the library kernels the reference borrows, cpu_baseline (off by default: a "
+                         "plain run times the steps and prints its line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32): every attention call's "
+                         "output, a fixed seeded sample of its rows when the whole would pass %d MB; single-GPU paths" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-gemm-ceiling", action="store_true",
-                    help="skip the torch.matmul (hipBLASLt) context measurement reported beside roofline.frac")
+                    help="with --full: skip the torch.matmul (hipBLASLt) context measurement reported beside roofline.frac "
+                         "and the borrowed library kernels")
     ap.add_argument("--sliding-block-rows", type=int, default=0, choices=[0, 128, 256],
                     help="query rows per workgroup of the sliding-tile launch (0 = library heuristic; 256 lets it join "
                          "the fused grid)")
@@ -634,6 +673,8 @@ def main():
                     help="fused: the experts of a layer as ONE grid (vorta_attn_fwd_batch); serial: one launch per "
                          "expert on one stream; concurrent: experts on side HIP streams")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_rank or os.environ.get("VORTA_BENCH_FORCE_SP") == "1"):
+        raise SystemExit("--dump-outputs: single-GPU paths only (not --gpus N > 1, --emulate-rank or VORTA_BENCH_FORCE_SP)")
 
     cfg = dict(CONFIGS[args.config])
     if args.dtype:
@@ -725,10 +766,14 @@ def main():
             raise SystemExit("--emulate-rank runs on one GPU")
         P = emu
     proc_info = None
+    dump = None  # --dump-outputs: OutputSample filled during the last timed step
+    calls = L * cfg["fwd_per_step"]
     if args.level == "processor":
         if P != 1:
             raise SystemExit("--level processor runs on one GPU")
         one_step, fp_tensor, layer_ids, proc_info = processor_level(cfg, args.mix, dev, dt, fp8)
+        if args.dump_outputs:  # every block's attention output (the video stream's hidden states)
+            dump = OutputSample("processor_out", calls, S, H * 128, dev, dt)
     elif P == 1 and not sp_run:
         geom = RoutedGeometry(cfg["latent"], cfg["tile"], cfg["window"], cfg["group"], cfg["rate"], dev)
         routings = [HeadRouting.from_expert_ids(e, dev) for e in layer_ids]
@@ -743,14 +788,19 @@ def main():
                  (ops.fp8_quantize_v(sets[0][2][0]), ops.i8_quantize_k(sets[0][0][0], sets[0][1][0])) if fp8 in ("i8pv", "auto8") else None)
         if te:
             geom.sta_tables(te)  # built once per prompt, outside the step (pipeline_hunyuan.py:378-392)
+        if args.dump_outputs:  # rows (head, token) of `out` with token < S + te: the padding text rows are nobody's output
+            dump = OutputSample("attention_out", calls, H * (S + te), 128, dev, dt,
+                                rows_of=lambda r: (r // (S + te)) * (S + T) + r % (S + te))
 
-        def one_step():
-            for _ in range(cfg["fwd_per_step"]):
+        def one_step(capture=None):
+            for f in range(cfg["fwd_per_step"]):
                 for l in range(L):
                     q, k, v = sets[l % len(sets)]
                     routed_attention(q, k, v, routings[l], geom, model=cfg["model"], text_len=T, text_valid=te, out=out,
                                      concurrent=concurrent, fused=fused, sliding_block_rows=args.sliding_block_rows,
                                      fp8=fp8, fp8_operands=f8buf)
+                    if capture is not None:
+                        capture(f * L + l, out)
     else:
         from vorta_amd import ulysses
         sp = ulysses.UlyssesRoutedAttention(cfg, layer_ids, per_head, dev, dt, rank, P,
@@ -759,7 +809,7 @@ def main():
                                             placement=args.placement, heaviest_rank=bool(emu),
                                             kv_splits=args.kv_splits if args.kv_splits == "auto" else int(args.kv_splits))
 
-        def one_step():
+        def one_step(capture=None):  # (--dump-outputs is refused on this path)
             for _ in range(cfg["fwd_per_step"]):
                 for l in range(L):
                     sp.layer(l)
@@ -792,14 +842,16 @@ def main():
         torch.cuda.set_sync_debug_mode("error")
     t0 = time.perf_counter()
     try:
-        for _ in range(args.steps):
-            one_step()
+        for i in range(args.steps):
+            one_step(dump if i == args.steps - 1 else None)
     finally:
         if proc_info is not None:
             torch.cuda.set_sync_debug_mode("default")
     barrier()
     elapsed = time.perf_counter() - t0
     ops.set_timeline(None)
+    if dump is not None:
+        dump.write(args.dump_outputs)
     if sp_run:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -930,7 +982,8 @@ def main():
         "switches": {"env": {k_: v_ for k_, v_ in sorted(os.environ.items()) if k_.startswith("VORTA_")},
                      "library": __import__("vorta_amd._C", fromlist=["lib"]).lib().vorta_build_info().decode()},
     }
-    if world == 1 and not sp_run and not args.no_gemm_ceiling:
+    full = args.full and world == 1 and not sp_run  # the context measurements below: runs of their own, --full only
+    if full and not args.no_gemm_ceiling:
         # context for `frac`: what a plain library GEMM (hipBLASLt via torch.matmul, same dtype) sustains on THIS
         # box right now -- the practical MFMA ceiling under the chip's power/clock management (measured after the
         # timed region, never part of `value`)
@@ -959,10 +1012,10 @@ def main():
         except Exception as exc:  # context only: never let it cost the bench line
             roofline["library_gemm_tflops"] = None
             roofline["library_gemm_error"] = f"{type(exc).__name__}: {exc}"[:200]
-    if world == 1 and not sp_run and not args.no_gemm_ceiling and not emu and proc_info is None:
+    if full and not args.no_gemm_ceiling and not emu and proc_info is None:
         borrowed_dense(cfg, S, te, H, L, dev, roofline, res, achieved, layer_ids)
     if rank == 0:
-        if world == 1 and not sp_run and not args.no_cpu_baseline and not emu and proc_info is None:
+        if full and not args.no_cpu_baseline and not emu and proc_info is None:
             res["cpu_baseline"] = cpu_baseline(cfg, layer_ids, cfg["dtype"])
         abandoned = res.pop("_abandoned_thread", False)
         print(json.dumps(res), flush=True)

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ def _line(out: str) -> dict:
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--config", "tiny", "--steps", "2", "--warmup", "1"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--config", "tiny", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _line(r.stdout)
@@ -32,6 +33,34 @@ def test_bench_single_gpu_line():
     # the library kernels the reference borrows, beside ours (context fields; an error is named, never raised)
     assert "library_sdpa_tflops" in j["roofline"] and "step_ms_if_borrowed_routed" in j["config"], j["config"]
     assert j["config"]["step_ms_if_borrowed_routed"] is None or j["config"]["step_ms_if_borrowed_routed"] > 0
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries none of the context measurements that take runs of their own.  --dump-outputs writes
+    what the last timed step computed -- every layer's output (tiny: all valid rows; the processor level: every block's video
+    stream), float32 -- and the same inputs give the same arrays from run to run."""
+    import bench
+    tiny = bench.CONFIGS["tiny"]
+    S = tiny["latent"][0] * tiny["latent"][1] * tiny["latent"][2]
+    dumps = {}
+    for name, extra, file, shape in (
+            ("a", [], "attention_out", (tiny["layers"], tiny["heads"] * (S + tiny["text_valid"]), 128)),
+            ("b", [], "attention_out", None),
+            ("processor", ["--level", "processor"], "processor_out", (tiny["layers"], S, tiny["heads"] * 128))):
+        r = subprocess.run([sys.executable, "bench.py", "--config", "tiny", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / name)] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (name, r.stderr[-2000:])
+        j = _line(r.stdout)
+        assert KEYS <= set(j) and j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert "cpu_baseline" not in j and "step_ms_if_borrowed_routed" not in j["config"]
+        assert not {"library_gemm_tflops", "library_sdpa_tflops"} & set(j["roofline"]) and j["roofline"]["achieved"] > 0
+        assert os.listdir(tmp_path / name) == [file + ".npy"]
+        a = np.load(tmp_path / name / (file + ".npy"))
+        assert a.dtype == np.float32 and a.nbytes <= 64 << 20 and np.isfinite(a).all() and np.abs(a).max() > 0
+        assert a.shape == (shape or dumps["a"].shape)
+        assert not np.array_equal(a[0], a[1])  # one array per layer, not one layer's output repeated
+        dumps[name] = a
+    assert np.array_equal(dumps["a"], dumps["b"])
 
 
 @pytest.mark.parametrize("dtype", ["fp16", "fp8"])

@@ -53,7 +53,7 @@ import json; d=json.loads(open('$f').read().strip().splitlines()[-1]); print('$f
   ;;
 bench)
   for c in ${CONFIGS:-hunyuan-129f:fp16 wan1.3b-49f:bf16}; do
-    timeout -k 10 600 python3 bench.py --config ${c%%:*} --dtype ${c##*:} --steps ${STEPS:-5} --warmup 2 > $O/bench_${c%%:*}_${c##*:}.json 2>> $O/bench_err.txt || tail -5 $O/bench_err.txt
+    timeout -k 10 600 python3 bench.py --full --config ${c%%:*} --dtype ${c##*:} --steps ${STEPS:-5} --warmup 2 > $O/bench_${c%%:*}_${c##*:}.json 2>> $O/bench_err.txt || tail -5 $O/bench_err.txt
     tail -c 600 $O/bench_${c%%:*}_${c##*:}.json
   done
   if [ -n "${PROF:-}" ]; then
