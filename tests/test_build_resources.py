@@ -11,7 +11,7 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not __import__
                                 reason="needs hipcc")
 
 
-@pytest.mark.parametrize("source", ["attn_fwd.hip", "attn_fwd_fp8.hip"])
+@pytest.mark.parametrize("source", ["attn_fwd.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip"])
 def test_attention_kernels_do_not_spill(source):
     res = build.kernel_resources(source)
     assert len(res) >= 10

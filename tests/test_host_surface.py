@@ -58,6 +58,88 @@ def test_argument_validation_happens_before_any_launch():
         _C.check(_C.VORTA_EUNSUPPORTED, "x")
 
 
+def test_attention_entry_points_refuse_before_any_launch():
+    """The refusal codes of the six attention entry points and of the mixed route (fp8 entry points, ext->flags bit1).
+    Fake 16-byte-aligned pointers: every call below returns before a launch (no GPU needed)."""
+    from vorta_amd import _C
+    lib = _C.lib()
+    P = 1 << 20  # never dereferenced
+    EINVAL, EUNSUP, OK = _C.VORTA_EINVAL, _C.VORTA_EUNSUPPORTED, _C.VORTA_OK
+    BF, FP = _C.VORTA_BF16, _C.VORTA_FP16
+
+    def seg(kind, dtype=BF, rows=256, variant=0, heads=1):
+        a = _C.AttnArgs()
+        a.struct_size, a.head_dim, a.n_heads = ctypes.sizeof(_C.AttnArgs), 128, heads
+        a.dtype = _C.VORTA_FP8E4M3 if kind == "fp8" else dtype  # "mx": v e4m3, "i8": k int8, v e4m3
+        for t in (a.q, a.k, a.v, a.o):
+            t.ptr, t.stride_s, t.stride_h = P, 128, 128 * 4096  # (strides in elements of any width)
+        a.n_q, a.n_kv, a.q_valid, a.scale, a.block_rows, a.n_splits, a.variant = 512, 512, 512, 0.1, rows, 1, variant
+        return a
+
+    def fp8_ext(flags=0, v_descale=P):
+        e = _C.AttnFp8Ext()
+        e.struct_size, e.out_dtype, e.flags = ctypes.sizeof(_C.AttnFp8Ext), BF, flags
+        e.v_descale, e.v_descale_stride_h = v_descale, 128
+        return e
+
+    def i8_ext():
+        e = _C.AttnI8Ext()
+        e.struct_size = ctypes.sizeof(_C.AttnI8Ext)
+        e.k_bias, e.q_prep, e.q_prep_stride_h, e.k_head_scale, e.v_descale, e.v_descale_stride_h = P, P, 256, P, P, 128
+        return e
+
+    def arr(*segs):
+        return (_C.AttnArgs * len(segs))(*segs)
+
+    def batch(kind, segs, ext=None, n=None):
+        n = len(segs) if n is None else n
+        if kind == "16":
+            return lib.vorta_attn_fwd_batch(arr(*segs), n, None)
+        if kind == "i8":
+            return lib.vorta_attn_fwd_batch_i8(arr(*segs), ctypes.byref(ext or i8_ext()), n, None)
+        return lib.vorta_attn_fwd_batch_fp8(arr(*segs), ctypes.byref(ext or fp8_ext(2 if kind == "mx" else 0)), n, None)
+
+    for kind in ("16", "fp8", "mx", "i8"):
+        one, short, empty = seg(kind), seg(kind, rows=128), seg(kind, rows=128, heads=0)
+        assert batch(kind, [one] * 7) == EINVAL  # more launches than one grid holds
+        assert batch(kind, [one], n=-1) == EINVAL
+        assert batch(kind, [one, short]) == EUNSUP  # only the 256-row pipelined kernel fuses
+        # an empty launch is skipped before the fused-grid rules (its 128 rows) and does not set the grid's dtype
+        assert batch(kind, [empty, empty]) == OK
+        assert batch(kind, [empty, one, short]) == EUNSUP
+        if kind in ("16", "i8"):
+            assert batch(kind, [seg(kind, FP, heads=0), one, short]) == EUNSUP
+    assert lib.vorta_attn_fwd_batch(None, 1, None) == EINVAL
+    assert lib.vorta_attn_fwd_batch_fp8(None, ctypes.byref(fp8_ext()), 1, None) == EINVAL
+    assert lib.vorta_attn_fwd_batch_i8(None, ctypes.byref(i8_ext()), 1, None) == EINVAL
+    assert lib.vorta_attn_fwd_batch_fp8(arr(seg("fp8")), None, 0, None) == EINVAL  # a null ext even for an empty batch
+    assert lib.vorta_attn_fwd_batch_i8(arr(seg("i8")), None, 0, None) == EINVAL
+    # the 16-bit plain kernel (variant 1) and the e4m3 kernel's VALU row sum (ext->flags bit0) have no fused form
+    assert batch("16", [seg("16"), seg("16", variant=1)]) == EUNSUP
+    assert batch("fp8", [seg("fp8"), seg("fp8")], fp8_ext(flags=1)) == EUNSUP
+    # one output type per grid: 16-bit and int8-score grids refuse mixed dtypes; an e4m3 grid never gets there (a 16-bit
+    # launch fails its own dtype check), nor does the mixed route (ext->out_dtype binds the dtype of every launch)
+    assert batch("16", [seg("16", BF), seg("16", FP)]) == EINVAL
+    assert batch("i8", [seg("i8", BF), seg("i8", FP)]) == EINVAL
+    assert batch("fp8", [seg("fp8"), seg("16")]) == EUNSUP
+    assert batch("mx", [seg("mx", BF), seg("mx", FP)]) == EUNSUP
+    # single launches
+    assert lib.vorta_attn_fwd(None, None) == EINVAL
+    assert lib.vorta_attn_fwd_fp8(ctypes.byref(seg("fp8")), None, None) == EINVAL
+    assert lib.vorta_attn_fwd_i8(ctypes.byref(seg("i8")), None, None) == EINVAL
+    assert lib.vorta_attn_fwd_fp8(ctypes.byref(seg("fp8", variant=1)), ctypes.byref(fp8_ext()), None) == EUNSUP
+    assert lib.vorta_attn_fwd_fp8(ctypes.byref(seg("mx", variant=1)), ctypes.byref(fp8_ext(2)), None) == EUNSUP
+    assert lib.vorta_attn_fwd_i8(ctypes.byref(seg("i8", variant=1)), ctypes.byref(i8_ext()), None) == EUNSUP
+    # the mixed route is ext->flags bit1, single and fused: 16-bit q, k without v_descale is an argument error there and a
+    # dtype error on the all-e4m3 path
+    for fn in (lambda a, e: lib.vorta_attn_fwd_fp8(ctypes.byref(a), ctypes.byref(e), None),
+               lambda a, e: batch("fp8", [a], e)):
+        assert fn(seg("mx"), fp8_ext(2, v_descale=None)) == EINVAL
+        assert fn(seg("mx"), fp8_ext(0, v_descale=None)) == EUNSUP
+        assert fn(seg("mx"), fp8_ext(2 | 1)) == EUNSUP  # the VALU row sum is an experiment of the all-e4m3 kernel only
+        assert fn(seg("fp8"), fp8_ext(2)) == EUNSUP
+
+
 def test_ops_refuse_cpu_tensors():
     from vorta_amd import _C, ops
     q = torch.zeros((1, 64, 128), dtype=torch.bfloat16)

@@ -1,5 +1,6 @@
-// Shared pieces of the gather flash-attention kernels (attn_fwd.hip: 32 query rows per wave, two waves per
-// SIMD; attn_fwd_w64.hip: 64 query rows per wave, one wave per SIMD).
+// Shared pieces of the gather flash-attention kernel families (attn_fwd.hip: 16 bits; attn_fwd_fp8.hip: all e4m3;
+// attn_fwd_mx.hip: 16-bit scores, e4m3 P V; attn_fwd_i8.hip: int8 scores, e4m3 P V): the launch parameters, the fused-grid
+// block, the split-key merge and the host launch path.  Only the loop bodies are a family's own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -71,11 +72,162 @@ __device__ __forceinline__ int live_order(const Params& p, int b, int n, bool re
 #endif
 constexpr int MAX_SEGMENTS = VORTA_MAX_SEGMENTS;  // launches fused into one grid (vorta_attn_fwd_batch): three experts, the text queries or up to
                                  // two partial full-attention heads of a sequence-parallel rank (ulysses/engine.py split_placement)
-struct MultiParams {
-  Params seg[MAX_SEGMENTS];
+// Params8, ParamsMx and ParamsI8 extend a Params `p` with their family's fields; base_of reaches the common part of any block
+template <class PP> __host__ __device__ __forceinline__ Params& base_of(PP& pp) { return pp.p; }
+template <class PP> __host__ __device__ __forceinline__ const Params& base_of(const PP& pp) { return pp.p; }
+__host__ __device__ __forceinline__ Params& base_of(Params& p) { return p; }
+__host__ __device__ __forceinline__ const Params& base_of(const Params& p) { return p; }
+
+template <class PP> struct MultiOf {
+  PP seg[MAX_SEGMENTS];
   int start[MAX_SEGMENTS + 1];  // first workgroup of each segment; start[n] = grid size
   int n;
 };
+
+// Segment of physical block b of a fused grid, and (wg) its logical workgroup id in XCD-aware order INSIDE the segment:
+// workgroups whose ids are equal mod 8 share an XCD (round-robin dispatch), so each such class gets a contiguous chunk of
+// the segment's logical ids (same head, neighbouring query blocks -> one L2 serves the K/V stream instead of eight).  Every
+// XCD still gets 1/8 of every segment, which keeps the chip balanced across segments of different cost.
+template <class PP>
+__device__ __forceinline__ const PP& segment_of(const MultiOf<PP>& mp, int b, int& wg) {
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < MAX_SEGMENTS; ++i) s += (i < mp.n && b >= mp.start[i]) ? 1 : 0;
+  wg = live_order(base_of(mp.seg[s]), b - mp.start[s], mp.start[s + 1] - mp.start[s], true);
+  return mp.seg[s];
+}
+
+// Per-channel factor of the merged output: v_descale[head] for the families with e4m3 V, none in 16 bits
+__device__ __forceinline__ float2 out_descale(const Params&, int, int) { return make_float2(1.f, 1.f); }
+template <class PP> __device__ __forceinline__ float2 out_descale(const PP& pp, int head, int lane) {
+  return *(const float2*)(pp.v_descale + (int64_t)head * pp.v_descale_sh + lane * 2);
+}
+
+// Merge the split-key partials: one wave per (head slot, query position).  The partials are unnormalised (in the e4m3-P
+// families both sums carry the 2^p_bias factor) and the reference points are in the exp2 domain.
+template <typename T, class PP>
+__global__ __launch_bounds__(256) void attn_combine_kernel(const PP pp) {
+  const Params& p = base_of(pp);
+  const int lane = threadIdx.x & 63;
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= (int64_t)p.n_heads * p.n_q) return;
+  const int y = (int)(item / p.n_q);
+  const int pos = (int)(item - (int64_t)y * p.n_q);
+  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
+  const int head = p.head_list ? p.head_list[y] : y;
+  float m = -1e30f;
+  for (int s = 0; s < p.n_splits; ++s) m = fmaxf(m, p.ws_ml[(((int64_t)y * p.n_splits + s) * p.n_q + pos) * 2]);
+  float acc0 = 0.f, acc1 = 0.f, l = 0.f;
+  for (int s = 0; s < p.n_splits; ++s) {
+    const int64_t slot = ((int64_t)y * p.n_splits + s) * p.n_q + pos;
+    const float w = __builtin_amdgcn_exp2f(p.ws_ml[slot * 2] - m);
+    l += w * p.ws_ml[slot * 2 + 1];
+    const float2 v = *(const float2*)(p.ws_o + slot * D + lane * 2);
+    acc0 += w * v.x;
+    acc1 += w * v.y;
+  }
+  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
+  const float inv = (pos < q_valid && l > 0.f) ? 1.f / l : 0.f;
+  const float2 sd = out_descale(pp, head, lane);
+  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
+  const int64_t row = q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
+  T pair[2] = {(T)(acc0 * inv * sd.x), (T)(acc1 * inv * sd.y)};
+  char* ob = p.o + (int64_t)head * p.o_sh + lane * 4;
+  *(uint32_t*)(ob + row * p.o_ss) = *(uint32_t*)pair;
+  if (p.dup_rows && pos < p.n_dup_pos) {
+    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)pos * p.n_dup;
+    for (int i = 0; i < p.n_dup; ++i) *(uint32_t*)(ob + (int64_t)dr[i] * p.o_ss) = *(uint32_t*)pair;
+  }
+}
+
+// ---- host: the launch path of every family ----
+// A family (one per source file) supplies only what differs:
+//   F::PP                            its parameter block (Params, or one that extends it)
+//   f.fill(a, pp, block_rows)        validation + launch geometry of one launch (the args and the family's ext)
+//   f.fusable(a, pp)                 whether a 256-row launch may join a fused grid
+//   f.out_dtype(a)                   VORTA_BF16 / VORTA_FP16: the output type T of the kernels
+//   F::kernel<T>(a, pp, block_rows)  the single-launch kernel (block_rows / 32 waves)
+//   F::multi<T>                      the fused-grid kernel (8 waves)
+
+template <typename T, class PP>
+int launch_combine(const PP& pp, hipStream_t st) {
+  const Params& p = base_of(pp);
+  if (p.n_splits <= 1) return VORTA_OK;
+  const int64_t items = (int64_t)p.n_heads * p.n_q;
+  hipLaunchKernelGGL((attn_combine_kernel<T, PP>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+}
+
+template <typename T, class PP>
+int launch_single(void (*kernel)(PP), int block_rows, const PP& pp, hipStream_t st) {
+  const Params& p = base_of(pp);
+  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads * p.n_splits;
+  if (total <= 0) return VORTA_OK;
+  if (total > 0x7fffffff) return VORTA_EINVAL;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(block_rows * 2), 0, st, pp);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return vorta_set_hip_error(e);
+  return launch_combine<T>(pp, st);
+}
+
+// vorta_attn_fwd and its siblings: one launch of the family's kernel, then the split-key merge
+template <class F>
+int fwd_single(const F& f, const vorta_attn_args* a, void* hip_stream) {
+  typename F::PP pp{};
+  int block_rows = 0;
+  const int rc = f.fill(a, pp, block_rows);
+  if (rc != VORTA_OK) return rc;
+  if (base_of(pp).n_heads == 0 || base_of(pp).n_groups == 0) return VORTA_OK;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (f.out_dtype(*a) == VORTA_BF16) return launch_single<__bf16>(F::template kernel<__bf16>(*a, pp, block_rows), block_rows, pp, st);
+  return launch_single<_Float16>(F::template kernel<_Float16>(*a, pp, block_rows), block_rows, pp, st);
+}
+
+template <typename T, class PP>
+int launch_fused(void (*kernel)(MultiOf<PP>), const MultiOf<PP>& mp, int total, hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(512), 0, st, mp);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return vorta_set_hip_error(e);
+  for (int i = 0; i < mp.n; ++i) {
+    const int rc = launch_combine<T>(mp.seg[i], st);
+    if (rc != VORTA_OK) return rc;
+  }
+  return VORTA_OK;
+}
+
+// vorta_attn_fwd_batch and its siblings: up to MAX_SEGMENTS launches as the segments of ONE grid, in the given order.
+// Empty launches are skipped; the others must resolve to the 256-row pipelined kernel and share one output type.
+template <class F>
+int fwd_batch(const F& f, const vorta_attn_args* args, int32_t n, void* hip_stream) {
+  if (!args || n < 0 || n > MAX_SEGMENTS) return VORTA_EINVAL;
+  MultiOf<typename F::PP> mp{};
+  int64_t total = 0;
+  int dtype = -1, m = 0;
+  for (int i = 0; i < n; ++i) {
+    typename F::PP pp{};
+    int block_rows = 0;
+    const int rc = f.fill(&args[i], pp, block_rows);
+    if (rc != VORTA_OK) return rc;
+    Params& p = base_of(pp);
+    if (p.n_heads == 0 || p.n_groups == 0) continue;
+    if (block_rows != 256 || !f.fusable(args[i], pp)) return VORTA_EUNSUPPORTED;
+    if (dtype >= 0 && dtype != f.out_dtype(args[i])) return VORTA_EINVAL;
+    dtype = f.out_dtype(args[i]);
+    p.xcd_remap = 0;  // segment_of orders the workgroups
+    mp.seg[m] = pp;
+    mp.start[m] = (int)total;
+    total += (int64_t)p.n_groups * p.blocks_per_group * p.n_heads * p.n_splits;
+    if (total > 0x7fffffff) return VORTA_EINVAL;
+    ++m;
+  }
+  if (m == 0) return VORTA_OK;
+  for (int i = m; i <= MAX_SEGMENTS; ++i) mp.start[i] = (int)total;
+  mp.n = m;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (dtype == VORTA_BF16) return launch_fused<__bf16>(F::template multi<__bf16>, mp, (int)total, st);
+  return launch_fused<_Float16>(F::template multi<_Float16>, mp, (int)total, st);
+}
 
 // attn_fwd.hip: argument validation + launch geometry (in_esize = bytes per q/k element, v_esize per v element: 0 = the
 // same; args->dtype names the 2-byte type, or e4m3 when in_esize = 1)

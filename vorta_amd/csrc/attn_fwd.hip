@@ -707,82 +707,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_pipe_kernel(const Params 
 // workgroups instead of idling until a kernel boundary.
 
 template <typename T>
-__global__ __launch_bounds__(512, 2) void attn_fwd_multi_kernel(const MultiParams mp) {
+__global__ __launch_bounds__(512, 2) void attn_fwd_multi_kernel(const MultiOf<Params> mp) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub
   __shared__ __attribute__((aligned(16))) char smem[2 * RING * TILE_BYTES];  // K and V rings
-  const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_SEGMENTS; ++i) s += (i < mp.n && b >= mp.start[i]) ? 1 : 0;
-  const Params& p = mp.seg[s];
-  // XCD-aware order INSIDE the segment: workgroups whose ids are equal mod 8 share an XCD (round-robin
-  // dispatch), so give each such class a contiguous chunk of the segment's logical ids (same head,
-  // neighbouring query blocks -> one L2 serves the K/V stream instead of eight).  Every XCD still gets 1/8 of
-  // every segment, which keeps the chip balanced across segments of different cost.
-  const int wg = live_order(p, b - mp.start[s], mp.start[s + 1] - mp.start[s], true);
+  int wg;
+  const Params& p = segment_of(mp, blockIdx.x, wg);
   if (p.kv_rows) attn_pipe_dma_body<T, 8, true, RING>(p, smem, wg);
   else attn_pipe_dma_body<T, 8, false, RING>(p, smem, wg);
 #endif
-}
-
-// Merge the split-key partials: one wave per (head slot, query position).
-template <typename T>
-__global__ __launch_bounds__(256) void attn_combine_kernel(const Params p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (item >= (int64_t)p.n_heads * p.n_q) return;
-  const int y = (int)(item / p.n_q);
-  const int pos = (int)(item - (int64_t)y * p.n_q);
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  float m = -1e30f;
-  for (int s = 0; s < p.n_splits; ++s) m = fmaxf(m, p.ws_ml[(((int64_t)y * p.n_splits + s) * p.n_q + pos) * 2]);
-  float acc0 = 0.f, acc1 = 0.f, l = 0.f;
-  for (int s = 0; s < p.n_splits; ++s) {
-    const int64_t slot = ((int64_t)y * p.n_splits + s) * p.n_q + pos;
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[slot * 2] - m);  // reference points are stored in the exp2 domain
-    l += w * p.ws_ml[slot * 2 + 1];
-    const float2 v = *(const float2*)(p.ws_o + slot * D + lane * 2);
-    acc0 += w * v.x;
-    acc1 += w * v.y;
-  }
-  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
-  const float inv = (pos < q_valid && l > 0.f) ? 1.f / l : 0.f;
-  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int64_t row = q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
-  T pair[2] = {(T)(acc0 * inv), (T)(acc1 * inv)};
-  char* ob = p.o + (int64_t)head * p.o_sh + lane * 4;
-  *(uint32_t*)(ob + row * p.o_ss) = *(uint32_t*)pair;
-  if (p.dup_rows && pos < p.n_dup_pos) {
-    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)pos * p.n_dup;
-    for (int i = 0; i < p.n_dup; ++i) *(uint32_t*)(ob + (int64_t)dr[i] * p.o_ss) = *(uint32_t*)pair;
-  }
-}
-
-template <typename T, int NW>
-int launch(const Params& p, hipStream_t st, bool pipe) {
-  const int64_t n_qb = (int64_t)p.n_groups * p.blocks_per_group;
-  const int64_t total = n_qb * p.n_heads * p.n_splits;
-  if (total <= 0) return VORTA_OK;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  hipError_t e;
-  if (pipe) {
-    if (p.kv_rows) hipLaunchKernelGGL((attn_fwd_pipe_kernel<T, NW, true>), dim3((unsigned)total), dim3(NW * 64), 0, st, p);
-    else hipLaunchKernelGGL((attn_fwd_pipe_kernel<T, NW, false>), dim3((unsigned)total), dim3(NW * 64), 0, st, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vorta_set_hip_error(e);
-  } else {
-    hipLaunchKernelGGL((attn_fwd_kernel<T, NW>), dim3((unsigned)total), dim3(NW * 64), 0, st, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vorta_set_hip_error(e);
-  }
-  if (p.n_splits > 1) {
-    const int64_t items = (int64_t)p.n_heads * p.n_q;
-    hipLaunchKernelGGL((attn_combine_kernel<T>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vorta_set_hip_error(e);
-  }
-  return VORTA_OK;
 }
 
 }  // namespace
@@ -861,7 +793,20 @@ int vorta_attn::fill_params(const vorta_attn_args* a, Params& p, int& block_rows
 
 namespace {
 using namespace vorta_attn;
-int fill_params(const vorta_attn_args* a, Params& p, int& block_rows) { return vorta_attn::fill_params(a, p, block_rows, 2); }
+
+struct Family16 {
+  using PP = Params;
+  int fill(const vorta_attn_args* a, Params& p, int& block_rows) const { return fill_params(a, p, block_rows, 2); }
+  bool fusable(const vorta_attn_args& a, const Params&) const { return a.variant != 1; }
+  int out_dtype(const vorta_attn_args& a) const { return a.dtype; }
+  template <typename T> static constexpr auto multi = attn_fwd_multi_kernel<T>;
+  template <typename T> static auto kernel(const vorta_attn_args& a, const Params& p, int block_rows) {
+    // variant 0 (auto) = the software-pipelined kernel with LDS-DMA staging, for both workgroup sizes
+    if (a.variant == 1) return block_rows == 256 ? attn_fwd_kernel<T, 8> : attn_fwd_kernel<T, 4>;
+    if (block_rows == 256) return p.kv_rows ? attn_fwd_pipe_kernel<T, 8, true> : attn_fwd_pipe_kernel<T, 8, false>;
+    return p.kv_rows ? attn_fwd_pipe_kernel<T, 4, true> : attn_fwd_pipe_kernel<T, 4, false>;
+  }
+};
 }  // namespace
 
 extern "C" int vorta_attn_workspace_bytes(const vorta_attn_args* a, uint64_t* ws_o_bytes, uint64_t* ws_ml_bytes) {
@@ -889,60 +834,7 @@ extern "C" int vorta_attn_plan(const vorta_attn_args* a, int32_t* block_rows_out
 }
 
 extern "C" int vorta_attn_fwd_batch(const vorta_attn_args* args, int32_t n, void* hip_stream) {
-  if (!args || n < 0 || n > MAX_SEGMENTS) return VORTA_EINVAL;
-  MultiParams mp{};
-  int64_t total = 0;
-  int dtype = -1, m = 0;
-  for (int i = 0; i < n; ++i) {
-    Params p{};
-    int block_rows = 0;
-    int rc = fill_params(&args[i], p, block_rows);
-    if (rc != VORTA_OK) return rc;
-    if (p.n_heads == 0 || p.n_groups == 0) continue;
-    // only launches that resolve to the 256-row pipelined kernel can share a grid
-    if (block_rows != 256 || args[i].variant == 1) return VORTA_EUNSUPPORTED;
-    if (dtype >= 0 && dtype != args[i].dtype) return VORTA_EINVAL;
-    dtype = args[i].dtype;
-    p.xcd_remap = 0;
-    mp.seg[m] = p;
-    mp.start[m] = (int)total;
-    total += (int64_t)p.n_groups * p.blocks_per_group * p.n_heads * p.n_splits;
-    if (total > 0x7fffffff) return VORTA_EINVAL;
-    ++m;
-  }
-  if (m == 0) return VORTA_OK;
-  for (int i = m; i <= MAX_SEGMENTS; ++i) mp.start[i] = (int)total;
-  mp.n = m;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (dtype == VORTA_BF16) hipLaunchKernelGGL((attn_fwd_multi_kernel<__bf16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  else hipLaunchKernelGGL((attn_fwd_multi_kernel<_Float16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  for (int i = 0; i < m; ++i) {
-    const Params& p = mp.seg[i];
-    if (p.n_splits > 1) {
-      const int64_t items = (int64_t)p.n_heads * p.n_q;
-      if (dtype == VORTA_BF16)
-        hipLaunchKernelGGL((attn_combine_kernel<__bf16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p);
-      else
-        hipLaunchKernelGGL((attn_combine_kernel<_Float16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p);
-      e = hipGetLastError();
-      if (e != hipSuccess) return vorta_set_hip_error(e);
-    }
-  }
-  return VORTA_OK;
+  return fwd_batch(Family16{}, args, n, hip_stream);
 }
 
-extern "C" int vorta_attn_fwd(const vorta_attn_args* a, void* hip_stream) {
-  Params p{};
-  int block_rows = 0;
-  int rc = fill_params(a, p, block_rows);
-  if (rc != VORTA_OK) return rc;
-  if (p.n_heads == 0 || p.n_groups == 0) return VORTA_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  // variant 0 (auto) = the software-pipelined kernel with LDS-DMA staging, for both workgroup sizes
-  const bool pipe = a->variant != 1;
-  if (a->dtype == VORTA_BF16)
-    return block_rows == 256 ? launch<__bf16, 8>(p, st, pipe) : launch<__bf16, 4>(p, st, pipe);
-  return block_rows == 256 ? launch<_Float16, 8>(p, st, pipe) : launch<_Float16, 4>(p, st, pipe);
-}
+extern "C" int vorta_attn_fwd(const vorta_attn_args* a, void* hip_stream) { return fwd_single(Family16{}, a, hip_stream); }

@@ -43,11 +43,6 @@ struct Params8 {
   float thr;     // p_bias + defer: offset scores above this move the reference point
   int lsum_valu; // row sums by VALU adds (experiment) instead of the ones-tile MFMA
 };
-struct MultiParams8 {
-  Params8 seg[MAX_SEGMENTS];
-  int start[MAX_SEGMENTS + 1];
-  int n;
-};
 
 __device__ __forceinline__ int imax3(int a, int b, int c) { return max(max(a, b), c); }
 
@@ -579,15 +574,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn8_kernel(const Params8 pp) {
 }
 
 template <typename TO>
-__global__ __launch_bounds__(512, 2) void attn8_multi_kernel(const MultiParams8 mp) {
+__global__ __launch_bounds__(512, 2) void attn8_multi_kernel(const MultiOf<Params8> mp) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __shared__ __attribute__((aligned(16))) char smem[SMEM8];
-  const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_SEGMENTS; ++i) s += (i < mp.n && b >= mp.start[i]) ? 1 : 0;
-  const Params8& pp = mp.seg[s];
-  const int wg = live_order(pp.p, b - mp.start[s], mp.start[s + 1] - mp.start[s], true);
+  int wg;
+  const Params8& pp = segment_of(mp, blockIdx.x, wg);
 #ifndef VORTA_MULTI_SWAP
 #define VORTA_MULTI_SWAP 1  /* see attn8_body: which half of the workgroup starts its steps with the VALU part; bit0 the body
                                without row tables, bit1 the body with them.  One box, fp8 step in ms, 0 / 1 / 2 / 3:
@@ -596,42 +587,6 @@ __global__ __launch_bounds__(512, 2) void attn8_multi_kernel(const MultiParams8 
   if (pp.p.kv_rows) attn8_body<TO, 8, true, true, (VORTA_MULTI_SWAP & 2) != 0>(pp, smem, wg);
   else attn8_body<TO, 8, false, true, (VORTA_MULTI_SWAP & 1) != 0>(pp, smem, wg);
 #endif
-}
-
-// Merge the split-key partials: one wave per (head slot, query position).
-template <typename TO>
-__global__ __launch_bounds__(256) void attn8_combine_kernel(const Params8 pp) {
-  const Params& p = pp.p;
-  const int lane = threadIdx.x & 63;
-  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (item >= (int64_t)p.n_heads * p.n_q) return;
-  const int y = (int)(item / p.n_q);
-  const int pos = (int)(item - (int64_t)y * p.n_q);
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  float m = -1e30f;
-  for (int s = 0; s < p.n_splits; ++s) m = fmaxf(m, p.ws_ml[(((int64_t)y * p.n_splits + s) * p.n_q + pos) * 2]);
-  float acc0 = 0.f, acc1 = 0.f, l = 0.f;
-  for (int s = 0; s < p.n_splits; ++s) {
-    const int64_t slot = ((int64_t)y * p.n_splits + s) * p.n_q + pos;
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[slot * 2] - m);
-    l += w * p.ws_ml[slot * 2 + 1];
-    const float2 v = *(const float2*)(p.ws_o + slot * D + lane * 2);
-    acc0 += w * v.x;
-    acc1 += w * v.y;
-  }
-  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
-  const float inv = (pos < q_valid && l > 0.f) ? 1.f / l : 0.f;
-  const float2 sd = *(const float2*)(pp.v_descale + (int64_t)head * pp.v_descale_sh + lane * 2);
-  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int64_t row = q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
-  TO pair[2] = {(TO)(acc0 * inv * sd.x), (TO)(acc1 * inv * sd.y)};
-  char* ob = p.o + (int64_t)head * p.o_sh + lane * 4;
-  *(uint32_t*)(ob + row * p.o_ss) = *(uint32_t*)pair;
-  if (p.dup_rows && pos < p.n_dup_pos) {
-    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)pos * p.n_dup;
-    for (int i = 0; i < p.n_dup; ++i) *(uint32_t*)(ob + (int64_t)dr[i] * p.o_ss) = *(uint32_t*)pair;
-  }
 }
 
 int fill8(const vorta_attn_args* a, const vorta_attn_fp8_ext* ext, Params8& pp, int& block_rows) {
@@ -653,85 +608,34 @@ int fill8(const vorta_attn_args* a, const vorta_attn_fp8_ext* ext, Params8& pp, 
   return VORTA_OK;
 }
 
-template <typename TO>
-int launch8(const Params8& pp, int block_rows, hipStream_t st) {
-  const Params& p = pp.p;
-  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads * p.n_splits;
-  if (total <= 0) return VORTA_OK;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  const dim3 g((unsigned)total);
-#define L8(NW_, TAB_, LM_) hipLaunchKernelGGL((attn8_kernel<TO, NW_, TAB_, LM_>), g, dim3(NW_ * 64), 0, st, pp)
-  if (block_rows == 256) {
-    if (pp.lsum_valu) { if (p.kv_rows) L8(8, true, false); else L8(8, false, false); }
-    else { if (p.kv_rows) L8(8, true, true); else L8(8, false, true); }
-  } else {
-    if (pp.lsum_valu) { if (p.kv_rows) L8(4, true, false); else L8(4, false, false); }
-    else { if (p.kv_rows) L8(4, true, true); else L8(4, false, true); }
-  }
-#undef L8
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  if (p.n_splits > 1) {
-    const int64_t items = (int64_t)p.n_heads * p.n_q;
-    hipLaunchKernelGGL((attn8_combine_kernel<TO>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vorta_set_hip_error(e);
-  }
-  return VORTA_OK;
+template <typename TO, int NW>
+auto kernel8(const Params8& pp) {
+  if (pp.lsum_valu) return pp.p.kv_rows ? attn8_kernel<TO, NW, true, false> : attn8_kernel<TO, NW, false, false>;
+  return pp.p.kv_rows ? attn8_kernel<TO, NW, true, true> : attn8_kernel<TO, NW, false, true>;
 }
+
+struct Family8 {
+  using PP = Params8;
+  const vorta_attn_fp8_ext* ext;
+  int fill(const vorta_attn_args* a, Params8& pp, int& block_rows) const { return fill8(a, ext, pp, block_rows); }
+  bool fusable(const vorta_attn_args&, const Params8& pp) const { return !pp.lsum_valu; }
+  int out_dtype(const vorta_attn_args&) const { return ext->out_dtype; }
+  template <typename TO> static constexpr auto multi = attn8_multi_kernel<TO>;
+  template <typename TO> static auto kernel(const vorta_attn_args&, const Params8& pp, int block_rows) {
+    return block_rows == 256 ? kernel8<TO, 8>(pp) : kernel8<TO, 4>(pp);
+  }
+};
 
 }  // namespace
 
 extern "C" int vorta_attn_fwd_fp8(const vorta_attn_args* a, const vorta_attn_fp8_ext* ext, void* hip_stream) {
   if (ext && ext->struct_size == sizeof(vorta_attn_fp8_ext) && (ext->flags & 2)) return mx_fwd(a, ext, hip_stream);
-  Params8 pp{};
-  int block_rows = 0;
-  int rc = fill8(a, ext, pp, block_rows);
-  if (rc != VORTA_OK) return rc;
-  if (pp.p.n_heads == 0 || pp.p.n_groups == 0) return VORTA_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  return ext->out_dtype == VORTA_BF16 ? launch8<__bf16>(pp, block_rows, st) : launch8<_Float16>(pp, block_rows, st);
+  return fwd_single(Family8{ext}, a, hip_stream);
 }
 
 extern "C" int vorta_attn_fwd_batch_fp8(const vorta_attn_args* args, const vorta_attn_fp8_ext* ext, int32_t n,
                                         void* hip_stream) {
   if (!args || !ext || n < 0 || n > MAX_SEGMENTS) return VORTA_EINVAL;
   if (ext->struct_size == sizeof(vorta_attn_fp8_ext) && (ext->flags & 2)) return mx_fwd_batch(args, ext, n, hip_stream);
-  MultiParams8 mp{};
-  int64_t total = 0;
-  int m = 0;
-  for (int i = 0; i < n; ++i) {
-    Params8 pp{};
-    int block_rows = 0;
-    int rc = fill8(&args[i], ext, pp, block_rows);
-    if (rc != VORTA_OK) return rc;
-    if (pp.p.n_heads == 0 || pp.p.n_groups == 0) continue;
-    if (block_rows != 256 || pp.lsum_valu) return VORTA_EUNSUPPORTED;  // only 256-row launches share a grid
-    pp.p.xcd_remap = 0;
-    mp.seg[m] = pp;
-    mp.start[m] = (int)total;
-    total += (int64_t)pp.p.n_groups * pp.p.blocks_per_group * pp.p.n_heads * pp.p.n_splits;
-    if (total > 0x7fffffff) return VORTA_EINVAL;
-    ++m;
-  }
-  if (m == 0) return VORTA_OK;
-  for (int i = m; i <= MAX_SEGMENTS; ++i) mp.start[i] = (int)total;
-  mp.n = m;
-  hipStream_t st = (hipStream_t)hip_stream;
-  const bool bf = ext->out_dtype == VORTA_BF16;
-  if (bf) hipLaunchKernelGGL((attn8_multi_kernel<__bf16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  else hipLaunchKernelGGL((attn8_multi_kernel<_Float16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  for (int i = 0; i < m; ++i) {
-    const Params8& pp = mp.seg[i];
-    if (pp.p.n_splits > 1) {
-      const int64_t items = (int64_t)pp.p.n_heads * pp.p.n_q;
-      if (bf) hipLaunchKernelGGL((attn8_combine_kernel<__bf16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-      else hipLaunchKernelGGL((attn8_combine_kernel<_Float16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-      e = hipGetLastError();
-      if (e != hipSuccess) return vorta_set_hip_error(e);
-    }
-  }
-  return VORTA_OK;
+  return fwd_batch(Family8{ext}, args, n, hip_stream);
 }

@@ -85,11 +85,6 @@ struct ParamsI8 {
   float p_bias;  // log2 bias of the probabilities (P' = 2^(z - reference + p_bias))
   float etrig;   // binades: a lane whose block exponent exceeds this moves its row's reference point (rare: the range is the scale's)
 };
-struct MultiParamsI8 {
-  ParamsI8 seg[MAX_SEGMENTS];
-  int start[MAX_SEGMENTS + 1];
-  int n;
-};
 
 __device__ __forceinline__ i32x16 mfma_i8(i32x4 a, i32x4 b, i32x16 c) {
   return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
@@ -854,54 +849,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_i8_kernel(const ParamsI8 pp) 
 
 // Several launches fused into ONE grid (the experts of a routed layer), as attn_fwd_multi_kernel
 template <typename T>
-__global__ __launch_bounds__(512, 2) void attn_i8_multi_kernel(const MultiParamsI8 mp) {
+__global__ __launch_bounds__(512, 2) void attn_i8_multi_kernel(const MultiOf<ParamsI8> mp) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __shared__ __attribute__((aligned(16))) char smem[SMEM_I8];
-  const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_SEGMENTS; ++i) s += (i < mp.n && b >= mp.start[i]) ? 1 : 0;
-  const ParamsI8& pp = mp.seg[s];
-  const int wg = live_order(pp.p, b - mp.start[s], mp.start[s + 1] - mp.start[s], true);
+  int wg;
+  const ParamsI8& pp = segment_of(mp, blockIdx.x, wg);
   if (pp.p.kv_rows) attn_i8_body<T, 8, true, NSI8>(pp, smem, wg);
   else attn_i8_body<T, 8, false, NSI8>(pp, smem, wg);
 #endif
-}
-
-// Merge the split-key partials: one wave per (head slot, query position); both partial sums carry the 2^p_bias factor
-template <typename T>
-__global__ __launch_bounds__(256) void attn_i8_combine_kernel(const ParamsI8 pp) {
-  const Params& p = pp.p;
-  const int lane = threadIdx.x & 63;
-  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (item >= (int64_t)p.n_heads * p.n_q) return;
-  const int y = (int)(item / p.n_q);
-  const int pos = (int)(item - (int64_t)y * p.n_q);
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  float m = -1e30f;
-  for (int s = 0; s < p.n_splits; ++s) m = fmaxf(m, p.ws_ml[(((int64_t)y * p.n_splits + s) * p.n_q + pos) * 2]);
-  float acc0 = 0.f, acc1 = 0.f, l = 0.f;
-  for (int s = 0; s < p.n_splits; ++s) {
-    const int64_t slot = ((int64_t)y * p.n_splits + s) * p.n_q + pos;
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[slot * 2] - m);
-    l += w * p.ws_ml[slot * 2 + 1];
-    const float2 v = *(const float2*)(p.ws_o + slot * D + lane * 2);
-    acc0 += w * v.x;
-    acc1 += w * v.y;
-  }
-  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
-  const float inv = (pos < q_valid && l > 0.f) ? 1.f / l : 0.f;
-  const float2 sd = *(const float2*)(pp.v_descale + (int64_t)head * pp.v_descale_sh + lane * 2);
-  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int64_t row = q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
-  T pair[2] = {(T)(acc0 * inv * sd.x), (T)(acc1 * inv * sd.y)};
-  char* ob = p.o + (int64_t)head * p.o_sh + lane * 4;
-  *(uint32_t*)(ob + row * p.o_ss) = *(uint32_t*)pair;
-  if (p.dup_rows && pos < p.n_dup_pos) {
-    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)pos * p.n_dup;
-    for (int i = 0; i < p.n_dup; ++i) *(uint32_t*)(ob + (int64_t)dr[i] * p.o_ss) = *(uint32_t*)pair;
-  }
 }
 
 int fill_i8(const vorta_attn_args* a, const vorta_attn_i8_ext* ext, ParamsI8& pp, int& block_rows) {
@@ -930,80 +885,26 @@ int fill_i8(const vorta_attn_args* a, const vorta_attn_i8_ext* ext, ParamsI8& pp
   return VORTA_OK;
 }
 
-template <typename T>
-int launch_i8(const ParamsI8& pp, int block_rows, hipStream_t st) {
-  const Params& p = pp.p;
-  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads * p.n_splits;
-  if (total <= 0) return VORTA_OK;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  const dim3 g((unsigned)total);
-#define LI8(NW_, TAB_) hipLaunchKernelGGL((attn_i8_kernel<T, NW_, TAB_>), g, dim3(NW_ * 64), 0, st, pp)
-  if (block_rows == 256) { if (p.kv_rows) LI8(8, true); else LI8(8, false); }
-  else { if (p.kv_rows) LI8(4, true); else LI8(4, false); }
-#undef LI8
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  if (p.n_splits > 1) {
-    const int64_t items = (int64_t)p.n_heads * p.n_q;
-    hipLaunchKernelGGL((attn_i8_combine_kernel<T>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vorta_set_hip_error(e);
+struct FamilyI8 {
+  using PP = ParamsI8;
+  const vorta_attn_i8_ext* ext;
+  int fill(const vorta_attn_args* a, ParamsI8& pp, int& block_rows) const { return fill_i8(a, ext, pp, block_rows); }
+  bool fusable(const vorta_attn_args&, const ParamsI8&) const { return true; }
+  int out_dtype(const vorta_attn_args& a) const { return a.dtype; }
+  template <typename T> static constexpr auto multi = attn_i8_multi_kernel<T>;
+  template <typename T> static auto kernel(const vorta_attn_args&, const ParamsI8& pp, int block_rows) {
+    if (block_rows == 256) return pp.p.kv_rows ? attn_i8_kernel<T, 8, true> : attn_i8_kernel<T, 8, false>;
+    return pp.p.kv_rows ? attn_i8_kernel<T, 4, true> : attn_i8_kernel<T, 4, false>;
   }
-  return VORTA_OK;
-}
+};
 
 }  // namespace
 
 extern "C" int vorta_attn_fwd_i8(const vorta_attn_args* a, const vorta_attn_i8_ext* ext, void* hip_stream) {
-  ParamsI8 pp{};
-  int block_rows = 0;
-  int rc = fill_i8(a, ext, pp, block_rows);
-  if (rc != VORTA_OK) return rc;
-  if (pp.p.n_heads == 0 || pp.p.n_groups == 0) return VORTA_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  return a->dtype == VORTA_BF16 ? launch_i8<__bf16>(pp, block_rows, st) : launch_i8<_Float16>(pp, block_rows, st);
+  return fwd_single(FamilyI8{ext}, a, hip_stream);
 }
 
 extern "C" int vorta_attn_fwd_batch_i8(const vorta_attn_args* args, const vorta_attn_i8_ext* ext, int32_t n, void* hip_stream) {
-  if (!args || !ext || n < 0 || n > MAX_SEGMENTS) return VORTA_EINVAL;
-  MultiParamsI8 mp{};
-  int64_t total = 0;
-  int m = 0;
-  int dtype = -1;
-  for (int i = 0; i < n; ++i) {
-    ParamsI8 pp{};
-    int block_rows = 0;
-    int rc = fill_i8(&args[i], ext, pp, block_rows);
-    if (rc != VORTA_OK) return rc;
-    if (pp.p.n_heads == 0 || pp.p.n_groups == 0) continue;
-    if (block_rows != 256) return VORTA_EUNSUPPORTED;  // only 256-row launches share a grid
-    if (dtype >= 0 && dtype != args[i].dtype) return VORTA_EINVAL;
-    dtype = args[i].dtype;
-    pp.p.xcd_remap = 0;
-    mp.seg[m] = pp;
-    mp.start[m] = (int)total;
-    total += (int64_t)pp.p.n_groups * pp.p.blocks_per_group * pp.p.n_heads * pp.p.n_splits;
-    if (total > 0x7fffffff) return VORTA_EINVAL;
-    ++m;
-  }
-  if (m == 0) return VORTA_OK;
-  for (int i = m; i <= MAX_SEGMENTS; ++i) mp.start[i] = (int)total;
-  mp.n = m;
-  hipStream_t st = (hipStream_t)hip_stream;
-  const bool bf = dtype == VORTA_BF16;
-  if (bf) hipLaunchKernelGGL((attn_i8_multi_kernel<__bf16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  else hipLaunchKernelGGL((attn_i8_multi_kernel<_Float16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  for (int i = 0; i < m; ++i) {
-    const ParamsI8& pp = mp.seg[i];
-    if (pp.p.n_splits > 1) {
-      const int64_t items = (int64_t)pp.p.n_heads * pp.p.n_q;
-      if (bf) hipLaunchKernelGGL((attn_i8_combine_kernel<__bf16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-      else hipLaunchKernelGGL((attn_i8_combine_kernel<_Float16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-      e = hipGetLastError();
-      if (e != hipSuccess) return vorta_set_hip_error(e);
-    }
-  }
-  return VORTA_OK;
+  if (!ext) return VORTA_EINVAL;
+  return fwd_batch(FamilyI8{ext}, args, n, hip_stream);
 }

@@ -40,11 +40,6 @@ struct ParamsMx {
   float p_bias;  // log2 bias of the probabilities (P' = 2^(z - reference + p_bias))
   float etrig;   // binades: a key tile whose block exponent exceeds this moves its row's reference point (rare)
 };
-struct MultiParamsMx {
-  ParamsMx seg[MAX_SEGMENTS];
-  int start[MAX_SEGMENTS + 1];
-  int n;
-};
 
 // O^T += V8^T P8^T with block scales on the B operand, as attn_fwd_i8.hip (round 5): scale block s of a column = bytes 16 s ...
 // 16 s + 15 of both lanes of the column = one query row x the 32 keys of key tile s; its E8M0 byte is read from the lane of half s
@@ -549,54 +544,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_mx_kernel(const ParamsMx pp) 
 
 // Several launches fused into ONE grid (the experts of a routed layer), as attn_fwd_multi_kernel
 template <typename T>
-__global__ __launch_bounds__(512, 2) void attn_mx_multi_kernel(const MultiParamsMx mp) {
+__global__ __launch_bounds__(512, 2) void attn_mx_multi_kernel(const MultiOf<ParamsMx> mp) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __shared__ __attribute__((aligned(16))) char smem[SMEM_MX];
-  const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_SEGMENTS; ++i) s += (i < mp.n && b >= mp.start[i]) ? 1 : 0;
-  const ParamsMx& pp = mp.seg[s];
-  const int wg = live_order(pp.p, b - mp.start[s], mp.start[s + 1] - mp.start[s], true);
+  int wg;
+  const ParamsMx& pp = segment_of(mp, blockIdx.x, wg);
   if (pp.p.kv_rows) attn_mx_body<T, 8, true, NSMX>(pp, smem, wg);
   else attn_mx_body<T, 8, false, NSMX>(pp, smem, wg);
 #endif
-}
-
-// Merge the split-key partials: one wave per (head slot, query position); both partial sums carry the 2^p_bias factor
-template <typename T>
-__global__ __launch_bounds__(256) void attn_mx_combine_kernel(const ParamsMx pp) {
-  const Params& p = pp.p;
-  const int lane = threadIdx.x & 63;
-  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (item >= (int64_t)p.n_heads * p.n_q) return;
-  const int y = (int)(item / p.n_q);
-  const int pos = (int)(item - (int64_t)y * p.n_q);
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  float m = -1e30f;
-  for (int s = 0; s < p.n_splits; ++s) m = fmaxf(m, p.ws_ml[(((int64_t)y * p.n_splits + s) * p.n_q + pos) * 2]);
-  float acc0 = 0.f, acc1 = 0.f, l = 0.f;
-  for (int s = 0; s < p.n_splits; ++s) {
-    const int64_t slot = ((int64_t)y * p.n_splits + s) * p.n_q + pos;
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[slot * 2] - m);
-    l += w * p.ws_ml[slot * 2 + 1];
-    const float2 v = *(const float2*)(p.ws_o + slot * D + lane * 2);
-    acc0 += w * v.x;
-    acc1 += w * v.y;
-  }
-  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
-  const float inv = (pos < q_valid && l > 0.f) ? 1.f / l : 0.f;
-  const float2 sd = *(const float2*)(pp.v_descale + (int64_t)head * pp.v_descale_sh + lane * 2);
-  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int64_t row = q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
-  T pair[2] = {(T)(acc0 * inv * sd.x), (T)(acc1 * inv * sd.y)};
-  char* ob = p.o + (int64_t)head * p.o_sh + lane * 4;
-  *(uint32_t*)(ob + row * p.o_ss) = *(uint32_t*)pair;
-  if (p.dup_rows && pos < p.n_dup_pos) {
-    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)pos * p.n_dup;
-    for (int i = 0; i < p.n_dup; ++i) *(uint32_t*)(ob + (int64_t)dr[i] * p.o_ss) = *(uint32_t*)pair;
-  }
 }
 
 int fill_mx(const vorta_attn_args* a, const vorta_attn_fp8_ext* ext, ParamsMx& pp, int& block_rows) {
@@ -620,80 +575,25 @@ int fill_mx(const vorta_attn_args* a, const vorta_attn_fp8_ext* ext, ParamsMx& p
   return VORTA_OK;
 }
 
-template <typename T>
-int launch_mx(const ParamsMx& pp, int block_rows, hipStream_t st) {
-  const Params& p = pp.p;
-  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads * p.n_splits;
-  if (total <= 0) return VORTA_OK;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  const dim3 g((unsigned)total);
-#define LMX(NW_, TAB_) hipLaunchKernelGGL((attn_mx_kernel<T, NW_, TAB_>), g, dim3(NW_ * 64), 0, st, pp)
-  if (block_rows == 256) { if (p.kv_rows) LMX(8, true); else LMX(8, false); }
-  else { if (p.kv_rows) LMX(4, true); else LMX(4, false); }
-#undef LMX
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  if (p.n_splits > 1) {
-    const int64_t items = (int64_t)p.n_heads * p.n_q;
-    hipLaunchKernelGGL((attn_mx_combine_kernel<T>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vorta_set_hip_error(e);
+struct FamilyMx {
+  using PP = ParamsMx;
+  const vorta_attn_fp8_ext* ext;
+  int fill(const vorta_attn_args* a, ParamsMx& pp, int& block_rows) const { return fill_mx(a, ext, pp, block_rows); }
+  bool fusable(const vorta_attn_args&, const ParamsMx&) const { return true; }
+  int out_dtype(const vorta_attn_args& a) const { return a.dtype; }
+  template <typename T> static constexpr auto multi = attn_mx_multi_kernel<T>;
+  template <typename T> static auto kernel(const vorta_attn_args&, const ParamsMx& pp, int block_rows) {
+    if (block_rows == 256) return pp.p.kv_rows ? attn_mx_kernel<T, 8, true> : attn_mx_kernel<T, 8, false>;
+    return pp.p.kv_rows ? attn_mx_kernel<T, 4, true> : attn_mx_kernel<T, 4, false>;
   }
-  return VORTA_OK;
-}
+};
 
 }  // namespace
 
 int vorta_attn::mx_fwd(const vorta_attn_args* a, const vorta_attn_fp8_ext* ext, void* hip_stream) {
-  ParamsMx pp{};
-  int block_rows = 0;
-  int rc = fill_mx(a, ext, pp, block_rows);
-  if (rc != VORTA_OK) return rc;
-  if (pp.p.n_heads == 0 || pp.p.n_groups == 0) return VORTA_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  return a->dtype == VORTA_BF16 ? launch_mx<__bf16>(pp, block_rows, st) : launch_mx<_Float16>(pp, block_rows, st);
+  return fwd_single(FamilyMx{ext}, a, hip_stream);
 }
 
 int vorta_attn::mx_fwd_batch(const vorta_attn_args* args, const vorta_attn_fp8_ext* ext, int32_t n, void* hip_stream) {
-  if (!args || !ext || n < 0 || n > MAX_SEGMENTS) return VORTA_EINVAL;
-  MultiParamsMx mp{};
-  int64_t total = 0;
-  int m = 0;
-  int dtype = -1;
-  for (int i = 0; i < n; ++i) {
-    ParamsMx pp{};
-    int block_rows = 0;
-    int rc = fill_mx(&args[i], ext, pp, block_rows);
-    if (rc != VORTA_OK) return rc;
-    if (pp.p.n_heads == 0 || pp.p.n_groups == 0) continue;
-    if (block_rows != 256) return VORTA_EUNSUPPORTED;  // only 256-row launches share a grid
-    if (dtype >= 0 && dtype != args[i].dtype) return VORTA_EINVAL;
-    dtype = args[i].dtype;
-    pp.p.xcd_remap = 0;
-    mp.seg[m] = pp;
-    mp.start[m] = (int)total;
-    total += (int64_t)pp.p.n_groups * pp.p.blocks_per_group * pp.p.n_heads * pp.p.n_splits;
-    if (total > 0x7fffffff) return VORTA_EINVAL;
-    ++m;
-  }
-  if (m == 0) return VORTA_OK;
-  for (int i = m; i <= MAX_SEGMENTS; ++i) mp.start[i] = (int)total;
-  mp.n = m;
-  hipStream_t st = (hipStream_t)hip_stream;
-  const bool bf = dtype == VORTA_BF16;
-  if (bf) hipLaunchKernelGGL((attn_mx_multi_kernel<__bf16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  else hipLaunchKernelGGL((attn_mx_multi_kernel<_Float16>), dim3((unsigned)total), dim3(512), 0, st, mp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vorta_set_hip_error(e);
-  for (int i = 0; i < m; ++i) {
-    const ParamsMx& pp = mp.seg[i];
-    if (pp.p.n_splits > 1) {
-      const int64_t items = (int64_t)pp.p.n_heads * pp.p.n_q;
-      if (bf) hipLaunchKernelGGL((attn_mx_combine_kernel<__bf16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-      else hipLaunchKernelGGL((attn_mx_combine_kernel<_Float16>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, pp);
-      e = hipGetLastError();
-      if (e != hipSuccess) return vorta_set_hip_error(e);
-    }
-  }
-  return VORTA_OK;
+  return fwd_batch(FamilyMx{ext}, args, n, hip_stream);
 }

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -135,8 +135,8 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     a.struct_size = C.sizeof(_C.AttnArgs)
     a.dtype = _C.VORTA_FP8E4M3 if fp8 else _DT[q.dtype]
     a._ext = None
-    a._mixed = mixed
-    a._i8 = i8
+    a._family = _FAMILIES["i8" if i8 else "fp8" if fp8 else "mx" if mixed else "16"]
+    a._out_type = "_Float16" if out.dtype == torch.float16 else "__bf16"  # T of the kernel symbols
     if i8:
         ext = _C.AttnI8Ext()
         ext.struct_size = C.sizeof(_C.AttnI8Ext)
@@ -235,31 +235,53 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     return a, ws
 
 
+class _Family(NamedTuple):
+    one: str     # entry point of a single launch
+    batch: str   # entry point of a fused grid
+    kernel: str  # kernel symbol of a single launch (the Timeline's name; the rocprofv3 tables under profiles/)
+    multi: str   # kernel symbol of a fused grid
+
+
+# the four kernel families of csrc/, one per source; the e4m3 ones take `_ext` after the args (the mixed one is
+# vorta_attn_fwd_fp8 with ext->flags bit1)
+_FAMILIES = {
+    "16": _Family("vorta_attn_fwd", "vorta_attn_fwd_batch", "attn_fwd_pipe_kernel<{t},{nw},{tab}>", "attn_fwd_multi_kernel<{t}>"),
+    "fp8": _Family("vorta_attn_fwd_fp8", "vorta_attn_fwd_batch_fp8", "attn8_kernel<{t},{nw},{tab},{lmfma}>", "attn8_multi_kernel<{t}>"),
+    "mx": _Family("vorta_attn_fwd_fp8", "vorta_attn_fwd_batch_fp8", "attn_mx_kernel<{t},{nw},{tab}>", "attn_mx_multi_kernel<{t}>"),
+    "i8": _Family("vorta_attn_fwd_i8", "vorta_attn_fwd_batch_i8", "attn_i8_kernel<{t},{nw},{tab}>", "attn_i8_multi_kernel<{t}>"),
+}
+
+
+def _ext(a) -> tuple:
+    return () if a._ext is None else (C.byref(a._ext),)
+
+
 def _launch_one(a):
-    if a._i8:
-        _C.check(_C.lib().vorta_attn_fwd_i8(C.byref(a), C.byref(a._ext), _stream()), "vorta_attn_fwd_i8")
-    elif a._ext is not None:
-        _C.check(_C.lib().vorta_attn_fwd_fp8(C.byref(a), C.byref(a._ext), _stream()), "vorta_attn_fwd_fp8")
-    else:
-        _C.check(_C.lib().vorta_attn_fwd(C.byref(a), _stream()), "vorta_attn_fwd")
+    name = a._family.one
+    _C.check(getattr(_C.lib(), name)(C.byref(a), *_ext(a), _stream()), name)
 
 
 def _plan(a) -> Tuple[int, int, str]:
     br, nwg, kid = C.c_int32(), C.c_int64(), C.c_int32()
     _C.check(_C.lib().vorta_attn_plan(C.byref(a), C.byref(br), C.byref(nwg), C.byref(kid)), "vorta_attn_plan")
-    tname = "_Float16" if a.dtype == _C.VORTA_FP16 else "__bf16"
     nw, kk = kid.value // 16, kid.value % 16
-    if a._i8:
-        return br.value, nwg.value, f"attn_i8_kernel<{tname},{nw},{'true' if kk & 2 else 'false'}>"
-    if a._ext is not None:
-        tname = "_Float16" if a._ext.out_dtype == _C.VORTA_FP16 else "__bf16"
-        if a._ext.flags & 2:
-            return br.value, nwg.value, f"attn_mx_kernel<{tname},{nw},{'true' if kk & 2 else 'false'}>"
-        return br.value, nwg.value, (f"attn8_kernel<{tname},{nw},{'true' if kk & 2 else 'false'},"
-                                     f"{'false' if a._ext.flags & 1 else 'true'}>")
-    sym = (f"attn_fwd_pipe_kernel<{tname},{nw},{'true' if kk & 2 else 'false'}>" if kk & 1
-           else f"attn_fwd_kernel<{tname},{nw}>")
-    return br.value, nwg.value, sym
+    fmt = a._family.kernel if kk & 1 else "attn_fwd_kernel<{t},{nw}>"  # (not pipelined: the 16-bit variant 1)
+    lmfma = "false" if a._ext is not None and a._ext.flags & 1 else "true"
+    return br.value, nwg.value, fmt.format(t=a._out_type, nw=nw, tab="true" if kk & 2 else "false", lmfma=lmfma)
+
+
+def _timed(launch, tag: str, flops: float, args, sym: Optional[str] = None) -> None:
+    """launch() the vorta_attn_args `args`; with a Timeline set, between two HIP events, recorded with their workgroups
+    under `sym` (default: the kernel of the single launch args[0])"""
+    if _timeline is None:
+        launch()
+        return
+    plans = [_plan(a) for a in args]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    _timeline.records.append((tag, sym or plans[0][2], sum(nwg for _, nwg, _ in plans), flops, e0, e1))
 
 
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, tag: str = "",
@@ -267,15 +289,7 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tenso
     """vorta_attn_fwd (include/vorta_hip.h); keyword arguments as `_attn_args`.  q_rows/kv_rows/dup_rows: int32; a
     leading head-slot axis is optional (2-D q_rows = per head slot, 1-D = shared)."""
     a, ws = _attn_args(q, k, v, out, **kw)
-    if _timeline is not None:
-        _, nwg, sym = _plan(a)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _launch_one(a)
-        e1.record()
-        _timeline.records.append((tag, sym, nwg, flops, e0, e1))
-        return
-    _launch_one(a)
+    _timed(lambda: _launch_one(a), tag, flops, [a])
     # `ws` may be released now: the caching allocator is stream ordered and the launch is on this stream
 
 
@@ -312,7 +326,7 @@ def attn_fwd_batch(calls) -> None:
         return
 
     def fusable_one(a):
-        return _plan(a)[0] == 256 and a.variant != 1 and not (a._ext is not None and not a._i8 and a._ext.flags & 1)
+        return _plan(a)[0] == 256 and a.variant != 1 and not (isinstance(a._ext, _C.AttnFp8Ext) and a._ext.flags & 1)
 
     ok = [fusable_one(a) for a, _, _, _ in built]
     fuse_all = 1 < len(built) <= MAX_FUSED and all(ok)
@@ -332,50 +346,18 @@ def attn_fwd_batch(calls) -> None:
 
 
 def attn_fwd_batch_built(built, fuse: bool = True) -> None:
-    fusable = fuse and len(built) > 1
-    if not fusable:
+    if not (fuse and len(built) > 1):
         for a, ws, tag, flops in built:
-            if _timeline is not None:
-                _, nwg, sym = _plan(a)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _launch_one(a)
-                e1.record()
-                _timeline.records.append((tag, sym, nwg, flops, e0, e1))
-            else:
-                _launch_one(a)
+            _timed(lambda: _launch_one(a), tag, flops, [a])
         return
-    arr = (_C.AttnArgs * len(built))(*[a for a, _, _, _ in built])
-    ext = built[0][0]._ext  # one operand set per layer: every fused launch shares v_descale and the options
-    i8 = built[0][0]._i8
-    if any(a._i8 != i8 for a, _, _, _ in built) or (not i8 and any(
-            (a._ext is None) != (ext is None) or (ext is not None and (a._ext.flags & 2) != (ext.flags & 2)) for a, _, _, _ in built)):
+    args = [a for a, _, _, _ in built]
+    fam = args[0]._family
+    if any(a._family is not fam for a in args):
         raise ValueError("a fused grid is all 16-bit, all e4m3, all mixed-precision or all int8-score")
-
-    def go():
-        if i8:
-            _C.check(_C.lib().vorta_attn_fwd_batch_i8(arr, C.byref(ext), len(built), _stream()), "vorta_attn_fwd_batch_i8")
-        elif ext is not None:
-            _C.check(_C.lib().vorta_attn_fwd_batch_fp8(arr, C.byref(ext), len(built), _stream()), "vorta_attn_fwd_batch_fp8")
-        else:
-            _C.check(_C.lib().vorta_attn_fwd_batch(arr, len(built), _stream()), "vorta_attn_fwd_batch")
-
-    if _timeline is not None:
-        if i8:
-            sym = f"attn_i8_multi_kernel<{'_Float16' if built[0][0].dtype == _C.VORTA_FP16 else '__bf16'}>"
-        elif ext is not None:
-            sym = ("attn_mx_multi_kernel" if ext.flags & 2 else "attn8_multi_kernel") + \
-                f"<{'_Float16' if ext.out_dtype == _C.VORTA_FP16 else '__bf16'}>"
-        else:
-            sym = f"attn_fwd_multi_kernel<{'_Float16' if built[0][0].dtype == _C.VORTA_FP16 else '__bf16'}>"
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        _timeline.records.append(("+".join(t for _, _, t, _ in built), sym,
-                                  sum(_plan(a)[1] for a, _, _, _ in built), sum(f for _, _, _, f in built), e0, e1))
-        return
-    go()
+    arr = (_C.AttnArgs * len(args))(*args)
+    # one operand set per layer: every fused launch shares v_descale and the options (the first launch's `_ext`)
+    go = lambda: _C.check(getattr(_C.lib(), fam.batch)(arr, *_ext(args[0]), len(args), _stream()), fam.batch)
+    _timed(go, "+".join(t for _, _, t, _ in built), sum(f for _, _, _, f in built), args, fam.multi.format(t=args[0]._out_type))
 
 
 FP8_OPTS: dict = {}  # process-wide defaults of the fp8 kernels' options (p_bias, defer, flags); experiments only
