@@ -270,9 +270,9 @@ def test_config3_one_rank_of_eight_at_full_size():
 def test_config4_one_rank_of_eight_fp8_at_full_size():
     """BASELINE configs[4]: Wan-2.1 14B 81x720x1280, Ulysses over 8 GPUs, fp8 contractions.  One rank's share -- 5 of the
     40 heads over the whole S = 75 600 sequence in the zero-copy receive layout, converted to e4m3 ONCE per buffer
-    (UlyssesLayout.fp8_views) -- against the bf16 kernels on the same layout: gate (ii) of tests/test_hip_fp8.py."""
+    (UlyssesLayout.fp8_head_views) -- against the bf16 kernels on the same layout: gate (ii) of tests/test_hip_fp8.py."""
     import math
-    from vorta_amd.routed import HeadRouting, RoutedGeometry, routed_attention
+    from vorta_amd.routed import AttnOperands, HeadRouting, RoutedGeometry, routed_attention
     from vorta_amd.ulysses import UlyssesLayout
     dtype = torch.bfloat16
     H, P, rank = 40, 8, 3
@@ -291,9 +291,9 @@ def test_config4_one_rank_of_eight_fp8_at_full_size():
     views = [lay.head_view(b) for b in bufs]
     ref, out = lay.new_buffer(), lay.new_buffer()
     routed_attention(*views, route, geom, model="wan", out=lay.head_view(ref), fp8=False)
-    q8, k8, v8, vd, f8 = lay.fp8_views(bufs)
+    q8, k8, v8, vd, f8 = lay.fp8_head_views(bufs)
     assert f8.q.shape == (1, lay.rows_total, 128) and vd.shape == (Hl, 128)
-    routed_attention(*views, route, geom, model="wan", out=lay.head_view(out), fp8=False, fp8_views=(q8, k8, v8, vd))
+    routed_attention(*views, route, geom, model="wan", out=lay.head_view(out), operands=AttnOperands("fp8", q8, k8, v8, vd))
     torch.cuda.synchronize()
     rm = lay.row_map.long()
     a, b = lay.head_view(out)[:, rm[:S]].float(), lay.head_view(ref)[:, rm[:S]].float()  # (Hl, S, D) in token order
@@ -310,7 +310,7 @@ def test_hunyuan_129f_fp8_with_text_and_biased_keys_at_full_size():
     3-sigma common component: operator PSNR >= 40 dB per expert against the fp16 kernels, valid text rows included; the
     padded text rows are exactly zero."""
     import math
-    from vorta_amd.routed import HeadRouting, RoutedGeometry, routed_attention
+    from vorta_amd.routed import AttnOperands, HeadRouting, RoutedGeometry, routed_attention
     from vorta_amd.ulysses import UlyssesLayout
     dtype = torch.float16
     H, P, rank = 24, 8, 2
@@ -335,11 +335,11 @@ def test_hunyuan_129f_fp8_with_text_and_biased_keys_at_full_size():
     views = [lay.head_view(b) for b in bufs]
     ref, out = lay.new_buffer(), lay.new_buffer()
     routed_attention(*views, route, geom, model="hunyuan", text_len=T, text_valid=te, out=lay.head_view(ref), fp8=False)
-    q8, k8, v8, vd, f8 = lay.fp8_views(bufs)
+    q8, k8, v8, vd, f8 = lay.fp8_head_views(bufs)
     c = f8.k_center()
     assert vd.shape == (Hl, 128) and float((c - bias).abs().max()) < 0.5  # each slot's own centre, near its own bias
-    routed_attention(*views, route, geom, model="hunyuan", text_len=T, text_valid=te, out=lay.head_view(out), fp8=False,
-                     fp8_views=(q8, k8, v8, vd))
+    routed_attention(*views, route, geom, model="hunyuan", text_len=T, text_valid=te, out=lay.head_view(out),
+                     operands=AttnOperands("fp8", q8, k8, v8, vd))
     torch.cuda.synchronize()
     rm = lay.row_map.long()
     a, b = lay.head_view(out)[:, rm].float(), lay.head_view(ref)[:, rm].float()  # (Hl, S + T, D) in token order
@@ -363,7 +363,7 @@ def test_hunyuan_129f_fp8pv_one_rank_of_eight_at_full_size():
     the video rows, >= 42 dB on the valid text rows, against the fp16 kernels; padded text rows exactly zero."""
     import math
     from vorta_amd import ops
-    from vorta_amd.routed import HeadRouting, RoutedGeometry, routed_attention
+    from vorta_amd.routed import AttnOperands, HeadRouting, RoutedGeometry, routed_attention
     from vorta_amd.ulysses import UlyssesLayout
     dtype = torch.float16
     H, P, rank = 24, 8, 2
@@ -401,8 +401,8 @@ def test_hunyuan_129f_fp8pv_one_rank_of_eight_at_full_size():
     for j, c in enumerate(chunks):
         ops.fp8_v_convert(c, amax, v8[j * Hl * Sl:(j + 1) * Hl * Sl].view(Hl, Sl, 128), v_descale=vd)
     ops.fp8_v_convert(texts, amax, v8[lay.rows_video:].as_strided((Hl, T, 128), (Sl * 128, 128, 1)))
-    routed_attention(*views, route, geom, model="hunyuan", text_len=T, text_valid=te, out=lay.head_view(out), fp8=False,
-                     fp8_views=(views[0], views[1], lay.head_view(v8), vd))
+    routed_attention(*views, route, geom, model="hunyuan", text_len=T, text_valid=te, out=lay.head_view(out),
+                     operands=AttnOperands("fp8pv", views[0], views[1], lay.head_view(v8), vd))
     torch.cuda.synchronize()
     rm = lay.row_map.long()
     a, b = lay.head_view(out)[:, rm].float(), lay.head_view(ref)[:, rm].float()

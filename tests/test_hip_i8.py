@@ -371,7 +371,7 @@ def test_auto8_flags_heavy_tailed_heads_and_each_head_equals_the_kernel_it_was_g
     the two heavy-tailed ones are flagged; under "auto8" every head's output is BIT FOR BIT what the precision it was routed to
     writes for it ("i8pv" for the unflagged, "fp8pv" for the flagged), whatever expert it belongs to."""
     from vorta_amd import ops
-    from vorta_amd.routed import HeadRouting, RoutedGeometry, routed_attention
+    from vorta_amd.routed import AttnOperands, HeadRouting, RoutedGeometry, routed_attention
     dev = torch.device("cuda")
     fams = ["white", "student_t3", "smooth", "student_t3", "outlier_w"]
     latent, q, k, v = _auto8_case(dev, fams)
@@ -395,7 +395,8 @@ def test_auto8_flags_heavy_tailed_heads_and_each_head_equals_the_kernel_it_was_g
             assert torch.equal(outs["auto8"][0, h], want), (experts, h, f)
     # the form the sequence-parallel path uses: converted views + 16-bit keys + flags handed in; flags through a row map
     v8, vd, _ = ops.fp8_quantize_v(v[0])
-    o_views = routed_attention(q, k, v, routing, geom, model="wan", fp8=False, fp8_views=(q[0], i8.k8, v8, vd, i8, k[0], flags))
+    o_views = routed_attention(q, k, v, routing, geom, model="wan",
+                               operands=AttnOperands("auto8", q[0], i8.k8, v8, vd, i8, k[0], flags))
     assert torch.equal(o_views, outs["auto8"])
     perm = torch.randperm(q.shape[2], device=dev)
     inv = torch.empty_like(perm)

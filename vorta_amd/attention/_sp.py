@@ -11,11 +11,11 @@ from typing import Optional
 import torch
 
 from .. import ops
-from ..routed import HeadRouting, geometry_for, routed_attention
+from ..routed import HeadRouting, geometry_for, precision_of, routed_attention
 from ..ulysses import SP_STATE
 from ..ulysses.state import PLACEMENTS, default_sp_groups, resolve_placement  # noqa: F401  (one rule for the processors and bench.py)
-from ..ulysses.engine import (UlyssesLayout, VWire, balanced_head_order, balanced_placement, exchange_and_attend, split_align, split_placement,
-                              slot_groups)
+from ..ulysses.engine import (RecvOperands, UlyssesLayout, auto_kv_splits, balanced_head_order, balanced_placement, exchange_and_attend,
+                              split_align, split_placement, slot_groups)
 
 _LAYOUTS = {}
 _BUFFERS = {}  # receive buffers per (geometry, head-slot count): kept when the layout cache is trimmed, least recently used out
@@ -37,8 +37,7 @@ SP_GROUPS = SP_GROUPS if SP_GROUPS == "auto" else max(1, int(SP_GROUPS))
 def _sp_groups(H: int, P: int) -> int:
     if SP_GROUPS != "auto":
         return int(SP_GROUPS)
-    from .. import routed as _routed
-    return default_sp_groups(H // max(P, 1), _routed.DEFAULT_FP8)
+    return default_sp_groups(H // max(P, 1), precision_of(None))
 # e4m3 attention under sequence parallelism: v crosses the links as e4m3 (ulysses/engine.py VWire); VORTA_DEBUG=sp_v_wire=0 keeps
 # the 16-bit exchange with the receive-side conversion (A/B; same bytes in the operand buffers either way)
 SP_V_WIRE = __import__("vorta_amd._debug", fromlist=["flag"]).flag("sp_v_wire", "1") != "0"
@@ -56,38 +55,6 @@ SP_PLACEMENT = __import__("os").environ.get("VORTA_SP_PLACEMENT", "auto")
 # of workgroups (a rank whose one or two heads leave the chip under one round of workgroups: small models on many ranks;
 # changes the summation order -- ulysses/engine.py, bench.py --kv-splits)
 SP_KV_SPLITS = __import__("os").environ.get("VORTA_SP_KV_SPLITS", "1")
-
-
-class _SpBuffers:
-    """layout + receive buffers of one (H, S, T, D, dtype) geometry; the e4m3 operand buffers are allocated on first use"""
-
-    def __init__(self, lay):
-        self.lay = lay
-        self.bufs = [lay.new_buffer() for _ in range(4)]
-        self.f8 = None
-        self.vwire = None
-        self._wire = None
-        self.i8 = None
-        self.group_ops = {}  # the operand buffers as each slot group sees them (UlyssesLayout.group_operands)
-
-    def fp8(self, mode=True):
-        """(operands, v wire) of the e4m3 path; mode "fp8pv" (16-bit scores) / "i8pv" (int8 scores: + `self.i8`, the int8 key
-        buffers): only the e4m3 receive buffer of v"""
-        if mode == "i8pv" and self.i8 is None:
-            self.i8 = self.lay.i8_operands()
-        if mode in ("fp8pv", "i8pv"):
-            if self.vwire is None or self.f8 is not None:
-                self.f8 = None
-                self.vwire = VWire(self.lay, torch.zeros((self.lay.rows_total, self.lay.D), dtype=torch.uint8,
-                                                         device=self.lay.device))
-            return None, self.vwire
-        if self.f8 is None:
-            self.f8 = self.lay.fp8_operands()
-            self._wire = None
-        if self._wire != SP_V_WIRE:  # (the switch may change between calls in A/B runs: the wire follows it)
-            self.vwire = VWire(self.lay, self.f8.v[0]) if SP_V_WIRE else None
-            self._wire = SP_V_WIRE
-        return self.f8, self.vwire
 
 
 def _layout(H, S, T, D, device, dtype, counts=None, extra_slots=0):
@@ -108,7 +75,7 @@ def _layout(H, S, T, D, device, dtype, counts=None, extra_slots=0):
         # sees several resolutions or text lengths keeps the `_buffer_set_limit` most recently used sets (every slot count of one geometry fits)
         while len(_BUFFERS) >= _buffer_set_limit(H, P):
             _BUFFERS.pop(next(iter(_BUFFERS)))
-        _BUFFERS[bkey] = _SpBuffers(lay)
+        _BUFFERS[bkey] = RecvOperands(lay)
     else:
         _BUFFERS[bkey] = _BUFFERS.pop(bkey)  # most recently used last
     return lay, _BUFFERS[bkey]
@@ -187,7 +154,6 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
     placement, order, counts, parts = place_heads(experts, cost, P, S, dense_only)
     sp_attention.last_placement = placement  # (what a test or a curious caller reads back)
     lay, sb = _layout(H, S, T, D, q.device, q.dtype, counts, extra_slots=len(order) - H)
-    bufs = sb.bufs
     groups = min(_sp_groups(H, P), min(counts))
     sg = slot_groups(lay.Hl, groups)
     sgs, _, _ = lay.grouping(len(sg))  # a slot group is a receive layout of its own inside the buffers (ulysses/engine.py)
@@ -202,45 +168,21 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
     ranges_of = lambda g0, g1: tuple((i - g0,) + tuple(local_parts[i]) for i in range(g0, g1) if local_parts[i] is not None)
     kv_splits = 1
     if not dense_only and SP_KV_SPLITS != "1":
-        if SP_KV_SPLITS == "auto":
-            rows = {0: S + T, 1: s_low + T, 2: S}
-            wgs = sum(-(-rows[int(x)] // 256) for x in local)
-            kv_splits = max(1, min(8, round(768 / max(wgs, 1)))) if wgs < 384 else 1
-        else:
-            kv_splits = max(1, int(SP_KV_SPLITS))
+        kv_splits = auto_kv_splits(local, S, T, s_low) if SP_KV_SPLITS == "auto" else max(1, int(SP_KV_SPLITS))
 
     # the precision switch (set_attention_precision / VORTA_ATTENTION_PRECISION) is about the ROUTED operator; dense
     # attention -- --native_attention, the PSNR reference -- stays in the dtype of q,k,v on one GPU and under SP alike
-    from .. import routed as _routed
-    fp8 = _routed.DEFAULT_FP8 if not dense_only else False  # False, True (all e4m3), "fp8pv" (16-bit scores), "i8pv" (int8)
-    auto8 = fp8 == "auto8"
-    f8, vwire = sb.fp8("i8pv" if auto8 else fp8) if fp8 else (None, None)
-    if vwire is not None:
-        vwire.lay = lay  # the layouts of one slot count share the buffers; the head offsets are this layer's
+    precision = precision_of(None) if not dense_only else "native"
+    vwire = sb.begin(lay, precision, SP_V_WIRE or precision != "fp8")  # (SP_V_WIRE: "fp8" only; the others always send e4m3 v)
 
     def attend(g0, g1, gi):
-        grp = sgs[gi]
-        sub = grp.lay
-        b = [grp.buffer(x) for x in bufs]
-        qv, kv, vv, ov = (sub.head_view(x) for x in b)
-        rm = sub.row_map
-        views = None
-        if fp8 == "i8pv" or auto8:  # k of the slot group that has landed -> int8 (q by the kernel); v arrived as e4m3
-            i8 = sub.i8_views(b, lay.group_operands(grp, sb.i8, sb.group_ops))
-            views = (qv, i8.k8, grp.head_view(vwire.buf), vwire.descale(grp), i8)
-            if auto8:  # + the 16-bit keys as they landed and the group's tail flags: each head to the kernel that holds it
-                views += (kv, ops.i8_tail_flags(i8.k8, row_map=rm[:S + T]))
-        elif fp8 == "fp8pv":  # q, k as they landed; v arrived as e4m3 (converted on the send side)
-            views = (qv, kv, grp.head_view(vwire.buf), vwire.descale(grp))
-        elif fp8:  # the slot group that has landed is converted while the next one is in flight
-            q8, k8, v8, vd, _ = sub.fp8_views(b, out=lay.group_operands(grp, f8, sb.group_ops), vwire=vwire,
-                                              v_descale=None if vwire is None else vwire.descale(grp))
-            views = (q8, k8, v8, vd)
+        qv, kv, vv, ov = (sgs[gi].head_view(b) for b in sb.bufs)
         if dense_only:
+            rm = sgs[gi].lay.row_map
             ops.attn_fwd(qv, kv, vv, ov, n_q=S + T, n_kv=S + te, q_valid=S + te, q_rows=rm[:S + T], kv_rows=rm[:S + te])
         else:
             routed_attention(qv, kv, vv, _routing(tuple(local[g0:g1]), q.device, ranges_of(g0, g1)), geoms[gi],
-                             model=model, text_len=T, text_valid=te, out=ov, fp8=False, fp8_views=views,
+                             model=model, text_len=T, text_valid=te, out=ov, operands=sb.operands(sgs[gi]),
                              kv_splits=kv_splits)
 
     def prepare():
@@ -253,7 +195,7 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
 
     # the received heads are written straight into the (1, N, H, D) result the output projection reads
     buf = torch.empty((1, N, H, D), dtype=q.dtype, device=q.device)
-    exchange_and_attend(lay, shards, bufs, order, texts, sg, attend,
+    exchange_and_attend(lay, shards, sb.bufs, order, texts, sg, attend,
                         buf[0, :Sl].transpose(0, 1), buf[0, Sl:].transpose(0, 1) if T else None, vwire=vwire,
                         prepare=prepare, parts=parts)
     return buf

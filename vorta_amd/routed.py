@@ -10,7 +10,7 @@ head gathers (hunyuan.py:612-640), pooled copies (coreset_select.py:68-124), til
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -216,6 +216,64 @@ def set_attention_precision(precision: str, *, measurement_only: bool = False) -
     if precision not in PRODUCT_PRECISIONS:
         raise ValueError(f"precision is one of {PRODUCT_PRECISIONS}")
     DEFAULT_FP8 = precision if precision in ("fp8pv", "i8pv", "auto8") else False
+
+
+PRECISIONS = ("native", "fp8", "fp8pv", "i8pv", "auto8")
+
+
+def precision_of(fp8) -> str:
+    """the precision name of an `fp8=` value: None = the process default (DEFAULT_FP8), False = "native", True = "fp8"
+    (both contractions in e4m3), or a name of PRECISIONS"""
+    fp8 = DEFAULT_FP8 if fp8 is None else fp8
+    if isinstance(fp8, str) and fp8 not in PRECISIONS:
+        raise ValueError(f"attention precision {fp8!r}: one of {PRECISIONS}")
+    return fp8 if isinstance(fp8, str) else "fp8" if fp8 else "native"
+
+
+class AttnOperands(NamedTuple):
+    """What one precision hands the attention kernels: q, k, v as the launches read them, `v_descale` of an e4m3 v, `i8`
+    the I8Operands of int8 keys; "auto8" adds the 16-bit keys `k16` and the heads' tail flags `tail` (ops.i8_tail_flags)."""
+    precision: str
+    q: torch.Tensor
+    k: torch.Tensor
+    v: torch.Tensor
+    v_descale: Optional[torch.Tensor] = None
+    i8: Optional["ops.I8Operands"] = None
+    k16: Optional[torch.Tensor] = None
+    tail: Optional[torch.Tensor] = None
+
+    def kwargs(self, scale: Optional[float]) -> dict:  # of ops.attn_fwd ("auto8": its int8-score launch)
+        return dict(q=self.q, k=self.k, v=self.v, scale=scale, v_descale=self.v_descale, i8=self.i8)
+
+    def tail_kwargs(self, scale: Optional[float]) -> dict:  # "auto8": the 16-bit-score launch of the flagged heads
+        return dict(q=self.q, k=self.k16, v=self.v, scale=scale, v_descale=self.v_descale)
+
+
+def prepare_operands(precision: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float],
+                     fp8_operands=None, video_tokens: int = 0) -> AttnOperands:
+    """the operands of a one-GPU call: (H,S,D) q, k, v converted for `precision`.  `fp8_operands`: buffers to reuse -- an
+    ops.Fp8Operands ("fp8"), the tuple of ops.fp8_quantize_v ("fp8pv") or (that tuple, ops.I8Operands) ("i8pv", "auto8")"""
+    reuse = isinstance(fp8_operands, tuple)
+    if precision in ("i8pv", "auto8"):
+        # int8 scores: k -> int8 rows (centred, balanced, one scale per head) + a float bias per row, v -> e4m3; q is centred,
+        # balanced and rounded by the attention kernel itself.  "auto8": per head, int8 scores where the head's int8 keys
+        # resolve their bulk, 16-bit scores where they do not (heavy tails).  The choice is made on the device (the tail
+        # flags here, ops.split_heads over every expert's head list): two fused launches per layer, one of them usually over
+        # empty lists (its workgroups exit in their first instruction), no host synchronisation
+        vo, ko = fp8_operands if reuse and len(fp8_operands) == 2 else (None, None)
+        v8, vd, _ = ops.fp8_quantize_v(v, out=vo)
+        i8 = ops.i8_quantize_k(q, k, out=ko)
+        tail = ops.i8_tail_flags(i8.k8) if precision == "auto8" else None
+        return AttnOperands(precision, q, i8.k8, v8, vd, i8, None if tail is None else k, tail)
+    if precision == "fp8pv":  # scores in 16 bits, P V in e4m3: only v is converted (exact per-channel abs-max, one pass + one)
+        v8, vd, _ = ops.fp8_quantize_v(v, out=fp8_operands if reuse and len(fp8_operands) == 3 else None)
+        return AttnOperands(precision, q, k, v8, vd)
+    if precision == "fp8":
+        f8 = ops.fp8_quantize_qkv(q, k, v, scale, out=fp8_operands, center_k=FP8_CENTER_K, video_tokens=video_tokens)
+        return AttnOperands(precision, f8.q, f8.k, f8.v, f8.v_descale)
+    return AttnOperands("native", q, k, v)
+
+
 _SIDE_STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
 
 
@@ -230,10 +288,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                      geom: RoutedGeometry, *, model: str, text_len: int = 0, text_valid: int = 0,
                      out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
                      concurrent: bool = False, fused: bool = True, sliding_block_rows: int = 0,
-                     expert_outs: Optional[Sequence[torch.Tensor]] = None, fp8: Optional[bool] = None,
-                     fp8_operands: Optional[ops.Fp8Operands] = None,
-                     fp8_views: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None,
-                     kv_splits: int = 1) -> torch.Tensor:
+                     expert_outs: Optional[Sequence[torch.Tensor]] = None, fp8=None, fp8_operands=None,
+                     operands: Optional[AttnOperands] = None, kv_splits: int = 1) -> torch.Tensor:
     """q,k,v: (1,H,S+T,D) [hunyuan: video then text] or (1,H,S,D) [wan].  Returns (1,H,S+T,D).
 
     hunyuan: hunyuan.py:556-605 (TripleEval.__call__ steps 5.1-5.4);  wan: wan.py:351-383.
@@ -245,11 +301,11 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     hundred workgroups on 256 CUs when only H/P heads are local) is filled by the next expert's workgroups.
     expert_outs: one output tensor per expert instead of `out` (heads may then appear under several experts).
     fp8=True: both contractions in e4m3 (BASELINE.json configs[4]; no reference counterpart): q,k,v are converted once
-    per call (vorta_fp8_quantize_qkv, or `fp8_operands` to reuse buffers) and every expert launch reads the e4m3
-    copies; the coreset ranking still reads the 16-bit q/k (coreset_select.py:98-105 ranks in the input dtype).
-    fp8=None follows the process-wide default (`set_attention_precision`, VORTA_ATTENTION_PRECISION).
-    fp8_views = (q8, k8, v8, v_descale): e4m3 views with the geometry of q,k,v that were converted elsewhere (the
-    sequence-parallel path converts the receive buffers once, vorta_amd/ulysses/engine.py).
+    per call (`prepare_operands`, `fp8_operands` to reuse buffers) and every expert launch reads the e4m3 copies; the
+    coreset ranking still reads the 16-bit q/k (coreset_select.py:98-105 ranks in the input dtype).  Other values:
+    `precision_of`; fp8=None follows the process-wide default (`set_attention_precision`, VORTA_ATTENTION_PRECISION).
+    operands: AttnOperands with the geometry of q,k,v prepared elsewhere (the sequence-parallel path converts the receive
+    buffers once, vorta_amd/ulysses/engine.py RecvOperands); `fp8` and `fp8_operands` are then not read.
     kv_splits > 1: the full-attention and coreset launches cut their KEYS into that many parts (+ a merge kernel) -- for
     a sequence-parallel rank whose one or two heads leave the chip under one round of workgroups, where a layer lasts as
     long as one workgroup's key loop; changes the summation order, so it is never chosen silently."""
@@ -277,41 +333,11 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     def nheads(e):  # for the algorithmic-work tags only
         return routing.counts_host[e] if routing.counts_host is not None else 0
 
-    base = dict(q=q3, k=k3, v=v3, scale=scale)
-    if fp8 is None:
-        fp8 = DEFAULT_FP8
-    if fp8_views is not None:
-        base = dict(q=fp8_views[0], k=fp8_views[1], v=fp8_views[2], scale=scale, v_descale=fp8_views[3])
-        if len(fp8_views) in (5, 7):  # int8 keys: + their I8Operands (row biases, query preparation, head scales)
-            base.update(i8=fp8_views[4])
-        if len(fp8_views) == 7:  # "auto8" on converted views: + the 16-bit keys and the heads' tail flags (sequence-parallel path)
-            base_tail = dict(q=fp8_views[0], k=fp8_views[5], v=fp8_views[2], scale=scale, v_descale=fp8_views[3])
-            tail, fp8 = fp8_views[6], "auto8"
-    elif fp8 == "i8pv":  # int8 scores: k -> int8 rows (centred, balanced, one scale per head) + a float bias per row, v -> e4m3;
-        # q is centred, balanced and rounded by the attention kernel itself
-        vo, ko = fp8_operands if isinstance(fp8_operands, tuple) and len(fp8_operands) == 2 else (None, None)
-        v8, vd, _ = ops.fp8_quantize_v(v3, out=vo)
-        i8 = ops.i8_quantize_k(q3, k3, out=ko)
-        base = dict(q=q3, k=i8.k8, v=v8, scale=scale, v_descale=vd, i8=i8)
-    elif fp8 == "auto8":
-        # per head: int8 scores where the head's int8 keys resolve their bulk, 16-bit scores where they do not (heavy tails);
-        # P V in e4m3 with block-scaled probabilities either way.  The choice is made on the device (ops.i8_tail_flags over the
-        # int8 keys, ops.split_heads over every expert's head list): two fused launches per layer, one of them usually over
-        # empty lists (its workgroups exit in their first instruction), no host synchronisation
-        vo, ko = fp8_operands if isinstance(fp8_operands, tuple) and len(fp8_operands) == 2 else (None, None)
-        v8, vd, _ = ops.fp8_quantize_v(v3, out=vo)
-        i8 = ops.i8_quantize_k(q3, k3, out=ko)
-        tail = ops.i8_tail_flags(i8.k8)
-        base = dict(q=q3, k=i8.k8, v=v8, scale=scale, v_descale=vd, i8=i8)
-        base_tail = dict(q=q3, k=k3, v=v8, scale=scale, v_descale=vd)
-    elif fp8 == "fp8pv":  # scores in 16 bits, P V in e4m3: only v is converted (exact per-channel abs-max, one pass + one)
-        v8, vd, _ = ops.fp8_quantize_v(v3, out=fp8_operands if isinstance(fp8_operands, tuple) and len(fp8_operands) == 3 else None)
-        base = dict(q=q3, k=k3, v=v8, scale=scale, v_descale=vd)
-    elif fp8:
+    if operands is None:
         # (video_tokens: the sample is summed in eighths of the video tokens + the text, as the sequence-parallel send side sums it)
-        f8 = ops.fp8_quantize_qkv(q3, k3, v3, scale, out=fp8_operands, center_k=FP8_CENTER_K,
-                                  video_tokens=S if rm is None and T > 0 else 0)
-        base = dict(q=f8.q, k=f8.k, v=f8.v, scale=scale, v_descale=f8.v_descale)
+        operands = prepare_operands(precision_of(fp8), q3, k3, v3, scale, fp8_operands,
+                                    video_tokens=S if rm is None and T > 0 else 0)
+    base = operands.kwargs(scale)
 
     split_kw = dict(n_splits=int(kv_splits)) if kv_splits and int(kv_splits) > 1 else {}
     slot_of = routing.slot_args  # (expert, H) -> head_list / n_heads / n_heads_dev of a launch ("auto8": one of the two parts)
@@ -403,12 +429,12 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         # 128-row launch with less padding (Hunyuan 129f: 4.77 s vs 4.91 s per step)
         sliding_block_rows = 256
     experts = [(expert_full, live(0)), (expert_lowres, live(1)), (expert_sliding, live(2))]
-    if fp8 == "auto8" and (fp8_views is None or len(fp8_views) == 7):
+    if operands.precision == "auto8":
         if concurrent:
             raise ValueError("'auto8' runs its two parts as fused grids (concurrent=False)")
-        parts = [ops.split_heads(tail, **routing.slot_args(e, H)) if on else None for e, (_, on) in enumerate(experts)]
-        pparts = [ops.split_heads(tail, hl, 1) for hl, _, _ in routing.partials or ()]
-        for which, b in ((0, base), (1, base_tail)):  # int8-score heads, then 16-bit-score heads
+        parts = [ops.split_heads(operands.tail, **routing.slot_args(e, H)) if on else None for e, (_, on) in enumerate(experts)]
+        pparts = [ops.split_heads(operands.tail, hl, 1) for hl, _, _ in routing.partials or ()]
+        for which, b in ((0, base), (1, operands.tail_kwargs(scale))):  # int8-score heads, then 16-bit-score heads
             base = b
             slot_of = lambda e, H_, which=which: parts[e][which]  # noqa: E731
             slot_part = lambda i, hl, which=which: pparts[i][which]  # noqa: E731

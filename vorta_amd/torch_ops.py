@@ -152,9 +152,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: tor
     from . import routed
     geom = routed.geometry_for(latent, tile, window, group, rate, q.device, row_map=row_map)
     routing = routed.HeadRouting(head_lists, list(counts_host) if counts_host is not None else None, head_counts)
-    fp8 = None if precision == "" else (False if precision == "native" else True if precision == "fp8" else precision)
     routed.routed_attention(q, k, v, routing, geom, model=model, text_len=text_len, text_valid=text_valid, out=out,
-                            scale=None if scale <= 0.0 else scale, fp8=fp8)
+                            scale=None if scale <= 0.0 else scale, fp8=routed.precision_of(precision or None))
 
 
 @routed_attention.register_fake

@@ -605,14 +605,14 @@ class UlyssesLayout:
         return torch.zeros((self.rows_total, self.D), dtype=self.dtype, device=self.device)
 
     def fp8_operands(self) -> "ops.Fp8Operands":
-        """e4m3 operand buffers of the receive layout (allocated once per layout; `fp8_views(out=...)` fills them)"""
+        """e4m3 operand buffers of the receive layout (allocated once per layout; `fp8_head_views(out=...)` fills them)"""
         nws = ops._C.lib().vorta_fp8_quant_ws_floats(self.Hl, self.D)
         return ops.Fp8Operands(*(torch.zeros((1, self.rows_total, self.D), dtype=torch.uint8, device=self.device) for _ in range(3)),
                                torch.zeros((self.Hl, self.D), dtype=torch.float32, device=self.device),
                                torch.zeros(nws, dtype=torch.float32, device=self.device))
 
-    def fp8_views(self, bufs: Sequence[torch.Tensor], scale: Optional[float] = None, out=None,
-                  vwire: Optional["VWire"] = None, v_descale: Optional[torch.Tensor] = None):
+    def fp8_head_views(self, bufs: Sequence[torch.Tensor], scale: Optional[float] = None, out=None,
+                       vwire: Optional["VWire"] = None, v_descale: Optional[torch.Tensor] = None):
         """e4m3 copies of the q, k, v receive buffers for the fp8 attention kernels: ONE conversion of each whole buffer
         (the head views overlap, so converting per view would redo it Hl times) in the quantiser's segmented row layout
         -- row r belongs to head slot (r // Sl) % Hl, text rows behind the video rows -- so every local head keeps its
@@ -623,7 +623,7 @@ class UlyssesLayout:
         x = [b.view(1, self.rows_total, self.D) for b in bufs[:3]]
         if vwire is not None:
             if out is None or v_descale is None:
-                raise ValueError("fp8_views(vwire=...): `out` = the operands whose v is the e4m3 receive buffer, `v_descale` its scales")
+                raise ValueError("fp8_head_views(vwire=...): `out` = the operands whose v is the e4m3 receive buffer, `v_descale` its scales")
             x[2] = None
         f8 = ops.fp8_quantize_qkv(*x, scale, out=out, center_k=FP8_CENTER_K, heads=self.Hl, seg_len=self.Sl,
                                   tail_first=self.rows_video, tail_len=self.T)
@@ -993,35 +993,89 @@ class UlyssesLayout:
                 out_text[torch.as_tensor(list(head_order), device=out_text.device)] = allh
 
 
-class _RankState:
-    """everything of the receive side that depends on how many head slots this rank holds: buffers, e4m3 operands, the
-    routed geometry composed with the layout's row map"""
+def auto_kv_splits(local_experts: Sequence[int], S: int, T: int, s_low: int) -> int:
+    """`kv_splits="auto"`: the key splits of a rank's full-attention / coreset launches from its count of 256-row
+    workgroups -- a rank with one or two heads runs under one round of workgroups on 256 CUs, where key splits shorten
+    the layer and query splits do not.  `s_low`: the coreset expert's video tokens."""
+    rows = {0: S + T, 1: s_low + T, 2: S}
+    wgs = sum(-(-rows[int(x)] // 256) for x in local_experts)
+    return max(1, min(8, round(768 / max(wgs, 1)))) if wgs < 384 else 1
 
-    def __init__(self, lay: UlyssesLayout, cfg: dict, te: int, fp8: bool, v_wire: bool, loopback: bool):
-        from ..routed import RoutedGeometry
+
+class RecvOperands:
+    """The receive side of one head-slot count: the q, k, v, o receive buffers, v's e4m3 wire, the 8-bit operand buffers of
+    the precision (allocated on first use; a change of precision reallocates the 8-bit part only) and their slot-group
+    views.  `loopback`: the chunks no peer fills hold finite values of the same distribution."""
+
+    def __init__(self, lay: UlyssesLayout, loopback: bool = False):
         self.bufs = [lay.new_buffer() for _ in range(4)]  # q, k, v, o
-        if loopback:  # the chunks no peer will fill: finite values of the same distribution
+        if loopback:
             for b in self.bufs[:3]:
                 b.normal_()
-        self.f8 = self.vwire = self.i8 = None
-        if fp8 in ("fp8pv", "i8pv", "auto8"):  # only v is e4m3, converted on the send side (it always travels as bytes); "i8pv": k is
-            # rounded to int8 on this side, slot group by slot group (q by the attention kernel)
+        self.lay, self.loopback, self.precision = lay, loopback, "native"
+        self.f8 = self.i8 = self.vwire = None
+        self._wire = None  # whether `vwire` of precision "fp8" writes into f8.v
+        self.group_ops = {}  # the 8-bit operand buffers as each slot group sees them (UlyssesLayout.group_operands)
+
+    def begin(self, lay: UlyssesLayout, precision: str, v_wire: bool) -> Optional[VWire]:
+        """this layer's receive side: `lay` is its layout (of this slot count), `precision` a name of routed.PRECISIONS,
+        `v_wire` whether v crosses the links as e4m3.  Returns the v wire for the exchange (None: v travels in 16 bits)."""
+        self.lay, self.precision = lay, precision
+        if precision in ("fp8pv", "i8pv", "auto8"):  # only v is e4m3, converted on the send side (it always travels as bytes);
+            # "i8pv" / "auto8": k is rounded to int8 on this side, slot group by slot group (q by the attention kernel)
             if not v_wire:
-                raise ValueError(f"precision '{fp8}' under sequence parallelism converts v on the send side (v_wire)")
-            if fp8 in ("i8pv", "auto8"):
+                raise ValueError(f"precision '{precision}' under sequence parallelism converts v on the send side (v_wire)")
+            if precision != "fp8pv" and self.i8 is None:
                 self.i8 = lay.i8_operands()
-            buf8 = torch.zeros((lay.rows_total, lay.D), dtype=torch.uint8, device=lay.device)
-            if loopback:
-                buf8.random_(0, 120)
-            self.vwire = VWire(lay, buf8)
-        elif fp8:
-            self.f8 = lay.fp8_operands()
-            if v_wire:  # v travels as e4m3 straight into the operand buffer
-                self.vwire = VWire(lay, self.f8.v[0])
-                if loopback:
+            if self.vwire is None or self.f8 is not None:
+                self.f8 = None
+                buf8 = torch.zeros((lay.rows_total, lay.D), dtype=torch.uint8, device=lay.device)
+                if self.loopback:
+                    buf8.random_(0, 120)
+                self.vwire = VWire(lay, buf8)
+        elif precision == "fp8":
+            if self.f8 is None:
+                self.f8, self._wire = lay.fp8_operands(), None
+            if self._wire != v_wire:  # (the switch may change between calls in A/B runs: the wire follows it)
+                self.vwire = VWire(lay, self.f8.v[0]) if v_wire else None  # v travels as e4m3 straight into the operand buffer
+                self._wire = v_wire
+                if v_wire and self.loopback:
                     self.f8.v.random_(0, 120)  # finite e4m3 bytes in the chunks no peer fills
-        self.cfg, self.te, self.lay = cfg, te, lay
-        self._geoms, self.group_ops = {}, {}
+        else:
+            return None
+        if self.vwire is not None:
+            self.vwire.lay = lay  # the layouts of one slot count share the buffers; the head offsets are this layer's
+        return self.vwire
+
+    def operands(self, sg: SlotGroup):
+        """routed.AttnOperands of slot group `sg` of this layer's layout, once it has landed"""
+        from ..routed import AttnOperands
+        p, sub, vw = self.precision, sg.lay, self.vwire
+        b = [sg.buffer(x) for x in self.bufs]
+        q, k, v = (sub.head_view(x) for x in b[:3])
+        if p in ("i8pv", "auto8"):  # k of the slot group that has landed -> int8; q as it landed; v arrived as e4m3
+            i8 = sub.i8_views(b, self.lay.group_operands(sg, self.i8, self.group_ops))
+            # "auto8": + the 16-bit keys and the group's tail flags: each head to the kernel that holds it
+            tail = ops.i8_tail_flags(i8.k8, row_map=sub.row_map[:sub.S + sub.T]) if p == "auto8" else None
+            return AttnOperands(p, q, i8.k8, sg.head_view(vw.buf), vw.descale(sg), i8, None if tail is None else k, tail)
+        if p == "fp8pv":  # 16-bit q, k as they landed; v arrived as e4m3
+            return AttnOperands(p, q, k, sg.head_view(vw.buf), vw.descale(sg))
+        if p == "fp8":  # the slot group that has landed is converted while the next one is in flight
+            q8, k8, v8, vd, _ = sub.fp8_head_views(b, out=self.lay.group_operands(sg, self.f8, self.group_ops), vwire=vw,
+                                                   v_descale=None if vw is None else vw.descale(sg))
+            return AttnOperands(p, q8, k8, v8, vd)
+        return AttnOperands(p, q, k, v)
+
+
+class _RankState(RecvOperands):
+    """the receive side of one head-slot count (its 8-bit buffers allocated up front) + the routed geometry composed with
+    the row maps of its layouts"""
+
+    def __init__(self, lay: UlyssesLayout, cfg: dict, te: int, precision: str, v_wire: bool, loopback: bool):
+        super().__init__(lay, loopback)
+        self.begin(lay, precision, v_wire)
+        self.cfg, self.te = cfg, te
+        self._geoms = {}
         self.geom = self.geom_for(lay)
 
     def geom_for(self, lay: UlyssesLayout):
@@ -1048,12 +1102,12 @@ class UlyssesRoutedAttention:
                  v_wire: bool = True, placement: str = "even", heaviest_rank: bool = False, kv_splits=1):
         """heaviest_rank (with loopback): every layer is run as the rank that carries the largest cost in THAT layer -- a
         P-GPU step waits for its slowest rank layer by layer, so this (not a fixed rank) is the compute side of it."""
-        from ..routed import HeadRouting
+        from ..routed import HeadRouting, precision_of
         if placement not in ("even", "uneven", "split"):
             raise ValueError("placement is 'even', 'uneven' or 'split'")
         if heaviest_rank and not loopback:
             raise ValueError("heaviest_rank is an emulation mode (loopback)")
-        self.fp8 = fp8
+        self.precision, self.v_wire = precision_of(fp8), v_wire
         H, T = cfg["heads"], cfg["text"]
         S = cfg["latent"][0] * cfg["latent"][1] * cfg["latent"][2]
         self.cfg, self.P, self.rank = cfg, P, rank
@@ -1087,17 +1141,14 @@ class UlyssesRoutedAttention:
                 lay.loopback = loopback
                 layouts[key] = lay
                 if lay.Hl not in self.states:
-                    self.states[lay.Hl] = _RankState(lay, cfg, self.te, fp8, v_wire, loopback)
+                    self.states[lay.Hl] = _RankState(lay, cfg, self.te, self.precision, v_wire, loopback)
             lay = layouts[key]
             sg = slot_groups(lay.Hl, min(groups, min(counts)))
             local = [int(e[h]) for h in order[lay.starts[r]:lay.starts[r + 1]]]
             local_parts = [None] * len(local) if parts is None else parts[lay.starts[r]:lay.starts[r + 1]]
             if kv_splits == "auto":
-                s_low = (S // (cfg["group"][0] * cfg["group"][1] * cfg["group"][2])) * int(
-                    cfg["group"][0] * cfg["group"][1] * cfg["group"][2] * (1 - cfg["rate"]))
-                rows = {0: S + T, 1: s_low + T, 2: S}
-                wgs = sum(-(-rows[x] // 256) for x in local)
-                self.kv_splits.append(max(1, min(8, round(768 / max(wgs, 1)))) if wgs < 384 else 1)
+                g = cfg["group"][0] * cfg["group"][1] * cfg["group"][2]
+                self.kv_splits.append(auto_kv_splits(local, S, T, (S // g) * int(g * (1 - cfg["rate"]))))
             else:
                 self.kv_splits.append(max(1, int(kv_splits)))
             self.orders.append(order)
@@ -1122,9 +1173,8 @@ class UlyssesRoutedAttention:
         """`exchange_selfcheck` on layer l's placement, buffers and transport (before the warm-up of bench.py's N > 1 run)"""
         lay = self.lays[l]
         st = self.states[lay.Hl]
-        if st.vwire is not None:
-            st.vwire.lay = lay
-        return exchange_selfcheck(lay, self.orders[l], self.groups[l], st.bufs, vwire=st.vwire, break_order=break_order,
+        vwire = st.begin(lay, self.precision, self.v_wire)
+        return exchange_selfcheck(lay, self.orders[l], self.groups[l], st.bufs, vwire=vwire, break_order=break_order,
                                   parts=self.parts[l])
 
     def layer(self, l: int, exchange_only: bool = False):
@@ -1134,40 +1184,21 @@ class UlyssesRoutedAttention:
         shards, texts = self.sets[l % len(self.sets)]
         lay = self.lays[l]
         st = self.states[lay.Hl]
-        if st.vwire is not None:
-            st.vwire.lay = lay  # the layouts of one slot count share the state; the head offsets are the layer's
+        vwire = st.begin(lay, self.precision, self.v_wire)
         sgs, _, _ = lay.grouping(len(self.groups[l]))
         geoms = [st.geom_for(sg.lay) for sg in sgs]  # built (and their tables) before the slot groups fork onto their streams
 
         def attend(g0, g1, gi):
             if exchange_only:
                 return
-            sg = sgs[gi]
-            sub = sg.lay
-            b = [sg.buffer(x) for x in st.bufs]
-            q, k, v, o = (sub.head_view(x) for x in b)
-            views = None
-            if self.fp8 in ("i8pv", "auto8"):  # k of the slot group that has landed -> int8; q as it landed; v arrived as e4m3
-                i8 = sub.i8_views(b, lay.group_operands(sg, st.i8, st.group_ops))
-                views = (q, i8.k8, sg.head_view(st.vwire.buf), st.vwire.descale(sg), i8)
-                if self.fp8 == "auto8":  # + the 16-bit keys and the group's tail flags: each head to the kernel that holds it
-                    views += (k, ops.i8_tail_flags(i8.k8, row_map=sub.row_map[:lay.S + lay.T]))
-            elif self.fp8 == "fp8pv":  # 16-bit q, k as they landed; v arrived as e4m3
-                views = (q, k, sg.head_view(st.vwire.buf), st.vwire.descale(sg))
-            elif self.fp8:  # the slot group that has landed is converted while the next one is in flight
-                f8 = lay.group_operands(sg, st.f8, st.group_ops)
-                q8, k8, v8, vd, f8 = sub.fp8_views(b, out=f8, vwire=st.vwire,
-                                                   v_descale=None if st.vwire is None else st.vwire.descale(sg))
-                if sub is lay:
-                    st.f8 = f8
-                views = (q8, k8, v8, vd)
+            q, k, v, o = (sgs[gi].head_view(b) for b in st.bufs)
             routed_attention(q, k, v, self.routes[l][gi], geoms[gi], model=self.cfg["model"],
                              text_len=self.cfg["text"], text_valid=self.te, out=o, concurrent=self.concurrent,
-                             fused=self.fused, sliding_block_rows=self.sliding_block_rows, fp8=False, fp8_views=views,
+                             fused=self.fused, sliding_block_rows=self.sliding_block_rows, operands=st.operands(sgs[gi]),
                              kv_splits=self.kv_splits[l])
 
         # every cached table of this layer exists before the slot groups fork onto their streams (the routing lists were
         # copied to the device in __init__)
         exchange_and_attend(lay, shards, st.bufs, self.orders[l], texts, self.groups[l], attend, self.out_shard,
-                            self.out_text, vwire=st.vwire, parts=self.parts[l],
+                            self.out_text, vwire=vwire, parts=self.parts[l],
                             prepare=lambda: [g.prebuild(self.te if self.cfg["model"] == "hunyuan" else 0) for g in geoms])
