@@ -122,7 +122,8 @@ typedef struct vorta_attn_args {
    * q_group_len is ignored; group g still reads the key list kv_rows + g*kv_rows_stride_g.  Used by the sliding-tile
    * expert: query tiles whose clamped windows coincide (sliding_attn_flex.py:118-120 clamps the window centre, so the
    * two outermost tiles of a dimension see the same keys) are merged into one group, and the group is cut into full
-   * workgroups instead of every 792-token tile ending in a 24-row one. */
+   * workgroups instead of every 792-token tile ending in a 24-row one.  With n_splits > 1 the rows must cover every
+   * position in [0, n_q): the split-key merge writes each of them. */
   const int32_t* q_block_table;
   int32_t n_q_blocks;
   int32_t reserved2;

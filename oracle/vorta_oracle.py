@@ -646,7 +646,8 @@ def fp8_attn_launch(q: np.ndarray, k: np.ndarray, v: np.ndarray, out: np.ndarray
                     p_bias: float = 5.0, defer: float = 3.0, round_p: bool = True,
                     ambiguous: Optional[np.ndarray] = None,
                     q_group_bounds: Optional[Sequence[Tuple[int, int]]] = None,
-                    wave_filter=None, wave_operands=None, p_mode: str = "rne") -> None:
+                    wave_filter=None, wave_operands=None, p_mode: str = "rne",
+                    split_n_kv: Optional[int] = None) -> None:
     """include/vorta_hip.h vorta_attn_fwd_fp8 for ONE head: q,k,v (rows,D) decoded e4m3 values, `out` (rows,D) is
     written in place (rows named by q_rows / dup_rows only).  kv_rows: (n_kv,) or (n_groups, n_kv).
     `ambiguous` (rows,) float, optional: per output row, the total normalised probability of the keys whose e4m3
@@ -659,13 +660,18 @@ def fp8_attn_launch(q: np.ndarray, k: np.ndarray, v: np.ndarray, out: np.ndarray
     scale, hence the rounded key biases, belong to the wave -- `i8_wave_operands`); q and k are then not read.
     `p_mode="direct"`: the probabilities' bytes are rint(8 log2 P' + 56) (see `_fp8_flash_rows`); `p_mode="mx"`: vorta_attn_fwd_i8
     since ABI 7 -- one power-of-two scale per lane and block (`_i8_mx_flash_rows`; `defer` is then the trigger in binades,
-    24 in the kernel's default)."""
+    24 in the kernel's default).
+    `split_n_kv`: the key count the split boundaries are cut from (default `n_kv`).  The kernels cut them from the host
+    n_kv while a device-resident length (vorta_attn_args.n_kv_dev) may stop the keys earlier: pass the host n_kv here and
+    the effective length as `n_kv`.  Splits that then start at or past the effective end hold no keys (m = -1e30, l = 0
+    in the kernels' partials) and add nothing to the merge."""
     q_valid = n_q if q_valid is None else q_valid
     glen = q_group_len if q_group_len > 0 else n_q
     if q_group_bounds is None:  # equal groups; else [start, end) of every group (vorta_attn_args.q_block_table)
         q_group_bounds = [(g * glen, min((g + 1) * glen, n_q)) for g in range(-(-n_q // glen))]
     nblk = -(-n_kv // 64)
-    bps = -(-nblk // n_splits)
+    split_blk = -(-(n_kv if split_n_kv is None else split_n_kv) // 64)
+    bps = -(-split_blk // n_splits)
     for g, (g0, g1) in enumerate(q_group_bounds):
         pos = np.arange(g0, g1)
         rows = q_rows[pos] if q_rows is not None else q_row_offset + pos

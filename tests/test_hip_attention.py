@@ -283,6 +283,37 @@ def test_randomised_launch_shapes(seed):
     assert np.abs(got - ref).max() <= ATOL_SAME[dtype], desc
 
 
+
+@pytest.mark.parametrize("seed", range(56))
+def test_randomised_launches_device_lengths_splits_groups_duplicates(seed):
+    """Random launches (tests/_random_launch.py) that put key splits (1..8) together with query groups of equal or different
+    lengths (q_block_table), duplicate rows and head lists, with device-resident n_kv / q_valid / head counts: n_kv_dev
+    below, at and above n_kv, 0, or so short that the last splits hold no key.  Against the float64 oracle; rows of dead
+    slots and every row the launch does not name keep the sentinel.  With one split, device lengths L, V write the bytes
+    of the host lengths L, V: both walk the same key blocks and mask the same rows."""
+    import _random_launch as R
+    from vorta_amd import ops
+    rng = np.random.default_rng(5000 + seed)
+    dtype = (torch.bfloat16, torch.float16)[seed % 2]
+    L = R.draw(rng, empty_tail=seed % 4 == 3)
+    variant = int(rng.choice([1, 2]))
+    x = [rng.standard_normal((L.H_buf, L.S, 128)) for _ in range(3)]
+    qd, kd, vd = (to_dev(a, dtype) for a in x)
+    out = torch.full_like(qd, R.SENTINEL)
+    ops.attn_fwd(qd, kd, vd, out, variant=variant, **R.kwargs(L, dev()))
+    torch.cuda.synchronize()
+    r = [rounded(a, dtype) for a in x]
+    ref = R.dense_reference(L, *r, lambda q, k, v: O.dense_attention(q[None], k[None], v[None])[0])
+    desc = dict(R.describe(L), seed=seed, variant=variant)
+    got = out.float().cpu().numpy()
+    assert np.abs(got - ref).max() <= ATOL_SAME[dtype], desc
+    if L.n_splits == 1 and (L.n_kv_dev is not None or L.q_valid_dev is not None):
+        host = torch.full_like(qd, R.SENTINEL)
+        ops.attn_fwd(qd, kd, vd, host, variant=variant,
+                     **R.kwargs(L, dev(), n_kv=L.n_kv_eff, q_valid=L.q_valid_eff, n_kv_dev=None, q_valid_dev=None))
+        assert torch.equal(host, out), desc
+
+
 def test_table_extents_are_checked_on_the_host():
     """the kernels trust their tables; ops refuses every shape that cannot cover the launch (a 2-D key table is one
     list PER HEAD SLOT -- a single shared list must be 1-D)"""

@@ -151,3 +151,28 @@ def test_launch_emulator_groups_of_different_lengths():
     for g, (a, b) in enumerate(bounds):
         ref = O._softmax_attend(q[q_rows[a:b]], k[kv_rows[g]], v[kv_rows[g]], scale=np.log(2.0))
         assert np.abs(out[q_rows[a:b]] - ref).max() < 1e-12
+
+
+@pytest.mark.parametrize("n_splits", [2, 3, 8])
+def test_launch_emulator_splits_cut_from_a_longer_key_count(n_splits):
+    """`split_n_kv`: split boundaries cut from the host n_kv while the keys stop at a shorter effective n_kv (a
+    device-resident length).  Without probability rounding it is still softmax attention over the n_kv keys, also when
+    whole splits lie past them; the default call is the call with split_n_kv = n_kv."""
+    rng = np.random.default_rng(6)
+    q, k, v = _operands(rng, 120, 0.6), _operands(rng, 700, 0.6), _operands(rng, 700, 3.0)
+    vd = rng.uniform(0.01, 0.1, 128)
+    for n_kv, host in ((70, 640), (130, 700), (1, 600), (300, 300)):
+        out = np.full((120, 128), 9.0)
+        O.fp8_attn_launch(q, k, v, out, vd, n_q=100, q_row_offset=10, n_kv=n_kv, q_valid=90, n_splits=n_splits,
+                          round_p=False, split_n_kv=host)
+        ref = O._softmax_attend(q[10:100], k[:n_kv], v[:n_kv], scale=np.log(2.0)) * vd
+        assert np.abs(out[10:100] - ref).max() < 1e-12, (n_kv, host)
+        assert (out[100:110] == 0).all() and (out[:10] == 9.0).all() and (out[110:] == 9.0).all()
+    # with rounding the split boundaries matter; the default cuts them from n_kv itself
+    for kw in (dict(), dict(p_mode="mx", defer=24.0)):
+        a, b, c = (np.zeros((120, 128)) for _ in range(3))
+        O.fp8_attn_launch(q, k, v, a, vd, n_q=100, n_kv=450, n_splits=n_splits, **kw)
+        O.fp8_attn_launch(q, k, v, b, vd, n_q=100, n_kv=450, n_splits=n_splits, split_n_kv=450, **kw)
+        O.fp8_attn_launch(q, k, v, c, vd, n_q=100, n_kv=450, n_splits=n_splits, split_n_kv=700, **kw)
+        assert (a == b).all()
+        assert not (a == c).all()  # other boundaries, other reference points

@@ -562,6 +562,18 @@ def _coherence_worker(rank, world, port, ret):
         res["nan"] = "ok"
     except RuntimeError as e:
         res["nan"] = "not finite" if "not finite" in str(e) else str(e)
+    # above 2^25 elements (the Wan-1.3B-81f hidden state, in bf16): a float32 sample index rounds to one past the end
+    big = 50_319_360
+    for name, seed in (("big same", 7), ("big different seeds", 200 + rank)):
+        x = torch.randn(big, generator=torch.Generator().manual_seed(seed)).to(torch.bfloat16).view(1, -1, 1536)
+        try:
+            check_rank_coherence(x)
+            res[name] = "ok"
+        except RuntimeError as e:
+            res[name] = "different latents" if "different latents" in str(e) else str(e)
+        except IndexError as e:
+            res[name] = f"IndexError: {e}"
+        del x
     # what the old checksum (signed sum and abs-sum to 1e-3 of the abs-sum) said about the per-rank seeds: nothing
     sums = torch.stack([other.sum(), other.abs().sum()]).reshape(1, 2)
     every = [torch.empty_like(sums) for _ in range(world)]
@@ -581,4 +593,15 @@ def test_rank_coherence_check_sees_per_rank_seeds_at_production_sizes():
     mp.spawn(_coherence_worker, args=(2, _free_port(), ret), nprocs=2, join=True)
     for r in range(2):
         assert ret[r] == {"same": "ok", "ulp apart": "ok", "different seeds": "different latents", "nan": "not finite",
-                          "old checksum blind": True}, ret[r]
+                          "big same": "ok", "big different seeds": "different latents", "old checksum blind": True}, ret[r]
+
+
+@pytest.mark.parametrize("n", [2 ** 24 + 1, 2 ** 25 + 1, 50_319_360, 91_238_400, 1, 2, 63, 64, 65, 1000])
+def test_coherence_sample_indices_stay_inside_the_tensor(n):
+    """the sample of check_rank_coherence: every index below n, the first 0, the last n - 1, strictly increasing, at every size
+    (a float32 linspace put the last index AT n for n = 50_319_360: a device-side assert on the GPU)"""
+    from vorta_amd.patch._engine import COHERENCE_SAMPLE, coherence_sample_indices
+    idx = coherence_sample_indices(n)
+    assert idx.dtype == torch.int64 and idx.numel() == min(COHERENCE_SAMPLE, n)
+    assert int(idx[0]) == 0 and int(idx[-1]) == n - 1 and int(idx.max()) < n
+    assert bool((idx[1:] > idx[:-1]).all())

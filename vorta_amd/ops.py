@@ -354,8 +354,15 @@ def attn_fwd_batch_built(built, fuse: bool = True) -> None:
     fam = args[0]._family
     if any(a._family is not fam for a in args):
         raise ValueError("a fused grid is all 16-bit, all e4m3, all mixed-precision or all int8-score")
+    # one operand set per layer: every fused launch shares v_descale and the options (the first launch's `_ext`); a
+    # segment with operands of its own would be computed with the first one's, so it is refused
+    if args[0]._ext is not None:
+        for i, a in enumerate(args[1:], 1):
+            diff = [f for f, _ in a._ext._fields_ if getattr(a._ext, f) != getattr(args[0]._ext, f)]
+            if diff:
+                raise ValueError(f"fused launch {i} carries other 8-bit operands or options than launch 0 ({', '.join(diff)}): "
+                                 "one grid takes one operand set; launch it separately")
     arr = (_C.AttnArgs * len(args))(*args)
-    # one operand set per layer: every fused launch shares v_descale and the options (the first launch's `_ext`)
     go = lambda: _C.check(getattr(_C.lib(), fam.batch)(arr, *_ext(args[0]), len(args), _stream()), fam.batch)
     _timed(go, "+".join(t for _, _, t, _ in built), sum(f for _, _, _, f in built), args, fam.multi.format(t=args[0]._out_type))
 

@@ -275,6 +275,13 @@ def install_sp_rope(rope: nn.Module, model: nn.Module, frame_dim: int = 2) -> No
 COHERENCE_SAMPLE = 64
 
 
+def coherence_sample_indices(n: int, k: int = COHERENCE_SAMPLE, device=None) -> torch.Tensor:
+    """min(k, n) evenly spaced indices into n elements, the first 0 and the last n - 1.  Computed in int64: a float32
+    linspace rounds n - 1 up to n above 2^24 elements (a Wan-1.3B-81f hidden state has 50_319_360), one past the end."""
+    k = min(k, n)
+    return torch.arange(k, dtype=torch.int64, device=device) * (n - 1) // max(k - 1, 1)
+
+
 def check_rank_coherence(x: torch.Tensor) -> None:
     """Every sequence-parallel rank must enter the transformer with the SAME hidden states (the ranks keep whole latents and
     cut tokens inside the model): compare a fixed strided SAMPLE of `COHERENCE_SAMPLE` elements across ranks, element by element,
@@ -285,7 +292,7 @@ def check_rank_coherence(x: torch.Tensor) -> None:
     differ by their own magnitude, whatever N.  Raises RuntimeError naming the cause (non-finite values are told apart)."""
     flat = x.reshape(-1)
     n = flat.numel()
-    idx = torch.linspace(0, n - 1, min(COHERENCE_SAMPLE, n), device=x.device).long()
+    idx = coherence_sample_indices(n, device=x.device)
     sample = flat[idx].float()
     finite = torch.isfinite(x.float().abs().max()).float().reshape(1)
     from ..ulysses import all_gather
