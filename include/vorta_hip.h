@@ -31,7 +31,7 @@ extern "C" {
 #define VORTA_EUNSUPPORTED (-2) /* valid request this build does not implement (head_dim, dtype)      */
 #define VORTA_ELAUNCH (-3)      /* the HIP runtime refused the launch (see vorta_last_hip_error)      */
 
-#define VORTA_ABI_VERSION 8 /* 2: adds the fp8 entry points (vorta_fp8_*, vorta_attn_fwd_fp8*); 3: adds vorta_permute_heads;
+#define VORTA_ABI_VERSION 9 /* 2: adds the fp8 entry points (vorta_fp8_*, vorta_attn_fwd_fp8*); 3: adds vorta_permute_heads;
                                 4: vorta_fp8_quant_args gains slot_first / slot_count and flags bit2, adds vorta_fp8_v_absmax /
                                 vorta_fp8_v_convert; every earlier call means what it meant
                                 5: vorta_fp8_quant_args gains video_tokens / token_offset / total_tokens / src_map and flags
@@ -39,7 +39,8 @@ extern "C" {
                                 6: adds the int8-score entry points (vorta_i8_quantize_k, vorta_attn_fwd_i8, vorta_attn_fwd_batch_i8);
                                 7: the int8-score kernel writes its probabilities with one power-of-two scale per query row
                                    and 32 keys (vorta_attn_i8_ext.defer becomes the reference-point trigger in binades, default 24);
-                                8: adds vorta_i8_tail_flags and vorta_split_heads (per-head choice between int8 and 16-bit scores) */
+                                8: adds vorta_i8_tail_flags and vorta_split_heads (per-head choice between int8 and 16-bit scores)
+                                9: adds the backward entry points (vorta_attn_bwd, vorta_mix_experts_bwd, vorta_cast_grads) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -145,6 +146,46 @@ int vorta_attn_plan(const vorta_attn_args* args, int32_t* block_rows, int64_t* n
  *   attn_fwd_kernel<T,NW> (plain) or attn_fwd_pipe_kernel<T,NW,KVTAB> */
 /* bytes of ws_o and ws_ml for a given launch (0,0 when n_splits <= 1) */
 int vorta_attn_workspace_bytes(const vorta_attn_args* args, uint64_t* ws_o_bytes, uint64_t* ws_ml_bytes);
+
+/*
+ * vorta_attn_bwd (ABI 9) -- the gradient of exactly what ONE vorta_attn_fwd launch computes, for the same argument block (16-bit,
+ * head_dim 128).  The reference differentiates its experts with torch autograd (`_step_attention` hunyuan.py:136-189, `_attn`
+ * wan.py:103-149; the coreset pool / unpool of hunyuan.py:410-457, wan.py:243-270; the sliding tile of hunyuan.py:459-507,
+ * wan.py:272-294): this is the derivative of those lines, with the row tables as constants (coreset_select.py ranks with
+ * argsort: no gradient flows through the selection there either).  For head slot y, group g, query position p (row r(p)
+ * through q_rows / q_row_offset) and keys j < n_kv_eff (rows through kv_rows / kv_row_offset):
+ *     dO_eff[p] = w[head] (d_o[r(p)] + sum_i d_o[dup_rows[y][p][i]])     (duplicates: p < n_dup_pos; w = 1 without do_scale)
+ *     dO_eff[p] = 0  for p >= q_valid_eff                                 (the forward wrote zeros there)
+ *     P = softmax_j(scale q.k)       delta[p] = dO_eff[p] . o[r(p)] = sum_j P[p][j] (dO_eff[p] . v[j])
+ *     (fwd.o = the forward's OUTPUT, with d_o's geometry.  The kernel takes delta in the second form, from the P and dP it
+ *     forms anyway: sum_j dS[p][j] then cancels to the rounding of those numbers, and a row with a single key gets dS = 0
+ *     exactly, as float64 autograd does -- the first form leaves a 1e-7 residue.  fwd.o is validated and not read.)
+ *     dv[j] += sum_p P[p][j] dO_eff[p]          dS = P (dO_eff . v[j] - delta[p])
+ *     dq[r(p)] += scale sum_j dS[p][j] k[j]     dk[j] += scale sum_p dS[p][j] q[r(p)]
+ * dq / dk / dv are fp32 (H,S,D) buffers that are ADDED to (the caller zeroes them): the three experts of the soft mixture
+ * add into the SAME buffers and vorta_cast_grads rounds once.  Rows and heads the launch does not name receive nothing.
+ * One kernel for every expert (csrc/attn_bwd.hip): query-major 128-row workgroups, the softmax statistics recomputed in a
+ * first pass over the keys.  fwd.head_list, n_heads_dev, q_rows, q_group_len, q_block_table, kv_rows (both strides), dup_rows,
+ * q_valid, n_kv, n_kv_dev, q_valid_dev and scale mean what they mean for the forward; fwd.n_splits, ws_o, ws_ml and variant
+ * are ignored (splitting keys changes nothing in the gradient); fwd.block_rows is only validated (0, 128, 256; the table
+ * rows of a q_block_table are cut into 128-row workgroups).
+ * REPRODUCIBILITY: dq is written by one workgroup per row (read-add-write; launches on one stream are ordered) and is
+ * bit-reproducible; dk and dv are accumulated with vector float atomics (many query blocks touch one key row), so their
+ * summation order, and with it their last bits, change from run to run.
+ * VORTA_EUNSUPPORTED for a dtype other than bf16 / fp16 or head_dim != 128; VORTA_EINVAL for null or misaligned tensors
+ * (16-byte aligned rows: 8 elements of d_o, 4 floats of dq / dk / dv).
+ */
+typedef struct vorta_attn_bwd_args {
+  uint32_t struct_size;       /* = sizeof(vorta_attn_bwd_args) */
+  int32_t reserved;
+  vorta_attn_args fwd;        /* the forward launch; fwd.o = the forward's OUTPUT (read) */
+  vorta_tensor d_o;           /* 16-bit, geometry of fwd.o */
+  const void* do_scale;       /* optional [..][do_scale_stride_h] in fwd.dtype, indexed by the HEAD id: w[head] */
+  int64_t do_scale_stride_h;  /*   (soft mixture: scores + e, stride 3) */
+  vorta_tensor dq, dk, dv;    /* fp32, strides in elements; ADDED to -- the caller zeroes them */
+} vorta_attn_bwd_args;
+
+int vorta_attn_bwd(const vorta_attn_bwd_args* args, void* hip_stream);
 
 /*
  * fp8 (e4m3) path -- BASELINE.json configs[4] "fp8 MFMA QK^T/PV path".  The reference has no fp8 code: this path serves
@@ -498,7 +539,7 @@ int vorta_qk_norm_rope(const vorta_norm_rope_args* args, void* hip_stream);
  * vorta_mix_experts -- the score-weighted sum of the training-time forward:
  *   out[h][row][:] = sum_e scores[h][e] * x[e][h][row][:]        (fp32 accumulation, one rounding)
  * `_combine_attn_outputs`, hunyuan.py:509-513 == wan.py:296-300 (stack + multiply + sum over the expert axis).
- * Forward only: the library has no backward kernels.
+ * Its derivative is vorta_mix_experts_bwd (scores) and the do_scale weight of vorta_attn_bwd (expert outputs), below.
  */
 typedef struct vorta_mix_args {
   uint32_t struct_size;
@@ -510,6 +551,40 @@ typedef struct vorta_mix_args {
 } vorta_mix_args;
 
 int vorta_mix_experts(const vorta_mix_args* args, void* hip_stream);
+
+/*
+ * vorta_mix_experts_bwd (ABI 9) -- the derivative of `_combine_attn_outputs` (hunyuan.py:509-513 == wan.py:296-300) with
+ * respect to the routing scores:
+ *     dscores[h][e] = sum_{row,d} d_out[h][row][d] * x[e][h][row][d]            (fp32 out, [heads][3])
+ * one pass over d_out and the three saved expert outputs.  Deterministic: VORTA_MIX_BWD_PARTS partial sums per head over fixed
+ * row ranges, each a fixed reduction tree, summed in a fixed order by a second launch; no float atomics.  The derivative
+ * with respect to expert e's output, scores[h][e] * d_out, is NOT materialised: vorta_attn_bwd takes the weight (do_scale).
+ */
+#define VORTA_MIX_BWD_PARTS 64
+typedef struct vorta_mix_bwd_args {
+  uint32_t struct_size;
+  int32_t dtype, head_dim, heads, n_experts; /* n_experts = 3 */
+  int32_t n_rows;
+  vorta_tensor x[3];   /* (H, n_rows, D) views: the saved outputs of expert 0 / 1 / 2 */
+  vorta_tensor d_out;  /* (H, n_rows, D) view, dtype of x */
+  float* dscores;      /* out [heads][n_experts] */
+  float* ws;           /* workspace, heads * VORTA_MIX_BWD_PARTS * 4 floats (caller-owned) */
+} vorta_mix_bwd_args;
+
+int vorta_mix_experts_bwd(const vorta_mix_bwd_args* args, void* hip_stream);
+
+/*
+ * vorta_cast_grads (ABI 9) -- the one rounding at the end of a backward: up to three fp32 (H, n_rows, D) accumulation buffers
+ * (dq, dk, dv of vorta_attn_bwd) -> 16-bit (H, n_rows, D) views, round to nearest even.
+ */
+typedef struct vorta_cast_args {
+  uint32_t struct_size;
+  int32_t dtype, head_dim, heads, n_rows, n_tensors; /* dtype of dst: VORTA_BF16 / VORTA_FP16; 1 <= n_tensors <= 3 */
+  vorta_tensor src[3]; /* fp32, strides in elements, rows 16-byte aligned */
+  vorta_tensor dst[3]; /* 16-bit, strides in elements, rows 16-byte aligned */
+} vorta_cast_args;
+
+int vorta_cast_grads(const vorta_cast_args* args, void* hip_stream);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.
@@ -548,7 +623,7 @@ const char* vorta_build_info(void); /* static string: arch, compiler */
 int vorta_last_hip_error(void);     /* last hipError_t seen by a failed launch in this thread */
 int vorta_sizeof(int which);        /* 0 tensor, 1 attn_args, 2 coreset_args, 3 sta_args, 4 router_args, 5 norm_rope_args,
                                        6 mix_args, 7 fp8_quant_args, 8 attn_fp8_ext, 9 permute_args, 10 fp8_v_args,
-                                       11 i8_quant_args, 12 attn_i8_ext */
+                                       11 i8_quant_args, 12 attn_i8_ext, 13 attn_bwd_args, 14 mix_bwd_args, 15 cast_args */
 
 #ifdef __cplusplus
 }

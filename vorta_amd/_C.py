@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("VORTA_HIP_LIB") or os.path.join(_HERE, "csrc", "libvo
 
 VORTA_OK, VORTA_EINVAL, VORTA_EUNSUPPORTED, VORTA_ELAUNCH = 0, -1, -2, -3
 VORTA_BF16, VORTA_FP16, VORTA_FP32, VORTA_FP8E4M3, VORTA_INT8 = 0, 1, 2, 3, 4
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _i32, _i64, _u32, _f32, _vp = C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_void_p
 
@@ -136,6 +136,29 @@ class AttnI8Ext(C.Structure):
     ]
 
 
+class AttnBwdArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("reserved", _i32), ("fwd", AttnArgs), ("d_o", Tensor),
+        ("do_scale", _vp), ("do_scale_stride_h", _i64), ("dq", Tensor), ("dk", Tensor), ("dv", Tensor),
+    ]
+
+
+class MixBwdArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("heads", _i32), ("n_experts", _i32),
+        ("n_rows", _i32), ("x", Tensor * 3), ("d_out", Tensor), ("dscores", _vp), ("ws", _vp),
+    ]
+
+
+class CastArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("heads", _i32), ("n_rows", _i32),
+        ("n_tensors", _i32), ("src", Tensor * 3), ("dst", Tensor * 3),
+    ]
+
+
+MIX_BWD_PARTS = 64  # include/vorta_hip.h VORTA_MIX_BWD_PARTS
+
 # every symbol include/vorta_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "vorta_attn_fwd": (C.c_int, [C.POINTER(AttnArgs), _vp]),
@@ -162,6 +185,9 @@ SYMBOLS = {
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
     "vorta_qk_norm_rope": (C.c_int, [C.POINTER(NormRopeArgs), _vp]),
     "vorta_mix_experts": (C.c_int, [C.POINTER(MixArgs), _vp]),
+    "vorta_attn_bwd": (C.c_int, [C.POINTER(AttnBwdArgs), _vp]),
+    "vorta_mix_experts_bwd": (C.c_int, [C.POINTER(MixBwdArgs), _vp]),
+    "vorta_cast_grads": (C.c_int, [C.POINTER(CastArgs), _vp]),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "vorta_permute_heads": (C.c_int, [C.POINTER(PermuteArgs), _vp]),
     "vorta_abi_version": (C.c_int, []),
@@ -202,7 +228,8 @@ def lib():
     if h.vorta_abi_version() != ABI_VERSION:
         raise VortaHipError(f"ABI mismatch: library {h.vorta_abi_version()} vs binding {ABI_VERSION}")
     for which, st in enumerate((Tensor, AttnArgs, CoresetArgs, StaArgs, RouterArgs, NormRopeArgs, MixArgs, Fp8QuantArgs,
-                                AttnFp8Ext, PermuteArgs, Fp8VArgs, I8QuantArgs, AttnI8Ext)):
+                                AttnFp8Ext, PermuteArgs, Fp8VArgs, I8QuantArgs, AttnI8Ext, AttnBwdArgs, MixBwdArgs,
+                                CastArgs)):
         if h.vorta_sizeof(which) != C.sizeof(st):
             raise VortaHipError(f"struct layout mismatch for {st.__name__}: "
                                 f"C {h.vorta_sizeof(which)} vs ctypes {C.sizeof(st)}")

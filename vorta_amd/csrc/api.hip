@@ -39,6 +39,9 @@ extern "C" int vorta_sizeof(int which) {
     case 10: return (int)sizeof(vorta_fp8_v_args);
     case 11: return (int)sizeof(vorta_i8_quant_args);
     case 12: return (int)sizeof(vorta_attn_i8_ext);
+    case 13: return (int)sizeof(vorta_attn_bwd_args);
+    case 14: return (int)sizeof(vorta_mix_bwd_args);
+    case 15: return (int)sizeof(vorta_cast_args);
     default: return -1;
   }
 }

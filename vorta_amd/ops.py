@@ -838,6 +838,80 @@ def mix_experts(xs, scores: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# keywords of attn_fwd that do not change the gradient (split keys, workgroup size, fused-grid hints, timing tags)
+_BWD_DROPPED = ("n_splits", "block_rows", "fused_n_splits", "fused_first", "flops", "tag", "variant", "v_descale", "fp8_opts", "i8")
+
+
+def _f32_tensor(t: torch.Tensor, like: torch.Tensor, name: str) -> _C.Tensor:
+    if t is None or t.dtype != torch.float32 or t.shape != like.shape or t.device != like.device:
+        raise ValueError(f"attn_bwd: {name} must be a float32 tensor of shape {tuple(like.shape)} on the inputs' device")
+    return _tensor(t)
+
+
+def attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, dq: torch.Tensor,
+             dk: torch.Tensor, dv: torch.Tensor, *, do_scale: Optional[torch.Tensor] = None, **kw) -> None:
+    """vorta_attn_bwd (include/vorta_hip.h): the gradient of the attn_fwd launch with the same keywords, ADDED to the float32
+    (H,S,D) buffers dq / dk / dv (the caller zeroes them).  `o` is the forward's output, `d_o` its gradient (16-bit, same
+    shape); `do_scale`: optional 1-D view in the inputs' dtype, one weight per HEAD id (the soft mixture's scores[:, e]).
+    The keywords that only shape the forward's launch (n_splits, block_rows with no q_block_table, the fused-grid hints,
+    tag / flops) are accepted and dropped.  dq is bit-reproducible, dk / dv are not (float atomics)."""
+    if q.dtype not in _DT or not (q.dtype == k.dtype == v.dtype == o.dtype == d_o.dtype):
+        raise ValueError("attn_bwd: q, k, v, o, d_o must share dtype bf16 or fp16 (there is no 8-bit backward)")
+    if d_o.shape != o.shape:
+        raise ValueError("attn_bwd: d_o must have the shape of o")
+    _require_gpu(d_o, dq, dk, dv, do_scale)
+    table = kw.get("q_block_table") is not None
+    kw = {key: val for key, val in kw.items() if key not in _BWD_DROPPED or (key == "block_rows" and table)}
+    f, _ = _attn_args(q, k, v, o, **kw)
+    a = _C.AttnBwdArgs()
+    a.struct_size = C.sizeof(_C.AttnBwdArgs)
+    a.fwd = f
+    a.d_o = _tensor(d_o)
+    if do_scale is not None:
+        if do_scale.dtype != q.dtype or do_scale.dim() != 1:
+            raise ValueError("attn_bwd: do_scale is a 1-D view (one weight per head id) in the inputs' dtype")
+        a.do_scale, a.do_scale_stride_h = do_scale.data_ptr(), do_scale.stride(0)
+    a.dq, a.dk, a.dv = _f32_tensor(dq, q, "dq"), _f32_tensor(dk, k, "dk"), _f32_tensor(dv, v, "dv")
+    _C.check(_C.lib().vorta_attn_bwd(C.byref(a), _stream()), "vorta_attn_bwd")
+
+
+def mix_experts_bwd(xs, d_out: torch.Tensor) -> torch.Tensor:
+    """vorta_mix_experts_bwd: dscores[h][e] = <d_out[h], xs[e][h]> as float32 (H,3), for (H,N,D) views; deterministic."""
+    _require_gpu(d_out, *xs)
+    if len(xs) != 3 or d_out.dtype not in _DT:
+        raise ValueError("mix_experts_bwd takes the saved outputs of the three experts and a bf16 / fp16 d_out")
+    H, N, D = d_out.shape
+    a = _C.MixBwdArgs()
+    a.struct_size = C.sizeof(_C.MixBwdArgs)
+    a.dtype, a.head_dim, a.heads, a.n_experts, a.n_rows = _DT[d_out.dtype], D, H, 3, N
+    for e in range(3):
+        if xs[e].shape != d_out.shape or xs[e].dtype != d_out.dtype:
+            raise ValueError("mix_experts_bwd: expert outputs must match d_out's shape and dtype")
+        a.x[e] = _tensor(xs[e])
+    a.d_out = _tensor(d_out)
+    dscores = torch.empty((H, 3), dtype=torch.float32, device=d_out.device)
+    ws = torch.empty(H * _C.MIX_BWD_PARTS * 4, dtype=torch.float32, device=d_out.device)
+    a.dscores, a.ws = dscores.data_ptr(), ws.data_ptr()
+    _C.check(_C.lib().vorta_mix_experts_bwd(C.byref(a), _stream()), "vorta_mix_experts_bwd")
+    return dscores
+
+
+def cast_grads(srcs, dsts) -> None:
+    """vorta_cast_grads: up to three float32 (H,N,D) buffers -> 16-bit (H,N,D) views in one launch, round to nearest even."""
+    _require_gpu(*srcs, *dsts)
+    if not srcs or len(srcs) != len(dsts) or len(srcs) > 3 or dsts[0].dtype not in _DT:
+        raise ValueError("cast_grads takes one to three (float32 source, bf16 / fp16 destination) pairs")
+    H, N, D = dsts[0].shape
+    a = _C.CastArgs()
+    a.struct_size = C.sizeof(_C.CastArgs)
+    a.dtype, a.head_dim, a.heads, a.n_rows, a.n_tensors = _DT[dsts[0].dtype], D, H, N, len(srcs)
+    for t, (x, y) in enumerate(zip(srcs, dsts)):
+        if x.dtype != torch.float32 or y.dtype != dsts[0].dtype or tuple(x.shape) != (H, N, D) or tuple(y.shape) != (H, N, D):
+            raise ValueError("cast_grads: every pair must be (heads, rows, D) of one shape, float32 -> one 16-bit dtype")
+        a.src[t], a.dst[t] = _tensor(x), _tensor(y)
+    _C.check(_C.lib().vorta_cast_grads(C.byref(a), _stream()), "vorta_cast_grads")
+
+
 def permute_heads(srcs, dsts, src_map: Optional[torch.Tensor] = None, dst_map: Optional[torch.Tensor] = None) -> None:
     """vorta_permute_heads: dsts[t][dst_map[h]] = srcs[t][src_map[h]] for up to four (H,N,D) views in one launch (the
     staging passes of the Ulysses exchange, vorta/ulysses/utils.py:61-91).  Maps: int32 device tensors of H entries."""

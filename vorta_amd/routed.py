@@ -289,7 +289,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                      out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
                      concurrent: bool = False, fused: bool = True, sliding_block_rows: int = 0,
                      expert_outs: Optional[Sequence[torch.Tensor]] = None, fp8=None, fp8_operands=None,
-                     operands: Optional[AttnOperands] = None, kv_splits: int = 1) -> torch.Tensor:
+                     operands: Optional[AttnOperands] = None, kv_splits: int = 1,
+                     record: Optional[list] = None) -> torch.Tensor:
     """q,k,v: (1,H,S+T,D) [hunyuan: video then text] or (1,H,S,D) [wan].  Returns (1,H,S+T,D).
 
     hunyuan: hunyuan.py:556-605 (TripleEval.__call__ steps 5.1-5.4);  wan: wan.py:351-383.
@@ -308,7 +309,9 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     buffers once, vorta_amd/ulysses/engine.py RecvOperands); `fp8` and `fp8_operands` are then not read.
     kv_splits > 1: the full-attention and coreset launches cut their KEYS into that many parts (+ a merge kernel) -- for
     a sequence-parallel rank whose one or two heads leave the chip under one round of workgroups, where a layer lasts as
-    long as one workgroup's key loop; changes the summation order, so it is never chosen silently."""
+    long as one workgroup's key loop; changes the summation order, so it is never chosen silently.
+    record: a list that receives the launches as launched -- the dictionaries of ops.attn_fwd keywords (q / k / v / out,
+    tables, head lists, lengths), in launch order; the backward replays them through ops.attn_bwd (`_replay_backward`)."""
     if q.dim() == 4 and q.shape[0] != 1:
         # hunyuan.py:168 asserts batch 1; Wan's CFG runs two batch-1 forwards (pipeline_wan.py:322-344)
         raise AssertionError(f"Batch size {q.shape[0]} is not supported by routed_attention.")
@@ -420,6 +423,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         return calls
 
     def launch(calls):
+        if record is not None:
+            record.extend(calls)
         for c in calls:
             c = {key: val for key, val in c.items() if key not in ("fused_n_splits", "fused_first")}
             ops.attn_fwd(c.pop("q"), c.pop("k"), c.pop("v"), c.pop("out"), **c)
@@ -440,6 +445,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             slot_part = lambda i, hl, which=which: pparts[i][which]  # noqa: E731
             calls = [c for fn, on in experts if on for c in fn()]
             if fused:
+                if record is not None:
+                    record.extend(calls)
                 ops.attn_fwd_batch(calls)
             else:
                 launch(calls)
@@ -447,6 +454,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     if not concurrent:
         calls = [c for fn, on in experts if on for c in fn()]
         if fused:
+            if record is not None:
+                record.extend(calls)
             ops.attn_fwd_batch(calls)
         else:
             launch(calls)
@@ -478,7 +487,8 @@ def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
     """Training-time FORWARD: every head through all three experts, outputs mixed with the routing
     scores of batch item 0 -- hunyuan.py:375-408,509-513 / wan.py:226-241,296-300.  The three experts over all H
     heads run as one fused grid into three buffers; `vorta_mix_experts` does the weighted sum in one pass.
-    No autograd: the library has no backward kernels (router training itself is out of scope)."""
+    No autograd: the library has no backward kernels (router training itself is out of scope).
+    (The differentiable form of this operator is `soft_mixture_attention_autograd`, below.)"""
     H = q.shape[-3]
     if out is None:
         out = torch.empty_like(q)
@@ -488,6 +498,98 @@ def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
                      text_valid=text_valid, scale=scale, expert_outs=bufs, fp8=False)
     ops.mix_experts([b[0] if b.dim() == 4 else b for b in bufs], routing_score, out[0] if out.dim() == 4 else out)
     return out
+
+
+def _replay_backward(launches, d_out: torch.Tensor, dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor,
+                     weight_of=None) -> None:
+    """one ops.attn_bwd per recorded forward launch, with the SAME dictionaries (forward and backward cannot disagree on a
+    table); `weight_of(launch, out)` = the per-head weight of the launch's output in the loss (None: 1)"""
+    for c in launches:
+        c = dict(c)
+        q, k, v, o = c.pop("q"), c.pop("k"), c.pop("v"), c.pop("out")
+        ops.attn_bwd(q, k, v, o, d_out, dq, dk, dv, do_scale=None if weight_of is None else weight_of(c, o), **c)
+
+
+class _SoftMixture(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, routing_score, geom, model, text_len, text_valid, scale):
+        H = q.shape[-3]
+        out = torch.empty_like(q)
+        bufs = [torch.empty_like(out) for _ in range(3)]
+        launches: list = []
+        routed_attention(q, k, v, HeadRouting.every_head_everywhere(H, q.device), geom, model=model, text_len=text_len,
+                         text_valid=text_valid, scale=scale, expert_outs=bufs, fp8=False, record=launches)
+        ops.mix_experts([b[0] if b.dim() == 4 else b for b in bufs], routing_score, out[0] if out.dim() == 4 else out)
+        ctx.save_for_backward(q, k, v, routing_score, *bufs)
+        ctx.launches = launches
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q, k, v, routing_score, *bufs = ctx.saved_tensors
+        fold = lambda x: x[0] if x.dim() == 4 else x  # noqa: E731
+        q3, bufs3 = fold(q), [fold(b) for b in bufs]
+        g3 = fold(d_out.contiguous())
+        acc = [torch.zeros(q3.shape, dtype=torch.float32, device=q.device) for _ in range(3)]
+        dscores = ops.mix_experts_bwd(bufs3, g3)
+        sc = routing_score[0].to(q.dtype).contiguous()  # what ops.mix_experts read in the forward
+
+        def weight_of(_, o):  # the launch wrote expert e's buffer: its output enters the mixture with scores[:, e]
+            e = next(i for i, b in enumerate(bufs3) if b.data_ptr() == o.data_ptr())
+            return sc[:, e]
+
+        _replay_backward(ctx.launches, g3, acc[0], acc[1], acc[2], weight_of)
+        grads = [torch.empty_like(q3) for _ in range(3)]
+        ops.cast_grads(acc, grads)
+        d_sc = torch.zeros_like(routing_score)  # batch items > 0 are not read by the forward
+        d_sc[0] = dscores.to(routing_score.dtype)
+        dq, dk, dv = (g.view(q.shape) for g in grads)
+        return dq, dk, dv, d_sc, None, None, None, None, None
+
+
+def soft_mixture_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,
+                                    geom: RoutedGeometry, *, model: str, text_len: int = 0, text_valid: int = 0,
+                                    scale: Optional[float] = None) -> torch.Tensor:
+    """`soft_mixture_attention` as a differentiable operator (router training: the loss reaches the routing scores and,
+    through q, k, v, every earlier layer).  The forward is the same launches and gives the same bits; it keeps q, k, v, the
+    scores, the three expert outputs and the launches as recorded.  The backward zeroes three float32 (H,N,D) buffers,
+    takes dscores[h][e] = <d_out[h], x_e[h]> (ops.mix_experts_bwd), replays every forward launch through ops.attn_bwd with
+    the weight scores[:, e] of its expert, and rounds dq, dk, dv once (ops.cast_grads).  The coreset keep / drop lists and
+    the sliding-tile tables are constants of the backward (the reference ranks with argsort: no gradient flows through the
+    selection there either, coreset_select.py:98-124).  dk / dv are not bit-reproducible (float atomics); dq and dscores are.
+    q, k, v: contiguous (1,H,N,D), like the forward's."""
+    return _SoftMixture.apply(q, k, v, routing_score, geom, model, text_len, text_valid, scale)
+
+
+class _Dense(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, kv_valid, q_valid, scale):
+        out = torch.empty_like(q)
+        Sq, Skv = q.shape[-2], k.shape[-2]
+        launch = dict(n_q=Sq, n_kv=Skv if kv_valid is None else kv_valid, q_valid=Sq if q_valid is None else q_valid,
+                      scale=scale)
+        ops.attn_fwd(ops.fold_heads(q), ops.fold_heads(k), ops.fold_heads(v), ops.fold_heads(out), **launch)
+        ctx.save_for_backward(q, k, v, out)
+        ctx.launch = launch
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q, k, v, out = ctx.saved_tensors
+        f = ops.fold_heads
+        acc = [torch.zeros(f(x).shape, dtype=torch.float32, device=q.device) for x in (q, k, v)]
+        ops.attn_bwd(f(q), f(k), f(v), f(out), f(d_out.contiguous()), acc[0], acc[1], acc[2], **ctx.launch)
+        grads = [torch.empty_like(x) for x in (q, k, v)]
+        ops.cast_grads(acc[:1], [f(grads[0])])
+        ops.cast_grads(acc[1:], [f(grads[1]), f(grads[2])])
+        return grads[0], grads[1], grads[2], None, None, None
+
+
+def dense_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, kv_valid: Optional[int] = None,
+                             q_valid: Optional[int] = None, scale: Optional[float] = None) -> torch.Tensor:
+    """`dense_attention` (the teacher path, use_original_attn=True: hunyuan.py:167-176, wan.py:134-145) as a differentiable
+    operator: the same launch forward, ops.attn_bwd + ops.cast_grads backward.  (B,H,Sq,D) x (B,H,Skv,D), contiguous."""
+    return _Dense.apply(q, k, v, kv_valid, q_valid, scale)
 
 
 def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, kv_valid: Optional[int] = None,

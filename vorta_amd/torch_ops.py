@@ -21,6 +21,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
                                                       -> ()    mutates out        the per-layer routed op (routed.py)
     vorta::soft_mixture_attention(q,k,v, scores, out, latent, ...) -> () mutates out   the training-time forward
     vorta::route_plan_(temb, weight, bias, heads, tau, n_experts, scores, expert, lists, counts) -> () mutates the four
+    vorta::soft_mixture_attention_grad(q,k,v, scores, latent, ...) -> out   functional, differentiable (register_autograd);
+    vorta::soft_mixture_attention_bwd(q,k,v, scores, d_out, latent, ...) -> (dq, dk, dv, dscores)   its autograd formula
 """
 from typing import List, Optional, Tuple
 
@@ -176,6 +178,62 @@ def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
 @soft_mixture_attention.register_fake
 def _(q, k, v, routing_score, out, latent, tile, window, group, rate, model, text_len=0, text_valid=0, scale=0.0) -> None:
     return None
+
+
+@torch.library.custom_op("vorta::soft_mixture_attention_grad", mutates_args=(), device_types="cuda")
+def soft_mixture_attention_grad(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,
+                                latent: List[int], tile: List[int], window: List[int], group: List[int], rate: float,
+                                model: str, text_len: int = 0, text_valid: int = 0, scale: float = 0.0) -> torch.Tensor:
+    """The differentiable soft mixture (functional: returns `out`; the mutating vorta::soft_mixture_attention has no
+    gradient).  Same launches and bits as routed.soft_mixture_attention; its autograd formula is
+    vorta::soft_mixture_attention_bwd."""
+    from . import routed
+    geom = routed.geometry_for(latent, tile, window, group, rate, q.device)
+    return routed.soft_mixture_attention(q, k, v, routing_score, geom, model=model, text_len=text_len, text_valid=text_valid,
+                                         scale=None if scale <= 0.0 else scale)
+
+
+@soft_mixture_attention_grad.register_fake
+def _(q, k, v, routing_score, latent, tile, window, group, rate, model, text_len=0, text_valid=0, scale=0.0):
+    return torch.empty_like(q)
+
+
+@torch.library.custom_op("vorta::soft_mixture_attention_bwd", mutates_args=(), device_types="cuda")
+def soft_mixture_attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,
+                               d_out: torch.Tensor, latent: List[int], tile: List[int], window: List[int], group: List[int],
+                               rate: float, model: str, text_len: int = 0, text_valid: int = 0,
+                               scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dq, dk, dv, dscores) of vorta::soft_mixture_attention_grad.  A traced operator keeps no Python state, so the three
+    expert outputs and the launch tables are recomputed here (one more forward, deterministic: the same bits and the same
+    tables the forward produced) and then differentiated as routed.soft_mixture_attention_autograd does."""
+    from . import routed
+    geom = routed.geometry_for(latent, tile, window, group, rate, q.device)
+    with torch.enable_grad():
+        leaves = [x.detach().requires_grad_(True) for x in (q, k, v, routing_score)]
+        out = routed.soft_mixture_attention_autograd(*leaves, geom, model=model, text_len=text_len, text_valid=text_valid,
+                                                     scale=None if scale <= 0.0 else scale)
+        dq, dk, dv, dsc = torch.autograd.grad(out, leaves, d_out)
+    return dq, dk, dv, dsc
+
+
+@soft_mixture_attention_bwd.register_fake
+def _(q, k, v, routing_score, d_out, latent, tile, window, group, rate, model, text_len=0, text_valid=0, scale=0.0):
+    return torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(routing_score)
+
+
+def _soft_mixture_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:4])
+    ctx.rest = inputs[4:]
+
+
+def _soft_mixture_backward(ctx, d_out):
+    q, k, v, sc = ctx.saved_tensors
+    grads = torch.ops.vorta.soft_mixture_attention_bwd(q, k, v, sc, d_out.contiguous(), *ctx.rest)
+    return (*grads,) + (None,) * len(ctx.rest)
+
+
+torch.library.register_autograd("vorta::soft_mixture_attention_grad", _soft_mixture_backward,
+                                setup_context=_soft_mixture_setup)
 
 
 @torch.library.custom_op("vorta::route_plan_", mutates_args=("scores", "expert", "lists", "counts"), device_types="cuda")
