@@ -40,7 +40,9 @@ extern "C" {
                                 7: the int8-score kernel writes its probabilities with one power-of-two scale per query row
                                    and 32 keys (vorta_attn_i8_ext.defer becomes the reference-point trigger in binades, default 24);
                                 8: adds vorta_i8_tail_flags and vorta_split_heads (per-head choice between int8 and 16-bit scores)
-                                9: adds the backward entry points (vorta_attn_bwd, vorta_mix_experts_bwd, vorta_cast_grads) */
+                                9: adds the backward entry points (vorta_attn_bwd, vorta_mix_experts_bwd, vorta_cast_grads);
+                                   9 also carries vorta_qk_norm_rope_bwd (a pure addition: every earlier call means what it meant;
+                                   a binding asks for the symbol and for vorta_sizeof(16) to tell the two libraries apart) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -536,6 +538,39 @@ typedef struct vorta_norm_rope_args {
 int vorta_qk_norm_rope(const vorta_norm_rope_args* args, void* hip_stream);
 
 /*
+ * vorta_qk_norm_rope_bwd (ABI 9, added after the other backward entry points) -- the gradient of ONE vorta_qk_norm_rope call
+ * for the same argument block.  The reference differentiates hunyuan.py:62-104 / wan.py:85-100 with torch autograd; this is
+ * the derivative of those lines in one pass.  With y = x r w, r = rsqrt(mean(x^2) + eps) (mean over D, or over H*D when
+ * across_heads), out = the interleaved-pair rotation of y, and g = d(out), in fp32:
+ *     dy[2i]   = g[2i] cos[2i]     + g[2i+1] sin[2i+1]
+ *     dy[2i+1] = g[2i+1] cos[2i+1] - g[2i]   sin[2i]                (rows >= rope_tokens, or no table: dy = g)
+ *     dx       = r (w dy) - x r^3 / n sum_n(w dy x)                  (n = D or H*D; w = 1 when weight is NULL)
+ *     dweight[c] = sum over the call's rows of dy[c] x[c] r          ([D] or [H*D], float32)
+ * fwd.x is the forward's INPUT (pre-norm; read only -- the forward ran in place, so the caller kept a copy).  g and dx are
+ * 16-bit (H,S,D) views of fwd.dtype with strides of their own; dx may alias g.  Only tokens [token_offset, token_offset +
+ * n_tokens) of dx are written: a caller that covered a tensor with several forward calls (video and text ranges) covers dx
+ * with the same calls.  dweight (may be NULL) is OVERWRITTEN by every call -- each call owns only its rows -- and the caller
+ * adds the calls' results.  It is deterministic: every workgroup reduces its rows to one fp32 partial per channel in `ws`
+ * (caller-owned, ws_floats >= min(ceil(n_tokens / 4), VORTA_NORM_ROPE_BWD_PARTS) * channels floats, 16-byte aligned; only
+ * needed with dweight) and a second launch adds the partials in a fixed order; no float atomics.
+ * Codes as vorta_qk_norm_rope: head_dim != 128, a dtype other than bf16 / fp16, or more than 40 heads across_heads are
+ * VORTA_EUNSUPPORTED; n_tokens == 0 returns VORTA_OK and zeroes dweight when it is given.
+ */
+#define VORTA_NORM_ROPE_BWD_PARTS 1024
+typedef struct vorta_norm_rope_bwd_args {
+  uint32_t struct_size; /* = sizeof(vorta_norm_rope_bwd_args) */
+  int32_t reserved;
+  vorta_norm_rope_args fwd; /* the forward call; fwd.x = the forward's INPUT (read) */
+  vorta_tensor g;           /* gradient of the forward's output, fwd.dtype */
+  vorta_tensor dx;          /* out, fwd.dtype; may alias g */
+  float* dweight;           /* out [D] or [H*D], or NULL */
+  float* ws;                /* workspace for dweight's partial sums (NULL without dweight) */
+  int64_t ws_floats;
+} vorta_norm_rope_bwd_args;
+
+int vorta_qk_norm_rope_bwd(const vorta_norm_rope_bwd_args* args, void* hip_stream);
+
+/*
  * vorta_mix_experts -- the score-weighted sum of the training-time forward:
  *   out[h][row][:] = sum_e scores[h][e] * x[e][h][row][:]        (fp32 accumulation, one rounding)
  * `_combine_attn_outputs`, hunyuan.py:509-513 == wan.py:296-300 (stack + multiply + sum over the expert axis).
@@ -623,7 +658,8 @@ const char* vorta_build_info(void); /* static string: arch, compiler */
 int vorta_last_hip_error(void);     /* last hipError_t seen by a failed launch in this thread */
 int vorta_sizeof(int which);        /* 0 tensor, 1 attn_args, 2 coreset_args, 3 sta_args, 4 router_args, 5 norm_rope_args,
                                        6 mix_args, 7 fp8_quant_args, 8 attn_fp8_ext, 9 permute_args, 10 fp8_v_args,
-                                       11 i8_quant_args, 12 attn_i8_ext, 13 attn_bwd_args, 14 mix_bwd_args, 15 cast_args */
+                                       11 i8_quant_args, 12 attn_i8_ext, 13 attn_bwd_args, 14 mix_bwd_args, 15 cast_args,
+                                       16 norm_rope_bwd_args (-1 from a library without vorta_qk_norm_rope_bwd) */
 
 #ifdef __cplusplus
 }

@@ -157,7 +157,15 @@ class CastArgs(C.Structure):
     ]
 
 
+class NormRopeBwdArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("reserved", _i32), ("fwd", NormRopeArgs), ("g", Tensor), ("dx", Tensor),
+        ("dweight", _vp), ("ws", _vp), ("ws_floats", _i64),
+    ]
+
+
 MIX_BWD_PARTS = 64  # include/vorta_hip.h VORTA_MIX_BWD_PARTS
+NORM_ROPE_BWD_PARTS = 1024  # include/vorta_hip.h VORTA_NORM_ROPE_BWD_PARTS
 
 # every symbol include/vorta_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -184,6 +192,7 @@ SYMBOLS = {
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
     "vorta_qk_norm_rope": (C.c_int, [C.POINTER(NormRopeArgs), _vp]),
+    "vorta_qk_norm_rope_bwd": (C.c_int, [C.POINTER(NormRopeBwdArgs), _vp]),
     "vorta_mix_experts": (C.c_int, [C.POINTER(MixArgs), _vp]),
     "vorta_attn_bwd": (C.c_int, [C.POINTER(AttnBwdArgs), _vp]),
     "vorta_mix_experts_bwd": (C.c_int, [C.POINTER(MixBwdArgs), _vp]),
@@ -222,14 +231,19 @@ def lib():
     except OSError as e:  # pragma: no cover
         raise VortaHipError(f"could not load {LIB_PATH}: {e}") from e
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(h, name)  # AttributeError if the library does not export a declared symbol
+        try:
+            fn = getattr(h, name)
+        except AttributeError:
+            # ABI 9 gained vorta_qk_norm_rope_bwd without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks it
+            raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
+                                "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
         fn.argtypes = args
     if h.vorta_abi_version() != ABI_VERSION:
         raise VortaHipError(f"ABI mismatch: library {h.vorta_abi_version()} vs binding {ABI_VERSION}")
     for which, st in enumerate((Tensor, AttnArgs, CoresetArgs, StaArgs, RouterArgs, NormRopeArgs, MixArgs, Fp8QuantArgs,
                                 AttnFp8Ext, PermuteArgs, Fp8VArgs, I8QuantArgs, AttnI8Ext, AttnBwdArgs, MixBwdArgs,
-                                CastArgs)):
+                                CastArgs, NormRopeBwdArgs)):
         if h.vorta_sizeof(which) != C.sizeof(st):
             raise VortaHipError(f"struct layout mismatch for {st.__name__}: "
                                 f"C {h.vorta_sizeof(which)} vs ctypes {C.sizeof(st)}")

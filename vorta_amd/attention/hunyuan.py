@@ -11,7 +11,7 @@ import torch
 
 from .. import ops
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import HeadRouting
+from ..routed import HeadRouting, dense_attention_autograd, geometry_for, qk_norm_rope_autograd, soft_mixture_attention_autograd
 from ..ulysses import SP_STATE, shrink_dim
 from .coreset_select import LowresGroupInfo
 from .sliding_tile import SlidingTileDescriptor
@@ -46,6 +46,14 @@ def fused_norm_rope(x: torch.Tensor, norm, rope: Optional[Tuple[torch.Tensor, to
     cos, sin = rope if rope is not None else (None, None)
     torch.ops.vorta.qk_norm_rope(x[0], w, float(norm.eps), cos, sin, rope_tokens if rope is not None else 0)
     return x
+
+
+def fused_norm_rope_grad(x: torch.Tensor, norm, rope: Optional[Tuple[torch.Tensor, torch.Tensor]], rope_tokens: int = 0):
+    """`fused_norm_rope` for a training graph: out of place (a contiguous copy of x), differentiable in x and the norm's
+    weight (routed.qk_norm_rope_autograd: one HIP pass forward, one backward)."""
+    cos, sin = rope if rope is not None else (None, None)
+    return qk_norm_rope_autograd(x, getattr(norm, "weight", None), float(norm.eps), cos, sin,
+                                 rope_tokens if rope is not None else 0)
 
 
 # project video and text tokens straight into ONE (1, S+T, H*D) buffer per tensor: the `torch.cat([q, eq], dim=2)` of a
@@ -91,19 +99,41 @@ def _valid_keys(attention_mask: torch.Tensor) -> torch.Tensor:
 
 
 class HunyuanVideoFlashAttnProcessor:
-    """Dense attention for every head: the --native_attention path (hunyuan.py:35-238)."""
+    """Dense attention for every head: the --native_attention path (hunyuan.py:35-238).
 
-    def __init__(self):
+    `differentiable=True` (off by default): a call in grad mode builds an autograd graph from the output back to
+    hidden_states, encoder_hidden_states and the module parameters -- projections through the modules, norm + RoPE through
+    `qk_norm_rope_autograd`, attention through `dense_attention_autograd`.  Under torch.no_grad() such a processor takes
+    the inference path and gives its bits."""
+
+    _HAS_BACKWARD = True  # the concrete class can sit in a training graph (the Eval classes cannot: hard top-1)
+
+    def __init__(self, differentiable: bool = False):
         ops._C.lib()  # fail loudly now if libvorta_hip.so is missing: there is no fallback path
+        if differentiable and not type(self)._HAS_BACKWARD:
+            raise ValueError(f"{type(self).__name__} routes every head to its top-1 expert, which has no gradient: "
+                             "differentiable=True belongs to the dense and the soft-mixture (Train) processors")
+        self.differentiable = bool(differentiable)
+
+    def _grad_path(self) -> bool:
+        """build an autograd graph in this call?  (never under sequence parallelism: the exchange has no autograd)"""
+        if not (self.differentiable and torch.is_grad_enabled()):
+            return False
+        if SP_STATE.enabled:
+            raise NotImplementedError("differentiable=True is not sequence-parallel in this build: the Ulysses exchange "
+                                      "has no autograd")
+        return True
 
     # -- steps 1-4 of hunyuan.py:42-134: everything before the attention boundary ----------------------
-    def _project(self, attn, hidden_states, encoder_hidden_states, image_rotary_emb):
+    def _project(self, attn, hidden_states, encoder_hidden_states, image_rotary_emb, grad: bool = False):
+        """grad=True: every step stays visible to autograd -- no GEMM `out=`, no in-place kernel"""
         single_stream = attn.add_q_proj is None  # single blocks carry text inside hidden_states
         T = encoder_hidden_states.shape[1]
         rope = None
         if image_rotary_emb is not None:
             rope = (shrink_dim(image_rotary_emb[0], dim=0), shrink_dim(image_rotary_emb[1], dim=0))
-        joint = self._project_joint(attn, hidden_states, encoder_hidden_states, rope, single_stream)
+        norm_rope = fused_norm_rope_grad if grad else fused_norm_rope
+        joint = None if grad else self._project_joint(attn, hidden_states, encoder_hidden_states, rope, single_stream)
         if joint is not None:
             return (*joint, T)
         if single_stream:
@@ -114,8 +144,8 @@ class HunyuanVideoFlashAttnProcessor:
         n_video = q.shape[2] - (T if single_stream else 0)
         if q.shape[0] == 1 and _fusable_norm(attn.norm_q, q, 128) and _fusable_norm(attn.norm_k, k, 128):
             # one in-place HIP pass per tensor: norm everywhere, rotation on the video tokens only
-            fused_norm_rope(q, attn.norm_q, rope, n_video)
-            fused_norm_rope(k, attn.norm_k, rope, n_video)
+            q = norm_rope(q, attn.norm_q, rope, n_video)
+            k = norm_rope(k, attn.norm_k, rope, n_video)
         else:
             if attn.norm_q is not None:
                 q = attn.norm_q(q)
@@ -132,8 +162,8 @@ class HunyuanVideoFlashAttnProcessor:
             ek = attn.add_k_proj(encoder_hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
             ev = attn.add_v_proj(encoder_hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
             if eq.shape[0] == 1 and _fusable_norm(attn.norm_added_q, eq, 128) and _fusable_norm(attn.norm_added_k, ek, 128):
-                fused_norm_rope(eq, attn.norm_added_q, None)
-                fused_norm_rope(ek, attn.norm_added_k, None)
+                eq = norm_rope(eq, attn.norm_added_q, None)
+                ek = norm_rope(ek, attn.norm_added_k, None)
             else:
                 if attn.norm_added_q is not None:
                     eq = attn.norm_added_q(eq)
@@ -219,17 +249,33 @@ class HunyuanVideoFlashAttnProcessor:
         torch.ops.vorta.attn_fwd(q[0], k[0], v[0], out[0], N, N, q_valid=N, n_kv_dev=L, q_valid_dev=L)
         return buf
 
-    @torch.no_grad()  # forward only: the HIP ops have no backward (training is out of scope)
-    def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask, image_rotary_emb):
+    def _dense_grad(self, q, k, v, attention_mask):
+        """`_dense` behind autograd.  dense_attention_autograd takes the valid-key count as a host integer: read once here,
+        as the reference does (hunyuan.py:169); the no-grad path keeps its sync-free form."""
+        assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
+        L = min(max(int(_valid_keys(attention_mask).item()), 1), q.shape[2])
+        out = dense_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), kv_valid=L, q_valid=L)
+        return out.transpose(1, 2)  # (B, S+T, H, D)
+
+    @torch.no_grad()  # forward only
+    def _call_no_grad(self, attn, hidden_states, encoder_hidden_states, attention_mask, image_rotary_emb):
         q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb)
         return self._output(attn, self._dense(q, k, v, attention_mask, T), T)
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask, image_rotary_emb):
+        if not self._grad_path():  # the default: no autograd graph, whatever the inputs ask for
+            return self._call_no_grad(attn, hidden_states, encoder_hidden_states, attention_mask, image_rotary_emb)
+        q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb, grad=True)
+        return self._output(attn, self._dense_grad(q, k, v, attention_mask), T)
 
 
 class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
     """Inference-time routed attention: hard top-1 expert per head (hunyuan.py:516-661)."""
 
-    def __init__(self, check_input: bool = False):
-        super().__init__()
+    _HAS_BACKWARD = False
+
+    def __init__(self, check_input: bool = False, differentiable: bool = False):
+        super().__init__(differentiable)
         self.check_input = check_input
 
     def _check_input(self, hidden_states, lowres_group_info, latent_shape, window_size, tile_size):
@@ -284,7 +330,12 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
     """Training-time soft mixture of the three experts (hunyuan.py:241-513), FORWARD only: every head runs all
     three experts and the outputs are summed with the routing scores.  There are no backward
     kernels: a call that would need gradients raises instead of silently returning a detached result.
-    `use_original_attn=True` (the dense teacher, hunyuan.py:312-321) is the dense processor."""
+    `use_original_attn=True` (the dense teacher, hunyuan.py:312-321) is the dense processor.
+    With `differentiable=True` a call in grad mode is the TRAINING forward instead: the same launches behind
+    `soft_mixture_attention_autograd`, with gradients for hidden_states, encoder_hidden_states, routing_score and the
+    module parameters."""
+
+    _HAS_BACKWARD = True
 
     def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask, image_rotary_emb,
                  use_original_attn: bool = False, routing_score: Optional[torch.Tensor] = None,
@@ -295,6 +346,16 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
         if use_original_attn:
             return HunyuanVideoFlashAttnProcessor.__call__(self, attn, hidden_states, encoder_hidden_states,
                                                            attention_mask, image_rotary_emb)
+        if self._grad_path():
+            self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
+            q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb, grad=True)
+            assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
+            te = self._text_valid(attention_mask, T, flex_attn_mask_func)
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            out = soft_mixture_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), routing_score, geom,
+                                                  model="hunyuan", text_len=T, text_valid=te)
+            return self._output(attn, out.transpose(1, 2), T)
         if torch.is_grad_enabled() and (hidden_states.requires_grad or routing_score.requires_grad):
             raise NotImplementedError("the soft-mixture forward of this build has no backward: call it under "
                                       "torch.no_grad() (router training is outside the inference hot path)")

@@ -9,7 +9,8 @@ import torch
 
 from .. import ops
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import HeadRouting, dense_attention
+from ..routed import (HeadRouting, dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
+                      soft_mixture_attention_autograd)
 from ..ulysses import SP_STATE, shrink_dim
 from .coreset_select import LowresGroupInfo
 from .sliding_tile import SlidingTileDescriptor
@@ -39,13 +40,33 @@ def _cos_sin(freqs: torch.Tensor):
 
 
 class WanAttnProcessor2_0:
-    """Dense attention (wan.py:40-160): self, text cross (Sq != Skv) and the optional I2V image branch."""
+    """Dense attention (wan.py:40-160): self, text cross (Sq != Skv) and the optional I2V image branch.
 
-    def __init__(self):
+    `differentiable=True` (off by default): a call in grad mode builds an autograd graph from the output back to
+    hidden_states, encoder_hidden_states and the module parameters (`qk_norm_rope_autograd`, `dense_attention_autograd`);
+    under torch.no_grad() such a processor takes the inference path and gives its bits."""
+
+    _HAS_BACKWARD = True  # the concrete class can sit in a training graph (the Eval class cannot: hard top-1)
+
+    def __init__(self, differentiable: bool = False):
         ops._C.lib()  # no fallback: fail now if the HIP library is missing
+        if differentiable and not type(self)._HAS_BACKWARD:
+            raise ValueError(f"{type(self).__name__} routes every head to its top-1 expert, which has no gradient: "
+                             "differentiable=True belongs to the dense and the soft-mixture (Train) processors")
+        self.differentiable = bool(differentiable)
 
-    def _input_proj(self, attn, hidden_states, encoder_hidden_states=None, rotary_emb=None):
-        """wan.py:64-101: q/k/v projections, RMSNorm across heads (before the head split), RoPE."""
+    def _grad_path(self) -> bool:
+        """build an autograd graph in this call?  (never under sequence parallelism: the exchange has no autograd)"""
+        if not (self.differentiable and torch.is_grad_enabled()):
+            return False
+        if SP_STATE.enabled:
+            raise NotImplementedError("differentiable=True is not sequence-parallel in this build: the Ulysses exchange "
+                                      "has no autograd")
+        return True
+
+    def _input_proj(self, attn, hidden_states, encoder_hidden_states=None, rotary_emb=None, grad: bool = False):
+        """wan.py:64-101: q/k/v projections, RMSNorm across heads (before the head split), RoPE.
+        grad=True: the norm + RoPE pass is the out-of-place, differentiable one."""
         enc_img = None
         if attn.add_k_proj is not None:
             enc_img = encoder_hidden_states[:, :257]
@@ -66,8 +87,12 @@ class WanAttnProcessor2_0:
             # RMSNorm over all H*D channels of a token + rotation, one in-place HIP pass per tensor
             cos, sin = _cos_sin(rope) if rope is not None else (None, None)
             q, k, v = (x.unflatten(2, (H, -1)).transpose(1, 2) for x in (q, k, v))
-            torch.ops.vorta.qk_norm_rope(q[0], attn.norm_q.weight, float(attn.norm_q.eps), cos, sin, -1, True)
-            torch.ops.vorta.qk_norm_rope(k[0], attn.norm_k.weight, float(attn.norm_k.eps), cos, sin, -1, True)
+            if grad:
+                q = qk_norm_rope_autograd(q, attn.norm_q.weight, float(attn.norm_q.eps), cos, sin, None, True)
+                k = qk_norm_rope_autograd(k, attn.norm_k.weight, float(attn.norm_k.eps), cos, sin, None, True)
+            else:
+                torch.ops.vorta.qk_norm_rope(q[0], attn.norm_q.weight, float(attn.norm_q.eps), cos, sin, -1, True)
+                torch.ops.vorta.qk_norm_rope(k[0], attn.norm_k.weight, float(attn.norm_k.eps), cos, sin, -1, True)
         else:
             if attn.norm_q is not None:
                 q = attn.norm_q(q)
@@ -99,14 +124,33 @@ class WanAttnProcessor2_0:
         return buf, buf_img
 
     @staticmethod
+    def _attn_grad(attn, q, k, v, enc_img):
+        """`_attn` behind autograd (dense_attention_autograd folds a batch into the head axis)"""
+        buf_img = None
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if enc_img is not None:
+            k_img = attn.norm_added_k(attn.add_k_proj(enc_img)).unflatten(2, (attn.heads, -1)).transpose(1, 2)
+            v_img = attn.add_v_proj(enc_img).unflatten(2, (attn.heads, -1)).transpose(1, 2)
+            buf_img = dense_attention_autograd(q, k_img.contiguous(), v_img.contiguous()).transpose(1, 2)
+        return dense_attention_autograd(q, k, v).transpose(1, 2), buf_img
+
+    @staticmethod
     def _output_proj(attn, buf, buf_img=None):
         hidden = buf.flatten(2, 3)
         if buf_img is not None:
             hidden = hidden + buf_img.flatten(2, 3)
         return attn.to_out[1](attn.to_out[0](hidden))
 
-    @torch.no_grad()  # forward only: the HIP ops have no backward (training is out of scope)
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, rotary_emb=None):
+        if not self._grad_path():  # the default: no autograd graph, whatever the inputs ask for
+            return self._call_no_grad(attn, hidden_states, encoder_hidden_states, attention_mask, rotary_emb)
+        if attention_mask is not None:
+            raise NotImplementedError("attention_mask is always None on this path (wan.py:141)")
+        q, k, v, enc_img = self._input_proj(attn, hidden_states, encoder_hidden_states, rotary_emb, grad=True)
+        return self._output_proj(attn, *self._attn_grad(attn, q, k, v, enc_img))
+
+    @torch.no_grad()  # forward only
+    def _call_no_grad(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, rotary_emb=None):
         if attention_mask is not None:
             raise NotImplementedError("attention_mask is always None on this path (wan.py:141)")
         is_cross = encoder_hidden_states is not None
@@ -120,8 +164,10 @@ class WanAttnProcessor2_0:
 class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
     """Inference-time routed self attention (wan.py:303-437)."""
 
-    def __init__(self, check_input: bool = False):
-        super().__init__()
+    _HAS_BACKWARD = False
+
+    def __init__(self, check_input: bool = False, differentiable: bool = False):
+        super().__init__(differentiable)
         self.check_input = check_input
 
     def _check_input(self, hidden_states, lowres_group_info, latent_shape, window_size, tile_size):
@@ -178,7 +224,11 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
 
 class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
     """Soft-mixture training forward (wan.py:163-300), FORWARD only (no backward kernels); the
-    dense teacher (`use_original_attn=True`) and cross attention are the dense processor."""
+    dense teacher (`use_original_attn=True`) and cross attention are the dense processor.
+    With `differentiable=True` a call in grad mode is the TRAINING forward instead: the same launches behind
+    `soft_mixture_attention_autograd`, with gradients for hidden_states, routing_score and the module parameters."""
+
+    _HAS_BACKWARD = True
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, rotary_emb=None,
                  use_original_attn: bool = False, routing_score: Optional[torch.Tensor] = None,
@@ -189,6 +239,15 @@ class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
+        if self._grad_path():
+            self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
+            q, k, v, _ = self._input_proj(attn, hidden_states, None, rotary_emb, grad=True)
+            assert q.shape[0] == 1, "the soft mixture runs one batch item per call"
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            out = soft_mixture_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), routing_score, geom,
+                                                  model="wan")
+            return self._output_proj(attn, out.transpose(1, 2))
         if torch.is_grad_enabled() and (hidden_states.requires_grad or routing_score.requires_grad):
             raise NotImplementedError("the soft-mixture forward of this build has no backward: call it under "
                                       "torch.no_grad() (router training is outside the inference hot path)")

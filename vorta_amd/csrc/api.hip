@@ -42,6 +42,7 @@ extern "C" int vorta_sizeof(int which) {
     case 13: return (int)sizeof(vorta_attn_bwd_args);
     case 14: return (int)sizeof(vorta_mix_bwd_args);
     case 15: return (int)sizeof(vorta_cast_args);
+    case 16: return (int)sizeof(vorta_norm_rope_bwd_args);
     default: return -1;
   }
 }

@@ -818,6 +818,63 @@ def qk_norm_rope(x: torch.Tensor, weight: Optional[torch.Tensor], eps: float, *,
     return x
 
 
+def qk_norm_rope_bwd(x_in: torch.Tensor, g: torch.Tensor, weight: Optional[torch.Tensor], eps: float, *,
+                     cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
+                     n_tokens: Optional[int] = None, token_offset: int = 0, rope_tokens: Optional[int] = None,
+                     across_heads: bool = False, want_dweight: bool = True,
+                     dx: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """vorta_qk_norm_rope_bwd: the gradient of the qk_norm_rope call with the same keywords.  `x_in` is that call's INPUT (the
+    forward ran in place: the caller kept a copy), `g` the gradient of its output; both (H,S,D) views of one 16-bit dtype.
+    Returns (dx, dweight): dx in the dtype of g (`dx=` names the buffer, which may be g itself; by default a new one, zero
+    outside the token range), dweight float32 [D] / [H*D] of THIS call's rows, or None without a weight or with
+    want_dweight=False.  Deterministic (no float atomics)."""
+    _require_gpu(x_in, g, weight, cos, sin, dx)
+    if x_in.dtype not in _DT or g.dtype != x_in.dtype or g.shape != x_in.shape:
+        raise ValueError("qk_norm_rope_bwd: x_in and g must be bf16 or fp16 views of one shape")
+    H, S, D = x_in.shape
+    n_tokens = S - token_offset if n_tokens is None else n_tokens
+    if token_offset < 0 or n_tokens < 0 or token_offset + n_tokens > S:
+        raise ValueError(f"qk_norm_rope_bwd: tokens [{token_offset}, {token_offset + n_tokens}) outside the {S} rows of x_in")
+    if dx is None:
+        dx = torch.empty_like(g) if n_tokens == S else torch.zeros_like(g)
+    elif dx.dtype != g.dtype or dx.shape != g.shape:
+        raise ValueError("qk_norm_rope_bwd: dx must have the shape and dtype of g")
+    a = _C.NormRopeBwdArgs()
+    a.struct_size = C.sizeof(_C.NormRopeBwdArgs)
+    f = a.fwd
+    f.struct_size = C.sizeof(_C.NormRopeArgs)
+    f.dtype, f.head_dim, f.heads = _DT[x_in.dtype], D, H
+    f.x = _tensor(x_in)
+    if weight is not None:
+        if weight.dtype != x_in.dtype or not weight.is_contiguous():
+            weight = weight.to(x_in.dtype).contiguous()
+        if weight.numel() != (H * D if across_heads else D):
+            raise ValueError("qk_norm_rope_bwd: weight must be [D], or [H*D] across heads")
+        f.weight = weight.data_ptr()
+    if cos is not None:
+        if cos.dtype != torch.float32 or not cos.is_contiguous():
+            cos = cos.float().contiguous()
+        if sin.dtype != torch.float32 or not sin.is_contiguous():
+            sin = sin.float().contiguous()
+        f.cos, f.sin = cos.data_ptr(), sin.data_ptr()
+        rope_tokens = min(cos.shape[0], n_tokens) if rope_tokens is None else rope_tokens
+        if cos.shape[0] < rope_tokens or cos.shape[-1] != D:
+            raise ValueError("cos/sin must be (>= rope_tokens, D)")
+    f.n_tokens, f.token_offset, f.rope_tokens = n_tokens, token_offset, rope_tokens or 0
+    f.eps = eps
+    f.across_heads = 1 if across_heads else 0
+    a.g, a.dx = _tensor(g), _tensor(dx)
+    dweight = None
+    if want_dweight and weight is not None:
+        channels = H * D if across_heads else D
+        dweight = torch.empty(channels, dtype=torch.float32, device=g.device)
+        parts = max(1, min((n_tokens + 3) // 4, _C.NORM_ROPE_BWD_PARTS))
+        ws = torch.empty(parts * channels, dtype=torch.float32, device=g.device)
+        a.dweight, a.ws, a.ws_floats = dweight.data_ptr(), ws.data_ptr(), ws.numel()
+    _C.check(_C.lib().vorta_qk_norm_rope_bwd(C.byref(a), _stream()), "vorta_qk_norm_rope_bwd")
+    return dx, dweight
+
+
 def mix_experts(xs, scores: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """vorta_mix_experts: out[h] = sum_e scores[0,h,e] * xs[e][h] for (H,N,D) views (hunyuan.py:509-513)."""
     _require_gpu(scores, out, *xs)

@@ -2,7 +2,8 @@
 
 Same module layout as the reference (`linear.weight (3H,E)`, `linear.bias (3H)`), so the published `router.pt`
 files load by key (`...blocks.{i}.router.linear.{weight,bias}`, vorta/train/checkpoint.py:63-73).  The forward
-runs in libvorta_hip.so (vorta_router_route) -- inference only, no autograd.
+runs in libvorta_hip.so (vorta_router_route) -- inference only, no autograd; `forward_autograd` is the same function
+through torch ops, for training the router.
 """
 import torch
 from torch import nn
@@ -28,6 +29,16 @@ class Router(nn.Module):
             w, b = w.to(torch.bfloat16), b.to(torch.bfloat16)
         scores, _, _, _ = ops.router_route(temb.to(w.dtype), w, b, self.heads, 0.0, self.num_experts)
         return scores
+
+    def forward_autograd(self, temb: torch.Tensor) -> torch.Tensor:
+        """`forward` as a differentiable function: softmax(linear(silu(temb)).view(B, H, E)) through torch ops in the module's
+        16-bit dtype, the roundings vorta_router_route makes (silu, logits and scores each rounded once).  The tensor is
+        (B, 3H): no kernel is warranted.  Under grad it gives linear.weight / linear.bias their gradients."""
+        w, b = self.linear.weight, self.linear.bias
+        if w.dtype not in (torch.bfloat16, torch.float16):
+            w, b = w.to(torch.bfloat16), b.to(torch.bfloat16)
+        logits = nn.functional.linear(self.silu(temb.to(w.dtype)), w, b)
+        return self.softmax(logits.view(temb.shape[0], self.heads, self.num_experts))
 
 
 def load_router_checkpoint(ckpt_file, transformer: nn.Module):

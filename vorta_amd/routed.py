@@ -592,6 +592,60 @@ def dense_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     return _Dense.apply(q, k, v, kv_valid, q_valid, scale)
 
 
+def _norm_rope_forward(x: torch.Tensor, weight, eps: float, cos, sin, rope_tokens, across_heads: bool) -> torch.Tensor:
+    """out of place: a fresh contiguous (.., H, N, D) copy of x, normalised and rotated by the in-place kernel"""
+    if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+        raise ValueError("qk_norm_rope_autograd takes a (H,N,D) or (1,H,N,D) view")
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device).copy_(x)
+    ops.qk_norm_rope(y[0] if y.dim() == 4 else y, weight, eps, cos=cos, sin=sin, rope_tokens=rope_tokens,
+                     across_heads=across_heads)
+    return y
+
+
+def _norm_rope_backward(x: torch.Tensor, g: torch.Tensor, weight, eps: float, cos, sin, rope_tokens, across_heads: bool,
+                        want_dweight: bool):
+    """(dx, dweight float32 | None) of `_norm_rope_forward`; dx in x's own layout (a transposed projection view stays one)"""
+    fold = lambda t: t[0] if t.dim() == 4 else t  # noqa: E731
+    if g.stride(-1) != 1 or any(st % 8 for st in g.stride()[:-1]) or g.data_ptr() % 16:
+        g = g.contiguous()
+    dx = torch.empty_like(x)
+    _, dw = ops.qk_norm_rope_bwd(fold(x), fold(g), weight, eps, cos=cos, sin=sin, rope_tokens=rope_tokens,
+                                 across_heads=across_heads, want_dweight=want_dweight, dx=fold(dx))
+    return dx, dw
+
+
+class _QkNormRope(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, eps, cos, sin, rope_tokens, across_heads):
+        y = _norm_rope_forward(x, weight, eps, cos, sin, rope_tokens, across_heads)
+        ctx.save_for_backward(x, weight, cos, sin)
+        ctx.rest = (eps, rope_tokens, across_heads)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, cos, sin = ctx.saved_tensors
+        eps, rope_tokens, across_heads = ctx.rest
+        dx, dw = _norm_rope_backward(x, g, weight, eps, cos, sin, rope_tokens, across_heads,
+                                     weight is not None and ctx.needs_input_grad[1])
+        if dw is not None:
+            dw = dw.to(weight.dtype).view(weight.shape)
+        return dx, dw, None, None, None, None, None
+
+
+def qk_norm_rope_autograd(x: torch.Tensor, weight: Optional[torch.Tensor], eps: float, cos: Optional[torch.Tensor] = None,
+                          sin: Optional[torch.Tensor] = None, rope_tokens: Optional[int] = None,
+                          across_heads: bool = False) -> torch.Tensor:
+    """`ops.qk_norm_rope` (RMSNorm + rotary embedding of q or k, hunyuan.py:62-104 / wan.py:85-100) as a differentiable,
+    OUT-OF-PLACE operator.  The in-place kernel would overwrite the output of a `Linear` behind autograd's back, so the
+    forward copies x into a fresh contiguous (H,N,D) buffer, runs the kernel on the copy (the same bits as the in-place op
+    on a copy) and keeps x, the weight and the tables; the backward is one `ops.qk_norm_rope_bwd` pass.  That extra copy
+    of q and of k is the price of training.  x: a (H,N,D) or (1,H,N,D) view with contiguous rows, e.g. the transposed view
+    of a (1,N,H*D) projection; gradients for x (in x's layout) and weight only -- cos / sin are constants.
+    rope_tokens None: every token the tables cover."""
+    return _QkNormRope.apply(x, weight, eps, cos, sin, rope_tokens, across_heads)
+
+
 def dense_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, kv_valid: Optional[int] = None,
                     q_valid: Optional[int] = None, out: Optional[torch.Tensor] = None,
                     scale: Optional[float] = None) -> torch.Tensor:

@@ -23,6 +23,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::route_plan_(temb, weight, bias, heads, tau, n_experts, scores, expert, lists, counts) -> () mutates the four
     vorta::soft_mixture_attention_grad(q,k,v, scores, latent, ...) -> out   functional, differentiable (register_autograd);
     vorta::soft_mixture_attention_bwd(q,k,v, scores, d_out, latent, ...) -> (dq, dk, dv, dscores)   its autograd formula
+    vorta::qk_norm_rope_grad(x, weight, eps, cos, sin, rope_tokens, across_heads) -> y   out of place, differentiable;
+    vorta::qk_norm_rope_bwd(x, g, weight, eps, cos, sin, ...) -> (dx, dweight)   its autograd formula (vorta_qk_norm_rope_bwd)
 """
 from typing import List, Optional, Tuple
 
@@ -234,6 +236,55 @@ def _soft_mixture_backward(ctx, d_out):
 
 torch.library.register_autograd("vorta::soft_mixture_attention_grad", _soft_mixture_backward,
                                 setup_context=_soft_mixture_setup)
+
+
+@torch.library.custom_op("vorta::qk_norm_rope_grad", mutates_args=(), device_types="cuda")
+def qk_norm_rope_grad(x: torch.Tensor, weight: Optional[torch.Tensor], eps: float, cos: Optional[torch.Tensor] = None,
+                      sin: Optional[torch.Tensor] = None, rope_tokens: int = -1, across_heads: bool = False) -> torch.Tensor:
+    """The differentiable, out-of-place norm + RoPE (routed.qk_norm_rope_autograd; the mutating vorta::qk_norm_rope has no
+    gradient).  rope_tokens < 0: every token the tables cover.  Its autograd formula is vorta::qk_norm_rope_bwd."""
+    from . import routed
+    return routed._norm_rope_forward(x, weight, eps, cos, sin, None if rope_tokens < 0 else rope_tokens, across_heads)
+
+
+@qk_norm_rope_grad.register_fake
+def _(x, weight, eps, cos=None, sin=None, rope_tokens=-1, across_heads=False):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op("vorta::qk_norm_rope_bwd", mutates_args=(), device_types="cuda")
+def qk_norm_rope_bwd(x: torch.Tensor, g: torch.Tensor, weight: Optional[torch.Tensor], eps: float,
+                     cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None, rope_tokens: int = -1,
+                     across_heads: bool = False, want_dweight: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dx, dweight) of vorta::qk_norm_rope_grad: vorta_qk_norm_rope_bwd.  dweight is float32 [D] / [H*D]; an empty tensor
+    without a weight or with want_dweight=False (an operator returns tensors, not None)."""
+    from . import routed
+    dx, dw = routed._norm_rope_backward(x, g, weight, eps, cos, sin, None if rope_tokens < 0 else rope_tokens, across_heads,
+                                        want_dweight and weight is not None)
+    return dx, dw if dw is not None else x.new_empty((0,), dtype=torch.float32)
+
+
+@qk_norm_rope_bwd.register_fake
+def _(x, g, weight, eps, cos=None, sin=None, rope_tokens=-1, across_heads=False, want_dweight=True):
+    n = weight.numel() if (want_dweight and weight is not None) else 0
+    return torch.empty_like(x), x.new_empty((n,), dtype=torch.float32)
+
+
+def _norm_rope_setup(ctx, inputs, output):
+    x, weight, eps, cos, sin, rope_tokens, across_heads = inputs
+    ctx.save_for_backward(x, weight, cos, sin)
+    ctx.rest = (eps, rope_tokens, across_heads)
+
+
+def _norm_rope_backward(ctx, g):
+    x, weight, cos, sin = ctx.saved_tensors
+    eps, rope_tokens, across_heads = ctx.rest
+    want = weight is not None and ctx.needs_input_grad[1]
+    dx, dw = torch.ops.vorta.qk_norm_rope_bwd(x, g, weight, eps, cos, sin, rope_tokens, across_heads, want)
+    return dx, (dw.to(weight.dtype).view(weight.shape) if want else None), None, None, None, None, None
+
+
+torch.library.register_autograd("vorta::qk_norm_rope_grad", _norm_rope_backward, setup_context=_norm_rope_setup)
 
 
 @torch.library.custom_op("vorta::route_plan_", mutates_args=("scores", "expert", "lists", "counts"), device_types="cuda")
