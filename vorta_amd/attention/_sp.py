@@ -57,8 +57,8 @@ SP_PLACEMENT = __import__("os").environ.get("VORTA_SP_PLACEMENT", "auto")
 SP_KV_SPLITS = __import__("os").environ.get("VORTA_SP_KV_SPLITS", "1")
 
 
-def _layout(H, S, T, D, device, dtype, counts=None, extra_slots=0):
-    """(layout of this layer's head placement, receive buffers of this rank's head-slot count)"""
+def _layout_only(H, S, T, D, device, dtype, counts=None, extra_slots=0) -> UlyssesLayout:
+    """the layout of a head placement (cached: a few integers and a shared row map), without receive buffers"""
     rank, P = SP_STATE.group_local_rank, SP_STATE.sp_size
     counts = tuple(counts) if counts is not None else (H // P,) * P
     lkey = (H, S, T, D, P, rank, str(device), dtype, counts)
@@ -66,7 +66,13 @@ def _layout(H, S, T, D, device, dtype, counts=None, extra_slots=0):
         if len(_LAYOUTS) > 512:
             _LAYOUTS.clear()
         _LAYOUTS[lkey] = UlyssesLayout(H, S, T, D, P, rank, device, dtype, SP_STATE.group, counts=counts, extra_slots=extra_slots)
-    lay = _LAYOUTS[lkey]
+    return _LAYOUTS[lkey]
+
+
+def _layout(H, S, T, D, device, dtype, counts=None, extra_slots=0):
+    """(layout of this layer's head placement, receive buffers of this rank's head-slot count)"""
+    rank, P = SP_STATE.group_local_rank, SP_STATE.sp_size
+    lay = _layout_only(H, S, T, D, device, dtype, counts, extra_slots)
     # one buffer set per distinct slot count (at most 2 H / P of them); layouts -- one per distinct tuple of head counts, cheap:
     # a few integers and a shared row map -- are evicted on their own, so trimming them never drops gigabytes mid-run
     bkey = (H, S, T, D, P, rank, str(device), dtype, lay.Hl)
@@ -208,3 +214,118 @@ def sp_wan_dense(proc, attn, q, k, v, enc_img, is_cross_attn: bool):
     if is_cross_attn:
         return proc._attn(attn, q, k, v, enc_img, True)
     return sp_attention(q, k, v, 0, None, None, model="wan"), None
+
+
+# ---- the soft mixture (router training) under sequence parallelism -------------------------------------------------------
+# After the exchange a rank holds whole heads and the mixture is independent per head: the single-GPU launches
+# (routed.soft_mixture_attention) run on the local heads through the receive layout.  Every head costs the same (all three
+# experts), so the heads are placed in their natural order: H / P per rank, or -- where P does not divide H -- one more on the
+# first H % P ranks (UlyssesLayout(counts=...)).  VORTA_SP_PLACEMENT, VORTA_SP_GROUPS, VORTA_SP_KV_SPLITS and the precision
+# switch do not apply: one slot group, one key split, the dtype of q, k, v -- what the single-GPU training forward pins.
+def _mixture_placement(H: int, P: int):
+    if H < P:
+        raise ValueError(f"{H} heads cannot cover {P} sequence-parallel ranks")
+    return list(range(H)), [H // P + (1 if j < H % P else 0) for j in range(P)]
+
+
+def _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape):
+    B, H, N, D = q.shape
+    if B != 1:
+        raise AssertionError(f"Batch size {B} is not supported by the sequence-parallel soft mixture.")
+    if model != "hunyuan" and T:
+        raise ValueError("only the hunyuan model carries text rows in its self attention")
+    P, Sl = SP_STATE.sp_size, N - T
+    order, counts = _mixture_placement(H, P)
+    lay = _layout_only(H, Sl * P, T, D, q.device, q.dtype, counts)
+    geom = geometry_for(latent_shape, tile_size, window_size, lowres_group_info.window_size, lowres_group_info.reduction_rate,
+                        q.device, row_map=lay.row_map)
+    me = SP_STATE.group_local_rank
+    return lay, order, geom, (lay.starts[me], lay.starts[me + 1])
+
+
+def _flat(lay: UlyssesLayout, buf: torch.Tensor) -> torch.Tensor:
+    """a receive buffer as ((P + 1) Hl, Sl, D): segment p holds rows of local head p % Hl only (P video chunks, then the text
+    segment), so an elementwise per-head kernel sees every row exactly once -- the head views overlap"""
+    return buf.view((lay.P + 1) * lay.Hl, lay.Sl, lay.D)
+
+
+def _recv_mixture_forward(lay, geom, qb, kb, vb, scores, ebufs, ob, model, T, te, scale, record=None):
+    """the three experts over the local heads in the receive layout, then the mix: scores (1, Hl, 3)"""
+    hv = lay.head_view
+    routed_attention(hv(qb), hv(kb), hv(vb), HeadRouting.every_head_everywhere(lay.Hl, qb.device), geom, model=model,
+                     text_len=T, text_valid=te, scale=scale, expert_outs=[hv(b) for b in ebufs], fp8=False, kv_splits=1,
+                     record=record)
+    ops.mix_experts([_flat(lay, b) for b in ebufs], scores[:1].repeat(1, lay.P + 1, 1), _flat(lay, ob))
+
+
+class _RecvSoftMixture(torch.autograd.Function):
+    """routed.`_SoftMixture` on receive buffers: q, k, v in, the mixed output out, all (rows_total, D) of one layout"""
+
+    @staticmethod
+    def forward(ctx, qb, kb, vb, scores, lay, geom, model, T, te, scale):
+        from ..ulysses.autograd import new_recv_buffer
+        ebufs = [new_recv_buffer(lay) for _ in range(3)]
+        ob = new_recv_buffer(lay)
+        launches: list = []
+        _recv_mixture_forward(lay, geom, qb, kb, vb, scores, ebufs, ob, model, T, te, scale, record=launches)
+        ctx.save_for_backward(qb, kb, vb, scores, *ebufs)
+        ctx.launches, ctx.lay = launches, lay
+        return ob
+
+    @staticmethod
+    def backward(ctx, d_ob):
+        from ..routed import _replay_backward
+        qb, kb, vb, scores, *ebufs = ctx.saved_tensors
+        lay = ctx.lay
+        hv = lay.head_view
+        g = d_ob.contiguous()
+        dsc = ops.mix_experts_bwd([_flat(lay, b) for b in ebufs], _flat(lay, g)).view(lay.P + 1, lay.Hl, 3).sum(0)
+        sc = scores[0].to(qb.dtype).contiguous()  # what ops.mix_experts read in the forward
+        ptrs = [b.data_ptr() for b in ebufs]
+        # float32 accumulators laid out like the receive buffers: a launch adds through the same row tables and head stride
+        acc = [torch.zeros((lay.rows_total, lay.D), dtype=torch.float32, device=qb.device) for _ in range(3)]
+        _replay_backward(ctx.launches, hv(g), hv(acc[0]), hv(acc[1]), hv(acc[2]),
+                         lambda _, o: sc[:, ptrs.index(o.data_ptr())])
+        grads = [torch.empty_like(qb) for _ in range(3)]
+        ops.cast_grads([_flat(lay, a) for a in acc], [_flat(lay, x) for x in grads])
+        d_sc = torch.zeros_like(scores)
+        d_sc[0] = dsc.to(scores.dtype)
+        return grads[0], grads[1], grads[2], d_sc, None, None, None, None, None, None
+
+
+def sp_soft_mixture_attention(q, k, v, T: int, routing_score: torch.Tensor, *, model: str, text_valid: int = 0,
+                              lowres_group_info=None, window_size=(3, 3, 3), tile_size=(6, 8, 8), latent_shape=None,
+                              scale: Optional[float] = None) -> torch.Tensor:
+    """`routed.soft_mixture_attention` under sequence parallelism, forward only (no autograd graph).
+    q,k,v: (1, H, S/P + T, D) local sequence shard with the replicated text at the end, as `sp_attention`; routing_score
+    (B, H, 3), item 0 is read.  Returns the (1, S/P + T, H, D) buffer (text rows: all heads, gathered).  The receive
+    buffers are the cached ones of the inference path."""
+    with torch.no_grad():
+        lay, order, geom, (h0, h1) = _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape)
+        _, sb = _layout(lay.H, lay.S, T, lay.D, q.device, q.dtype, lay.counts)
+        if getattr(sb, "mix_bufs", None) is None:
+            sb.mix_bufs = [lay.new_buffer() for _ in range(3)]  # the three experts' outputs, beside q, k, v, o
+        Sl = lay.Sl
+        lay.scatter_heads([x[0, :, :Sl] for x in (q, k, v)], sb.bufs[:3], order, [x[0, :, Sl:] for x in (q, k, v)] if T else None)
+        te = text_valid if model == "hunyuan" else 0
+        _recv_mixture_forward(lay, geom, *sb.bufs[:3], routing_score[:1, h0:h1], sb.mix_bufs, sb.bufs[3], model, T, te, scale)
+        buf = torch.empty((1, Sl + T, lay.H, lay.D), dtype=q.dtype, device=q.device)
+        lay.gather_heads(sb.bufs[3], buf[0, :Sl].transpose(0, 1), order, buf[0, Sl:].transpose(0, 1) if T else None)
+        return buf
+
+
+def sp_soft_mixture_attention_autograd(q, k, v, T: int, routing_score: torch.Tensor, *, model: str, text_valid: int = 0,
+                                       lowres_group_info=None, window_size=(3, 3, 3), tile_size=(6, 8, 8),
+                                       latent_shape=None, scale: Optional[float] = None) -> torch.Tensor:
+    """`sp_soft_mixture_attention` as a differentiable operator (`routed.soft_mixture_attention_autograd` on the local heads
+    between a differentiable exchange, ulysses/autograd.py).  The backward exchanges d_out to head shards, takes the score
+    gradients (ops.mix_experts_bwd), replays the recorded launches through ops.attn_bwd into float32 buffers laid out like
+    the receive buffers, rounds once (ops.cast_grads) and sends dq, dk, dv back in one exchange.  Text rows of dq, dk, dv and
+    d routing_score are non-zero for this rank's heads only: their sum over the ranks is the single-process gradient.
+    Every buffer an autograd node keeps is allocated by this call (the next layer overwrites the shared ones)."""
+    from ..ulysses.autograd import gather_heads_autograd, scatter_heads_autograd
+    lay, order, geom, (h0, h1) = _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape)
+    qb, kb, vb = scatter_heads_autograd(lay, [q[0], k[0], v[0]], order)
+    te = text_valid if model == "hunyuan" else 0
+    ob = _RecvSoftMixture.apply(qb, kb, vb, routing_score[:1, h0:h1], lay, geom, model, T, te, scale)
+    return gather_heads_autograd(lay, ob, order, token_major=True)[None]

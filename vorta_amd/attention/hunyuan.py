@@ -115,13 +115,14 @@ class HunyuanVideoFlashAttnProcessor:
                              "differentiable=True belongs to the dense and the soft-mixture (Train) processors")
         self.differentiable = bool(differentiable)
 
-    def _grad_path(self) -> bool:
-        """build an autograd graph in this call?  (never under sequence parallelism: the exchange has no autograd)"""
+    def _grad_path(self, sequence_parallel: bool = False) -> bool:
+        """build an autograd graph in this call?  `sequence_parallel`: the caller has a differentiable exchange (the soft
+        mixture, attention/_sp.py); the dense attention has none -- the teacher runs under torch.no_grad()"""
         if not (self.differentiable and torch.is_grad_enabled()):
             return False
-        if SP_STATE.enabled:
-            raise NotImplementedError("differentiable=True is not sequence-parallel in this build: the Ulysses exchange "
-                                      "has no autograd")
+        if SP_STATE.enabled and not sequence_parallel:
+            raise NotImplementedError("differentiable=True of the dense attention is not sequence-parallel in this build: "
+                                      "only the soft mixture has a differentiable exchange")
         return True
 
     # -- steps 1-4 of hunyuan.py:42-134: everything before the attention boundary ----------------------
@@ -327,13 +328,17 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
 
 
 class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTripleEval):
-    """Training-time soft mixture of the three experts (hunyuan.py:241-513), FORWARD only: every head runs all
-    three experts and the outputs are summed with the routing scores.  There are no backward
-    kernels: a call that would need gradients raises instead of silently returning a detached result.
+    """Training-time soft mixture of the three experts (hunyuan.py:241-513): every head runs all three experts and the
+    outputs are summed with the routing scores.  By default (`differentiable=False`) it is a forward:
+    a call that would need gradients raises instead of silently returning a detached result.
     `use_original_attn=True` (the dense teacher, hunyuan.py:312-321) is the dense processor.
     With `differentiable=True` a call in grad mode is the TRAINING forward instead: the same launches behind
     `soft_mixture_attention_autograd`, with gradients for hidden_states, encoder_hidden_states, routing_score and the
-    module parameters."""
+    module parameters.
+    Both forms run under sequence parallelism (attention/_sp.py `sp_soft_mixture_attention[_autograd]`): the heads are
+    resharded once, a rank mixes its own heads, and in grad mode the exchange is differentiable.  A rank then holds the
+    gradient of the replicated text rows (and of routing_score) for its own heads only: the training loop sums them over
+    the sequence-parallel group, like the parameter gradients.  The dense teacher stays a torch.no_grad() call there."""
 
     _HAS_BACKWARD = True
 
@@ -346,11 +351,17 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
         if use_original_attn:
             return HunyuanVideoFlashAttnProcessor.__call__(self, attn, hidden_states, encoder_hidden_states,
                                                            attention_mask, image_rotary_emb)
-        if self._grad_path():
+        if self._grad_path(sequence_parallel=True):
             self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
             q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb, grad=True)
             assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
             te = self._text_valid(attention_mask, T, flex_attn_mask_func)
+            if SP_STATE.enabled:  # norm + RoPE ran on the local shard (rotary rows shrunk in `_project`); whole heads after the exchange
+                from ._sp import sp_soft_mixture_attention_autograd
+                buf = sp_soft_mixture_attention_autograd(q, k, v, T, routing_score, model="hunyuan", text_valid=te,
+                                                         lowres_group_info=lowres_group_info, window_size=window_size,
+                                                         tile_size=tile_size, latent_shape=latent_shape)
+                return self._output(attn, buf, T)
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             out = soft_mixture_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), routing_score, geom,
@@ -359,13 +370,17 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
         if torch.is_grad_enabled() and (hidden_states.requires_grad or routing_score.requires_grad):
             raise NotImplementedError("the soft-mixture forward of this build has no backward: call it under "
                                       "torch.no_grad() (router training is outside the inference hot path)")
-        if SP_STATE.enabled:
-            raise NotImplementedError("the soft-mixture forward is not sequence-parallel in this build")
         with torch.no_grad():
             self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
             q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb)
             assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
             te = self._text_valid(attention_mask, T, flex_attn_mask_func)
+            if SP_STATE.enabled:
+                from ._sp import sp_soft_mixture_attention
+                buf = sp_soft_mixture_attention(q, k, v, T, routing_score, model="hunyuan", text_valid=te,
+                                                lowres_group_info=lowres_group_info, window_size=window_size,
+                                                tile_size=tile_size, latent_shape=latent_shape)
+                return self._output(attn, buf, T)
             buf, out = self._new_out(q)
             torch.ops.vorta.soft_mixture_attention(q, k, v, routing_score, out,
                                                    **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size,

@@ -55,13 +55,14 @@ class WanAttnProcessor2_0:
                              "differentiable=True belongs to the dense and the soft-mixture (Train) processors")
         self.differentiable = bool(differentiable)
 
-    def _grad_path(self) -> bool:
-        """build an autograd graph in this call?  (never under sequence parallelism: the exchange has no autograd)"""
+    def _grad_path(self, sequence_parallel: bool = False) -> bool:
+        """build an autograd graph in this call?  `sequence_parallel`: the caller has a differentiable exchange (the soft
+        mixture, attention/_sp.py); the dense attention has none -- the teacher runs under torch.no_grad()"""
         if not (self.differentiable and torch.is_grad_enabled()):
             return False
-        if SP_STATE.enabled:
-            raise NotImplementedError("differentiable=True is not sequence-parallel in this build: the Ulysses exchange "
-                                      "has no autograd")
+        if SP_STATE.enabled and not sequence_parallel:
+            raise NotImplementedError("differentiable=True of the dense attention is not sequence-parallel in this build: "
+                                      "only the soft mixture has a differentiable exchange")
         return True
 
     def _input_proj(self, attn, hidden_states, encoder_hidden_states=None, rotary_emb=None, grad: bool = False):
@@ -223,10 +224,13 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
 
 
 class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
-    """Soft-mixture training forward (wan.py:163-300), FORWARD only (no backward kernels); the
-    dense teacher (`use_original_attn=True`) and cross attention are the dense processor.
-    With `differentiable=True` a call in grad mode is the TRAINING forward instead: the same launches behind
-    `soft_mixture_attention_autograd`, with gradients for hidden_states, routing_score and the module parameters."""
+    """Soft-mixture training forward (wan.py:163-300); the dense teacher (`use_original_attn=True`)
+    and cross attention are the dense processor.  By default (`differentiable=False`) a call that would need gradients
+    raises.  With `differentiable=True` a call in grad mode is the TRAINING forward instead: the same launches behind
+    `soft_mixture_attention_autograd`, with gradients for hidden_states, routing_score and the module parameters.
+    Both forms run under sequence parallelism (attention/_sp.py `sp_soft_mixture_attention[_autograd]`); in grad mode a
+    rank holds d routing_score for its own heads only (summed over the group by the training loop, like the parameter
+    gradients).  The dense teacher stays a torch.no_grad() call there."""
 
     _HAS_BACKWARD = True
 
@@ -239,10 +243,16 @@ class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
-        if self._grad_path():
+        if self._grad_path(sequence_parallel=True):
             self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
             q, k, v, _ = self._input_proj(attn, hidden_states, None, rotary_emb, grad=True)
             assert q.shape[0] == 1, "the soft mixture runs one batch item per call"
+            if SP_STATE.enabled:  # norm + RoPE ran on the local shard (rotary rows shrunk in `_input_proj`)
+                from ._sp import sp_soft_mixture_attention_autograd
+                buf = sp_soft_mixture_attention_autograd(q, k, v, 0, routing_score, model="wan",
+                                                         lowres_group_info=lowres_group_info, window_size=window_size,
+                                                         tile_size=tile_size, latent_shape=latent_shape)
+                return self._output_proj(attn, buf)
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             out = soft_mixture_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), routing_score, geom,
@@ -251,12 +261,15 @@ class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
         if torch.is_grad_enabled() and (hidden_states.requires_grad or routing_score.requires_grad):
             raise NotImplementedError("the soft-mixture forward of this build has no backward: call it under "
                                       "torch.no_grad() (router training is outside the inference hot path)")
-        if SP_STATE.enabled:
-            raise NotImplementedError("the soft-mixture forward is not sequence-parallel in this build")
         with torch.no_grad():
             self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
             q, k, v, _ = self._input_proj(attn, hidden_states, None, rotary_emb)
             assert q.shape[0] == 1, "the soft mixture runs one batch item per call"
+            if SP_STATE.enabled:
+                from ._sp import sp_soft_mixture_attention
+                buf = sp_soft_mixture_attention(q, k, v, 0, routing_score, model="wan", lowres_group_info=lowres_group_info,
+                                                window_size=window_size, tile_size=tile_size, latent_shape=latent_shape)
+                return self._output_proj(attn, buf)
             buf, out = self._new_out(q)
             torch.ops.vorta.soft_mixture_attention(q, k, v, routing_score, out,
                                                    **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size,

@@ -678,3 +678,16 @@ def geometry_for(latent, tile, window, group, rate, device, row_map: Optional[to
             _GEOMETRY_CACHE.pop(next(iter(_GEOMETRY_CACHE)))
     _GEOMETRY_CACHE[key] = g  # most recently used last
     return g
+
+
+def sp_soft_mixture_attention(q, k, v, T, routing_score, **kw) -> torch.Tensor:
+    """`soft_mixture_attention` under sequence parallelism, forward only: attention/_sp.py (imported on use: it builds on
+    this module)"""
+    from .attention._sp import sp_soft_mixture_attention as fn
+    return fn(q, k, v, T, routing_score, **kw)
+
+
+def sp_soft_mixture_attention_autograd(q, k, v, T, routing_score, **kw) -> torch.Tensor:
+    """`soft_mixture_attention_autograd` under sequence parallelism (differentiable exchange): attention/_sp.py"""
+    from .attention._sp import sp_soft_mixture_attention_autograd as fn
+    return fn(q, k, v, T, routing_score, **kw)

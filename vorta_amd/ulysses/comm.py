@@ -1,4 +1,4 @@
-"""Ulysses collectives with the reference's call surface (vorta/ulysses/utils.py), forward only.
+"""Ulysses collectives with the reference's call surface (vorta/ulysses/utils.py).
 
 `torch.distributed` is the transport: backend "nccl" is RCCL over xGMI on the GPU box, "gloo" on CPU for the
 world_size>1 tests.  Differences from the reference, by design:
@@ -7,7 +7,8 @@ world_size>1 tests.  Differences from the reference, by design:
     seq->head direction sends the input buffer as is, the head->seq direction receives in place);
   * the attention processors do not use these at all when SP is on: they use the zero-copy path of
     engine.py.  These functions exist so code written against the reference keeps working.
-Backward passes (SeqAllToAll4D.backward, AllGather.backward) are training-only and out of scope.
+`all_to_all_4D` and `all_gather` carry the reference's autograd (SeqAllToAll4D.backward: the opposite all-to-all,
+utils.py:111-120; AllGather.backward: this rank's slice, utils.py:148-158); their forward bytes are what they were.
 """
 import torch
 import torch.distributed as dist
@@ -51,17 +52,43 @@ def _all_to_all_4D(x: torch.Tensor, scatter_idx: int = 2, gather_idx: int = 1, g
     raise RuntimeError("scatter_idx must be 1 or 2 and gather_idx must be 1 or 2")
 
 
+class _SeqAllToAll4D(torch.autograd.Function):
+    """vorta/ulysses/utils.py:96-120: the gradient of an all-to-all is the all-to-all with the two axes exchanged"""
+
+    @staticmethod
+    def forward(ctx, group, input_, scatter_idx, gather_idx):
+        ctx.group, ctx.scatter_idx, ctx.gather_idx = group, scatter_idx, gather_idx
+        return _all_to_all_4D(input_, scatter_idx, gather_idx, group=group)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return None, _SeqAllToAll4D.apply(ctx.group, grad, ctx.gather_idx, ctx.scatter_idx), None, None
+
+
 def all_to_all_4D(input_: torch.Tensor, scatter_idx: int, gather_idx: int) -> torch.Tensor:
-    return _all_to_all_4D(input_, scatter_idx, gather_idx, group=SP_STATE.group)
+    return _SeqAllToAll4D.apply(SP_STATE.group, input_, scatter_idx, gather_idx)
+
+
+class _AllGather(torch.autograd.Function):
+    """vorta/ulysses/utils.py:127-158: every rank holds the same gathered tensor, so the gradient is this rank's slice"""
+
+    @staticmethod
+    def forward(ctx, input_, dim):
+        ctx.dim, ctx.size = dim, input_.size(dim)
+        parts = [torch.empty_like(input_) for _ in range(SP_STATE.sp_size)]
+        dist.all_gather(parts, input_.contiguous(), group=SP_STATE.group)
+        return torch.cat(parts, dim=dim)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return grad.narrow(ctx.dim, ctx.size * SP_STATE.group_local_rank, ctx.size), None
 
 
 def all_gather(input_: torch.Tensor, dim: int = 0) -> torch.Tensor:
     """rank-ordered concatenation along `dim` (vorta/ulysses/utils.py:127-162)."""
     if not SP_STATE.enabled:
         return input_
-    parts = [torch.empty_like(input_) for _ in range(SP_STATE.sp_size)]
-    dist.all_gather(parts, input_.contiguous(), group=SP_STATE.group)
-    return torch.cat(parts, dim=dim)
+    return _AllGather.apply(input_, dim)
 
 
 def shrink_dim(tensor: torch.Tensor, dim: int) -> torch.Tensor:

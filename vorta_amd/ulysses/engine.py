@@ -879,6 +879,33 @@ class UlyssesLayout:
         self._finish(self.gather_heads_start(buf, state))
         self.gather_heads_end(buf, state, out_text)
 
+    def gather_heads_multi(self, bufs: Sequence[torch.Tensor], out_shards: Sequence[torch.Tensor], head_order: Sequence[int]):
+        """`gather_heads` of up to four tensors of one layout TOGETHER (dq, dk, dv of a backward pass, ulysses/autograd.py):
+        one all_to_all_single per tensor, all started before any is waited for, then ONE un-permute pass over the staged
+        ones.  Whole heads in one slot group; no text rows (a gradient's text rows stay on the rank that owns the head)."""
+        if self.Hv != self.H or len(head_order) != self.H:
+            raise ValueError("gather_heads_multi takes whole heads (no heads split by query range)")
+        if not 1 <= len(bufs) <= 4 or len(bufs) != len(out_shards):
+            raise ValueError("gather_heads_multi takes one to four (buffer, output shard) pairs")
+        order = list(head_order)
+        natural = self.even and order == list(range(self.H))
+        blk = self.Hl * self.Sl
+        pairs, staged = [], []
+        for t, (buf, out) in enumerate(zip(bufs, out_shards)):
+            dst = out if natural and out.is_contiguous() else self._stage(("g", t))
+            if dst is not out:
+                staged.append((dst, out))
+            pairs.append((buf[:self.P * blk], dst.view(self.Hv * self.Sl, self.D)))
+        splits = (None, None) if self.even else ([blk] * self.P, [c * self.Sl for c in self.counts])
+        self._finish(self._start_a2a(pairs, *splits))
+        if staged:
+            if staged[0][1].is_cuda and HIP_STAGING:
+                ops.permute_heads([x for x, _ in staged], [y for _, y in staged], dst_map=self._head_map(order))
+            else:
+                idx = torch.as_tensor(order, device=staged[0][1].device)
+                for x, y in staged:
+                    y.index_copy_(0, idx, x)
+
     def gather_heads_begin(self, out_shard: torch.Tensor, head_order: Sequence[int],
                            parts: Optional[Sequence[Optional[tuple]]] = None, n_groups: int = 1):
         """`parts` (`split_placement`): parts[i] = (t0, t1) when slot i of the head order computed only those query tokens
