@@ -323,7 +323,6 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   const int wrow0 = p0 + wave * 32;
   const bool wave_active = wrow0 < pend;  // wave-uniform
   const int my_p = wrow0 + r32;
-  const bool row_ok = my_p < pend;
   const int ld_p = min(my_p, pend - 1);
   const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
   const int64_t my_row = q_rows ? (int64_t)q_rows[ld_p] : (int64_t)(p.q_row_offset + ld_p);
@@ -368,18 +367,26 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   }
   int rowK[CH], rowV[CH];  // rows of the next K block / next V block to fetch
   int posK[CH];            // key positions behind rowK (the loop's running value)
-#define ROWS_OF(dst_, blk_)                                                       \
+  // A dense key range needs none of the three while whole blocks are requested: the source byte offsets of a lane's
+  // pieces advance by 64 rows per step (unsigned: the value left after the last such step may wrap, it is never used)
+  unsigned offK[CH], offV[CH];
+  const unsigned k_step = (unsigned)(KVB * k_ss32), v_step = (unsigned)(KVB * v_ss32);
+  // clamp_ = false only where every position of the block is known to be a key (< n_kv)
+#define ROWS_OF(dst_, blk_, clamp_)                                               \
   _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    const int pos_ = min((blk_) * KVB + 4 * (CH * wave + i_) + (lane >> 4), n_kv - 1); \
+    int pos_ = (blk_) * KVB + 4 * (CH * wave + i_) + (lane >> 4);                 \
+    if constexpr (clamp_) pos_ = min(pos_, n_kv - 1);                             \
     if constexpr (KVTAB) dst_[i_] = kv_rows[pos_];                                \
     else dst_[i_] = p.kv_row_offset + pos_;                                       \
   }
-#define DMA_K(par_) _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) __builtin_amdgcn_raw_ptr_buffer_load_lds(   \
-      k_rsrc, (LDS_AS void*)(smem + (par_) * TILE_BYTES + (CH * wave + i_) * 1024), 16,                            \
-      (int)__umul24((unsigned)rowK[i_], (unsigned)k_ss32) + k_col[i_], 0, 0, 0);
-#define DMA_V(par_) _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) __builtin_amdgcn_raw_ptr_buffer_load_lds(   \
-      v_rsrc, (LDS_AS void*)(smem + (NS + (par_)) * TILE_BYTES + (CH * wave + i_) * 1024), 16,                     \
-      (int)__umul24((unsigned)rowV[i_], (unsigned)v_ss32) + v_col[i_], 0, 0, 0);
+#define K_OFF(i_) ((int)__umul24((unsigned)rowK[i_], (unsigned)k_ss32) + k_col[i_])
+#define V_OFF(i_) ((int)__umul24((unsigned)rowV[i_], (unsigned)v_ss32) + v_col[i_])
+#define DMA_K_AT(par_, off_) _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) __builtin_amdgcn_raw_ptr_buffer_load_lds( \
+      k_rsrc, (LDS_AS void*)(smem + (par_) * TILE_BYTES + (CH * wave + i_) * 1024), 16, (int)(off_), 0, 0, 0);
+#define DMA_V_AT(par_, off_) _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) __builtin_amdgcn_raw_ptr_buffer_load_lds( \
+      v_rsrc, (LDS_AS void*)(smem + (NS + (par_)) * TILE_BYTES + (CH * wave + i_) * 1024), 16, (int)(off_), 0, 0, 0);
+#define DMA_K(par_) DMA_K_AT(par_, K_OFF(i_))
+#define DMA_V(par_) DMA_V_AT(par_, V_OFF(i_))
 
   // ---- LDS read addresses ----
   int k_rd[8];
@@ -473,21 +480,34 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   }
   // top of step j: K(j+2) -> the slot K(j) left, V(j+1) -> the slot V(j-1) left.  They are read in step j+1, after the
   // barrier that ends step j (one step of latency cover)
-  // (the key positions of the loop are running values, one add per step: written as (block index) * 64 + lane term every
-  // unrolled step keeps its own hoisted copy of the sum in a register)
-#define STAGE_DMA(kfree_, vfree_, j_)                                             \
-  DMA_K(kfree_)                                                                   \
-  DMA_V(vfree_)                                                                   \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) rowV[i_] = rowK[i_];          \
-  if constexpr (NW == 8) {                                                        \
-    _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                           \
-      posK[i_] += KVB;                                                            \
-      const int pos_ = min(posK[i_], n_kv - 1);                                   \
-      if constexpr (KVTAB) rowK[i_] = kv_rows[pos_];                              \
-      else rowK[i_] = p.kv_row_offset + pos_;                                     \
+  // (where rows are looked up -- a key table, and the tail steps of a dense range -- the key positions posK are running
+  // values, one add per step: written as (block index) * 64 + lane term every unrolled step keeps its own hoisted copy of
+  // the sum in a register.  The dense main loop uses offK / offV alone and leaves posK stale; posK, rowK and rowV are
+  // rebuilt from the block index where the tail steps begin)
+  // All of this sits in front of the scheduled block, so its vector instructions are serial issue for the wave.  tail_
+  // = false (the steps of the main loop, which only request whole blocks): a dense range costs one add per request, a
+  // key table its row-id loads; tail_ = true (the last few steps of a range, whose requests may reach past n_kv):
+  // positions are clamped to the last key, so every request stays inside the tensor and the rows of a partial block
+  // behind its end are copies of a real row (finite: their P is exactly 0).
+#define STAGE_DMA(kfree_, vfree_, j_, tail_)                                      \
+  if constexpr (!KVTAB && !(tail_)) {                                             \
+    DMA_K_AT(kfree_, offK[i_])                                                    \
+    DMA_V_AT(vfree_, offV[i_])                                                    \
+    _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) { offK[i_] += k_step; offV[i_] += v_step; } \
+  } else {                                                                        \
+    DMA_K(kfree_)                                                                 \
+    DMA_V(vfree_)                                                                 \
+    _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) rowV[i_] = rowK[i_];        \
+    if constexpr (NW == 8) {                                                      \
+      _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                         \
+        posK[i_] += KVB;                                                          \
+        const int pos_ = (tail_) ? min(posK[i_], n_kv - 1) : posK[i_];            \
+        if constexpr (KVTAB) rowK[i_] = kv_rows[pos_];                            \
+        else rowK[i_] = p.kv_row_offset + pos_;                                   \
+      }                                                                           \
+    } else { /* (four pieces per wave, key table or tail step: running positions cost more registers than the hoisted sums) */ \
+      ROWS_OF(rowK, (j_) + NS + 1, tail_)                                         \
     }                                                                             \
-  } else { /* (four pieces per wave: the running values cost more registers than the hoisted sums) */ \
-    ROWS_OF(rowK, (j_) + NS + 1)                                                  \
   }                                                                               \
   __builtin_amdgcn_sched_barrier(0);
   // end of a step: own DMA requests older than the current step have landed, then the workgroup barrier (which
@@ -526,13 +546,13 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   // one key block.  The active path is ONE basic block after the (rare) mask / rescale branches: the MFMAs of
   // the next block's scores, the exp/convert VALU work of this block, the staging traffic and the PV MFMAs are
   // all visible to the scheduler together.
-#define STEP(c0_, c1_, n0_, n1_, kcur_, knext_, vfree_, j_)                       \
+#define STEP(c0_, c1_, n0_, n1_, kcur_, knext_, vfree_, j_, tail_)                \
   { /* kcur_ = j % NS: slot of K(j) (free) and of V(j); knext_ = (j+1) % NS; vfree_ = (j-1) % NS */ \
-    STAGE_DMA(kcur_, vfree_, j_)                                                  \
-    STEP_BODY(c0_, c1_, n0_, n1_, kcur_, knext_, j_)                              \
+    STAGE_DMA(kcur_, vfree_, j_, tail_)                                           \
+    STEP_BODY(c0_, c1_, n0_, n1_, kcur_, knext_, j_, tail_)                       \
     STEP_SYNC()                                                                   \
   }
-#define STEP_BODY(c0_, c1_, n0_, n1_, kcur_, knext_, j_)                          \
+#define STEP_BODY(c0_, c1_, n0_, n1_, kcur_, knext_, j_, tail_)                   \
   {                                                                               \
     if (wave_active) {                                                            \
       V8 kpre_[KPRE > 0 ? KPRE : 1][2];                                                          \
@@ -541,8 +561,8 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
         kpre_[ks_][1] = *(const V8*)(smem + (knext_) * TILE_BYTES + k_rd[ks_] + 32 * ROWB); \
       }                                                                           \
       /* mx_cur (row max of this block's scores) was computed under the previous step's PV MFMAs; only the */ \
-      /* last, partial key block has to mask its tail and redo it here                                      */ \
-      if ((j_) * KVB + KVB > n_kv) {                                              \
+      /* last, partial key block has to mask its tail and redo it here (a tail_ step: the main loop has none) */ \
+      if ((tail_) && (j_) * KVB + KVB > n_kv) {                                   \
         int h4_ = 4 * hh; /* opaque: else the 16 sums lane term + register row are hoisted into 16 registers */ \
         asm volatile("" : "+v"(h4_));                                             \
         _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) {                       \
@@ -590,15 +610,18 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
 
   if (blk0 < blk1) {
     // prologue: K(0), K(1) and V(0) -> their ring slots; then rowK = rows(2), rowV = rows(1)
-    ROWS_OF(rowK, blk0)
+    ROWS_OF(rowK, blk0, true)
     _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) rowV[i_] = rowK[i_];
     DMA_K(0)
     DMA_V(0)
-    ROWS_OF(rowK, blk0 + 1)
+    ROWS_OF(rowK, blk0 + 1, true)
     DMA_K(1)
     _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) rowV[i_] = rowK[i_];
-    ROWS_OF(rowK, blk0 + NS)
+    ROWS_OF(rowK, blk0 + NS, true)
     _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) posK[i_] = (blk0 + NS) * KVB + 4 * (CH * wave + i_) + (lane >> 4);
+    if constexpr (!KVTAB) {
+      _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) { offK[i_] = (unsigned)K_OFF(i_); offV[i_] = (unsigned)V_OFF(i_); }
+    }
     __syncthreads();
     if (wave_active) {
       QK(sA0, sA1, 0)  // seed 0: plain scores of the first block
@@ -621,10 +644,27 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
     }
     __syncthreads();  // every wave has read K(0) before iteration 0 overwrites its slot with K(2)
   }
-  for (int blk = blk0; blk < blk1; blk += 2) {
-    STEP(sA0, sA1, sB0, sB1, 0, 1, 1, blk)
+  // Main loop: pairs of steps that touch whole key blocks only.  Step j requests K(j+2) and V(j+1), and with a key table
+  // loads the row ids of block j+3, so it needs no clamp while that block ends at or before n_kv; the block it consumes
+  // is then whole as well, so there is no tail to mask.  The last few steps of the range (and an odd one left by the
+  // pairing) run below with the clamp and the mask test in.
+  const int blk_whole = min(blk1, n_kv / KVB - (KVTAB ? NS + 1 : NS));
+  int blk = blk0;
+  for (; blk + 1 < blk_whole; blk += 2) {
+    STEP(sA0, sA1, sB0, sB1, 0, 1, 1, blk, false)
+    STEP(sB0, sB1, sA0, sA1, 1, 0, 0, blk + 1, false)
+  }
+  if constexpr (!KVTAB) {  // back from running offsets to (clamped) rows: rowK = rows(blk + 2), rowV = rows(blk + 1)
+    if (blk > blk0 && blk < blk1) {
+      ROWS_OF(rowV, blk + 1, true)
+      ROWS_OF(rowK, blk + NS, true)
+      _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) posK[i_] = (blk + NS) * KVB + 4 * (CH * wave + i_) + (lane >> 4);
+    }
+  }
+  for (; blk < blk1; blk += 2) {
+    STEP(sA0, sA1, sB0, sB1, 0, 1, 1, blk, true)
     if (blk + 1 >= blk1) break;
-    STEP(sB0, sB1, sA0, sA1, 1, 0, 0, blk + 1)
+    STEP(sB0, sB1, sA0, sA1, 1, 0, 0, blk + 1, true)
   }
 #undef QK
 #undef QK_PRE
@@ -638,32 +678,47 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
 #undef ROWS_OF
 #undef DMA_K
 #undef DMA_V
+#undef DMA_K_AT
+#undef DMA_V_AT
+#undef K_OFF
+#undef V_OFF
 
   TRACE_FLUSH_()
   if (!wave_active) return;
   // ---------------- epilogue ----------------
+  // The row bookkeeping (e_p = my_p, hh_e = hh, e_row = my_row of the prologue) is derived again from the thread id,
+  // opaque to the compiler, so that it is not the prologue's values kept in registers across both loops.  The 0 VGPR
+  // spills / 0 scratch of vorta_amd.build.kernel_resources depend on it: with the prologue's values used here the
+  // allocator spills them in front of the loops -- attn_fwd_multi_kernel 8 VGPRs (28 B of scratch), attn_fwd_pipe_kernel
+  // <T, 8, true> 5 (24 B), <T, 8, false> 1 (8 B) -- and tests/test_build_resources.py fails.
+  int tid_e = threadIdx.x;
+  asm volatile("" : "+v"(tid_e));
+  const int hh_e = (tid_e >> 5) & 1;
+  const int e_p = wrow0 + (tid_e & 31);
+  const bool e_ok = e_p < pend;
+  const int64_t e_row = q_rows ? (int64_t)q_rows[min(e_p, pend - 1)] : (int64_t)(p.q_row_offset + min(e_p, pend - 1));
   const float l_tot = half_sum(l_run);
   if (p.n_splits > 1) {
     // unnormalised partials: ws_o[y][sp][pos][d], ws_ml[y][sp][pos][2]
-    if (row_ok) {
-      const int64_t slot = ((int64_t)y * p.n_splits + sp) * p.n_q + my_p;
+    if (e_ok) {
+      const int64_t slot = ((int64_t)y * p.n_splits + sp) * p.n_q + e_p;
       float* wo = p.ws_o + slot * D;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
           f32x4 v = {o[dt][4 * rg], o[dt][4 * rg + 1], o[dt][4 * rg + 2], o[dt][4 * rg + 3]};
-          *(f32x4*)(wo + 32 * dt + 8 * rg + 4 * hh) = v;
+          *(f32x4*)(wo + 32 * dt + 8 * rg + 4 * hh_e) = v;
         }
-      if (hh == 0) {
+      if (hh_e == 0) {
         p.ws_ml[slot * 2] = m_run;  // already in the exp2 domain
         p.ws_ml[slot * 2 + 1] = l_tot;
       }
     }
     return;
   }
-  if (!row_ok) return;
-  const float inv = (my_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
+  if (!e_ok) return;
+  const float inv = (e_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
   uint2 packed[16];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -674,7 +729,7 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
       for (int j = 0; j < 4; ++j) t[j] = (T)(o[dt][4 * rg + j] * inv);
       packed[dt * 4 + rg] = *(uint2*)&t;
     }
-  char* obase = p.o + (int64_t)head * p.o_sh + hh * 8;
+  char* obase = p.o + (int64_t)head * p.o_sh + hh_e * 8;
   auto store_row = [&](int64_t row) {
     char* op = obase + row * p.o_ss;
 #pragma unroll
@@ -682,9 +737,9 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) *(uint2*)(op + (32 * dt + 8 * rg) * 2) = packed[dt * 4 + rg];
   };
-  store_row(my_row);
-  if (p.dup_rows && my_p < p.n_dup_pos) {
-    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)my_p * p.n_dup;
+  store_row(e_row);
+  if (p.dup_rows && e_p < p.n_dup_pos) {
+    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)e_p * p.n_dup;
     for (int i = 0; i < p.n_dup; ++i) store_row((int64_t)dr[i]);
   }
 }
