@@ -42,7 +42,9 @@ extern "C" {
                                 8: adds vorta_i8_tail_flags and vorta_split_heads (per-head choice between int8 and 16-bit scores)
                                 9: adds the backward entry points (vorta_attn_bwd, vorta_mix_experts_bwd, vorta_cast_grads);
                                    9 also carries vorta_qk_norm_rope_bwd (a pure addition: every earlier call means what it meant;
-                                   a binding asks for the symbol and for vorta_sizeof(16) to tell the two libraries apart) */
+                                   a binding asks for the symbol and for vorta_sizeof(16) to tell the two libraries apart)
+                                   and the key-major backward, vorta_attn_bwd_stats / vorta_attn_bwd_kmajor (a pure addition too:
+                                   a binding asks for the symbols and for vorta_attn_bwd_kmajor_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -188,6 +190,41 @@ typedef struct vorta_attn_bwd_args {
 } vorta_attn_bwd_args;
 
 int vorta_attn_bwd(const vorta_attn_bwd_args* args, void* hip_stream);
+
+/*
+ * vorta_attn_bwd_stats + vorta_attn_bwd_kmajor (ABI 9, added after the other backward entry points) -- the SAME gradient as
+ * vorta_attn_bwd by a second, KEY-MAJOR algorithm, in two launches on one stream:
+ *   1. vorta_attn_bwd_stats (csrc/attn_bwd_stats.hip; query-major, no atomics) writes, for every head slot y and query
+ *      position p of the launch, two floats to the caller's workspace stats[y * stats_stride_h + 2 p + 0..1]:
+ *          lse2[p]  = m c + log2(l)     the log-sum-exp of the row's scores in the exp2 domain, c = scale log2(e)
+ *          delta[p] = sum_j P[p][j] (dO_eff[p] . v[j])
+ *      with dO_eff as above (do_scale weight, dup_rows gradients added, zero for p >= q_valid_eff).  Positions p >= q_valid_eff
+ *      get delta = 0 and a finite lse2.  bwd.dq / dk / dv are not read by this entry point.
+ *   2. vorta_attn_bwd_kmajor (csrc/attn_bwd_kmajor.hip) reads them: one workgroup owns 256 keys of one (head slot, group) key
+ *      list, keeps their dK and dV on chip while it sweeps the group's queries in 32-row slices, and adds only dQ across
+ *      workgroups -- a quarter of the atomic bytes of the query-major kernel, whose time is bounded by them.
+ * bwd means what it means for vorta_attn_bwd, including "ADDED to, the caller zeroes" and "rows and heads the launch does not
+ * name receive nothing".  n_key_lists = the number of groups (key lists) the rows of a q_block_table refer to (required with a
+ * table: the grid has one workgroup per list and key block); 0 without a table, where q_group_len gives it.  The grid is sized
+ * from n_kv; *n_kv_dev trims it as in the forward, max(1, min(*n_kv_dev, n_kv)).
+ * REPRODUCIBILITY: dq, dk and dv are ALL accumulated with vector float atomics here (dq: one add per key block; dk / dv: one add
+ * per workgroup -- key lists of different groups overlap, and the experts of the mixture share the buffers), so none of them
+ * is bit-reproducible from run to run.  There is no protocol between workgroups: none ever waits for another.
+ * VORTA_EINVAL for a wrong struct_size (either block), a null or misaligned tensor (stats: 8-byte aligned, stats_stride_h even
+ * and >= 2 n_q), a table without n_key_lists; VORTA_EUNSUPPORTED for a dtype other than bf16 / fp16 or head_dim != 128;
+ * n_heads == 0 is VORTA_OK and launches nothing.
+ */
+typedef struct vorta_attn_bwd_kmajor_args {
+  uint32_t struct_size;    /* = sizeof(vorta_attn_bwd_kmajor_args) = vorta_attn_bwd_kmajor_args_size() */
+  int32_t n_key_lists;     /* 0 = from q_group_len */
+  vorta_attn_bwd_args bwd; /* the launch, as for vorta_attn_bwd */
+  float* stats;            /* [n_heads][stats_stride_h]: written by _stats, read by _kmajor */
+  int64_t stats_stride_h;  /* floats per head slot, >= 2 n_q */
+} vorta_attn_bwd_kmajor_args;
+
+int vorta_attn_bwd_stats(const vorta_attn_bwd_kmajor_args* args, void* hip_stream);
+int vorta_attn_bwd_kmajor(const vorta_attn_bwd_kmajor_args* args, void* hip_stream);
+int vorta_attn_bwd_kmajor_args_size(void); /* (vorta_sizeof keeps its 17 indices: a library without these entry points lacks the symbol) */
 
 /*
  * fp8 (e4m3) path -- BASELINE.json configs[4] "fp8 MFMA QK^T/PV path".  The reference has no fp8 code: this path serves

@@ -4,12 +4,17 @@ and is not involved).
     python tools/bench_attn_bwd.py --case dense   --config hunyuan-129f     one dense head
     python tools/bench_attn_bwd.py --case mixture --config wan1.3b-49f      the full soft-mixture layer, every head
     python tools/bench_attn_bwd.py --all --out profiles/attn_bwd_timing.json
+    python tools/bench_attn_bwd.py --all --algorithm both --out profiles/attn_bwd_key_major_timing.json
 
 `--all` runs the four (case, config) steps as child processes, each under its own `timeout -k 10`, in a chain that stops at
 the first step that fails (the shell form: `timeout -k 10 600 python tools/bench_attn_bwd.py --case dense --config
 hunyuan-129f && timeout -k 10 600 ...`), and collects their JSON lines.  The yardstick of the backward figure is the forward of
 the SAME launches in the same process; FLOPs count the five products of the backward plus the recomputed scores (6 / 2 of
-the forward's 4 S_q S_kv D per head)."""
+the forward's 4 S_q S_kv D per head).
+
+`--algorithm query_major` (the default) times vorta_attn_bwd, `key_major` the statistics pass + vorta_attn_bwd_kmajor, `both`
+the two side by side in one process, with the bytes each adds with float atomics and bytes / time against the chip-wide rate
+of such adds (ATOMIC_RATE): a kernel near it is bound by its atomics whatever its loop does."""
 import argparse
 import json
 import os
@@ -19,6 +24,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+ATOMIC_RATE = 1.3e12  # bytes / s of float atomic adds, chip-wide (MI355X; measured at 1.26-1.36e12 for every placement)
 STEPS = [("dense", "hunyuan-129f"), ("dense", "wan1.3b-49f"), ("mixture", "hunyuan-129f"), ("mixture", "wan1.3b-49f")]
 
 
@@ -36,7 +42,26 @@ def _time(fn, warmup, steps):
     return e0.elapsed_time(e1) / steps
 
 
-def run_one(case, config, warmup, steps):
+def atomic_bytes(c, H):
+    """(query-major, key-major) bytes one recorded launch adds with float atomics.  Query-major: every 128-row query block
+    adds the dK and dV rows of all its keys.  Key-major: every live query row is added once per 256-key block (dQ), every
+    key row of a group with a live query once (dK, dV)."""
+    heads = c.get("n_heads") or (c["head_list"].numel() if c.get("head_list") is not None else H)
+    n_q, n_kv = c["n_q"], c["n_kv"]
+    q_valid = n_q if c.get("q_valid") is None else c["q_valid"]
+    if c.get("q_block_table") is not None:
+        rows = c["q_block_table"].cpu().tolist()
+    else:
+        glen = c.get("q_group_len", 0) or n_q
+        rows = [(g, g * glen, min((g + 1) * glen, n_q)) for g in range(-(-n_q // glen))]
+    live = [(g, a, min(b, q_valid)) for g, a, b in rows if min(b, q_valid) > a]
+    row_bytes = 128 * 4
+    qm = sum(-(-(b - a) // 128) for _, a, b in rows if b > a) * n_kv * row_bytes * 2
+    km = sum(b - a for _, a, b in live) * -(-n_kv // 256) * row_bytes + len({g for g, _, _ in live}) * n_kv * row_bytes * 2
+    return heads * qm, heads * km
+
+
+def run_one(case, config, warmup, steps, algorithm="query_major"):
     import torch
     from bench import CONFIGS
     from vorta_amd import ops, routed
@@ -66,14 +91,37 @@ def run_one(case, config, warmup, steps):
         weight_of = lambda c, o: s16[:, next(i for i, b in enumerate(bufs) if b.data_ptr() == o.data_ptr())]  # noqa: E731
         fwd = lambda: routed.routed_attention(q, k, v, routing, geom, **kw)  # noqa: E731
     acc = [torch.zeros(q.shape[1:], dtype=torch.float32, device=dev) for _ in range(3)]
-    bwd = lambda: routed._replay_backward(launches, g[0], acc[0], acc[1], acc[2], weight_of)  # noqa: E731
+    bwd_by = lambda alg: (lambda: routed._replay_backward(launches, g[0], acc[0], acc[1], acc[2], weight_of,  # noqa: E731
+                                                          algorithm=alg))
+
+    def stats_only():
+        for c in launches:
+            c = dict(c)
+            x = [c.pop(n) for n in ("q", "k", "v", "out")]
+            ops.attn_bwd_stats(*x, g[0], do_scale=None if weight_of is None else weight_of(c, x[3]), **c)
+
     fwd_ms = _time(fwd, warmup, steps)
-    bwd_ms = _time(bwd, warmup, steps)
     fwd_flops = sum(c.get("flops", 0.0) for c in launches)
-    return dict(case=case, config=config, dtype=cfg["dtype"], heads=H, tokens=S + T, launches=len(launches),
-                warmup=warmup, steps=steps, fwd_ms=round(fwd_ms, 3), bwd_ms=round(bwd_ms, 3),
-                bwd_over_fwd=round(bwd_ms / fwd_ms, 3), fwd_tflops=round(fwd_flops / fwd_ms / 1e9, 1),
-                bwd_tflops=round(3.0 * fwd_flops / bwd_ms / 1e9, 1), device=torch.cuda.get_device_name(0))
+    res = dict(case=case, config=config, dtype=cfg["dtype"], heads=H, tokens=S + T, launches=len(launches),
+               warmup=warmup, steps=steps, fwd_ms=round(fwd_ms, 3))
+    per = lambda ms: dict(bwd_ms=round(ms, 3), bwd_over_fwd=round(ms / fwd_ms, 3),  # noqa: E731
+                          bwd_tflops=round(3.0 * fwd_flops / ms / 1e9, 1))
+    if algorithm != "both":
+        res.update(per(_time(bwd_by(algorithm), warmup, steps)), fwd_tflops=round(fwd_flops / fwd_ms / 1e9, 1))
+        if algorithm == "key_major":
+            res.update(algorithm=algorithm, stats_ms=round(_time(stats_only, warmup, steps), 3))
+    else:
+        res["fwd_tflops"] = round(fwd_flops / fwd_ms / 1e9, 1)
+        nbytes = dict(zip(routed.ATTENTION_BACKWARDS, map(sum, zip(*(atomic_bytes(c, H) for c in launches)))))
+        for alg in routed.ATTENTION_BACKWARDS:
+            ms = _time(bwd_by(alg), warmup, steps)
+            res[alg] = dict(per(ms), atomic_bytes=nbytes[alg], atomic_floor_ms=round(nbytes[alg] / ATOMIC_RATE * 1e3, 3),
+                            atomic_tb_per_s=round(nbytes[alg] / ms / 1e9, 3),
+                            of_atomic_rate=round(nbytes[alg] / (ms * 1e-3) / ATOMIC_RATE, 3))
+        res["key_major"]["stats_ms"] = round(_time(stats_only, warmup, steps), 3)
+        res["key_major_speedup"] = round(res["query_major"]["bwd_ms"] / res["key_major"]["bwd_ms"], 3)
+    res["device"] = torch.cuda.get_device_name(0)
+    return res
 
 
 def main():
@@ -81,18 +129,19 @@ def main():
     ap.add_argument("--case", choices=["dense", "mixture"])
     ap.add_argument("--config", default="hunyuan-129f")
     ap.add_argument("--all", action="store_true")
+    ap.add_argument("--algorithm", choices=["query_major", "key_major", "both"], default="query_major")
     ap.add_argument("--out")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=280)
     a = ap.parse_args()
     if not a.all:
-        print(json.dumps(run_one(a.case, a.config, a.warmup, a.steps)), flush=True)
+        print(json.dumps(run_one(a.case, a.config, a.warmup, a.steps, a.algorithm)), flush=True)
         return 0
     results = []
     for case, config in STEPS:
         cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--case", case,
-               "--config", config, "--warmup", str(a.warmup), "--steps", str(a.steps)]
+               "--config", config, "--warmup", str(a.warmup), "--steps", str(a.steps), "--algorithm", a.algorithm]
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
         if r.returncode != 0:  # nothing more is started on the GPU after a step that failed
             print(r.stdout[-2000:], r.stderr[-2000:], f"step {case} {config} ended with {r.returncode}: stopping", sep="\n")
@@ -103,7 +152,10 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             json.dump(dict(note="backward / forward of the same launches in one process; TFLOP/s count 4 S_q S_kv D per head "
-                                "and launch for the forward and 3 x that (5 products + the recomputed scores) for the backward",
+                                "and launch for the forward and 3 x that (5 products + the recomputed scores) for the backward"
+                                + ("; atomic_bytes = bytes added with float atomics, atomic_floor_ms = those bytes at the "
+                                   "chip-wide rate of 1.3 TB/s, of_atomic_rate = bytes / time against that rate; key_major's "
+                                   "bwd_ms includes its statistics pass (stats_ms, timed alone)" if a.algorithm == "both" else ""),
                            results=results), f, indent=1)
     return 0
 

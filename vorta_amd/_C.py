@@ -143,6 +143,12 @@ class AttnBwdArgs(C.Structure):
     ]
 
 
+class AttnBwdKmajorArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("n_key_lists", _i32), ("bwd", AttnBwdArgs), ("stats", _vp), ("stats_stride_h", _i64),
+    ]
+
+
 class MixBwdArgs(C.Structure):
     _fields_ = [
         ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("heads", _i32), ("n_experts", _i32),
@@ -195,6 +201,9 @@ SYMBOLS = {
     "vorta_qk_norm_rope_bwd": (C.c_int, [C.POINTER(NormRopeBwdArgs), _vp]),
     "vorta_mix_experts": (C.c_int, [C.POINTER(MixArgs), _vp]),
     "vorta_attn_bwd": (C.c_int, [C.POINTER(AttnBwdArgs), _vp]),
+    "vorta_attn_bwd_stats": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
+    "vorta_attn_bwd_kmajor": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
+    "vorta_attn_bwd_kmajor_args_size": (C.c_int, []),
     "vorta_mix_experts_bwd": (C.c_int, [C.POINTER(MixBwdArgs), _vp]),
     "vorta_cast_grads": (C.c_int, [C.POINTER(CastArgs), _vp]),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
@@ -234,7 +243,8 @@ def lib():
         try:
             fn = getattr(h, name)
         except AttributeError:
-            # ABI 9 gained vorta_qk_norm_rope_bwd without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks it
+            # ABI 9 gained vorta_qk_norm_rope_bwd and the key-major backward without a new number: an older ABI-9 build
+            # (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
@@ -247,6 +257,10 @@ def lib():
         if h.vorta_sizeof(which) != C.sizeof(st):
             raise VortaHipError(f"struct layout mismatch for {st.__name__}: "
                                 f"C {h.vorta_sizeof(which)} vs ctypes {C.sizeof(st)}")
+    # (vorta_sizeof keeps its 17 indices; the key-major backward's block reports its size through a symbol of its own)
+    if h.vorta_attn_bwd_kmajor_args_size() != C.sizeof(AttnBwdKmajorArgs):
+        raise VortaHipError(f"struct layout mismatch for AttnBwdKmajorArgs: C {h.vorta_attn_bwd_kmajor_args_size()} "
+                            f"vs ctypes {C.sizeof(AttnBwdKmajorArgs)}")
     _lib = h
     return h
 

@@ -9,3 +9,11 @@ def set_attention_precision(precision: str, *, measurement_only: bool = False) -
     (vorta_amd/routed.py)."""
     from .routed import set_attention_precision as _set
     _set(precision, measurement_only=measurement_only)
+
+
+def set_attention_backward(name: str) -> None:
+    """"query_major" (the default: vorta_attn_bwd, dq bit-reproducible) or "key_major" (a softmax-statistics pass, then a
+    kernel that keeps dK / dV on chip and sums only dQ across workgroups) for the differentiable operators and processors.
+    Also: VORTA_ATTENTION_BACKWARD in the environment (vorta_amd/routed.py)."""
+    from .routed import set_attention_backward as _set
+    _set(name)

@@ -284,8 +284,10 @@ class _RecvSoftMixture(torch.autograd.Function):
         ptrs = [b.data_ptr() for b in ebufs]
         # float32 accumulators laid out like the receive buffers: a launch adds through the same row tables and head stride
         acc = [torch.zeros((lay.rows_total, lay.D), dtype=torch.float32, device=qb.device) for _ in range(3)]
+        # (the query-major backward whatever routed.set_attention_backward / VORTA_ATTENTION_BACKWARD say: pinned like the
+        # other choices of this mode)
         _replay_backward(ctx.launches, hv(g), hv(acc[0]), hv(acc[1]), hv(acc[2]),
-                         lambda _, o: sc[:, ptrs.index(o.data_ptr())])
+                         lambda _, o: sc[:, ptrs.index(o.data_ptr())], algorithm="query_major")
         grads = [torch.empty_like(qb) for _ in range(3)]
         ops.cast_grads([_flat(lay, a) for a in acc], [_flat(lay, x) for x in grads])
         d_sc = torch.zeros_like(scores)

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libvorta_hip.so")
-SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
+SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
            "sta_tables.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "permute.hip"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent fp32 adds of the softmax row sum into v_pk_add_f32 plus the
 # v_mov pairs to feed them -- more instructions on the VALU issue port that bounds the attention loop (+2 % without)
@@ -20,6 +20,10 @@ SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_fwd_fp8.hip", "attn_
 # loop for the worse (+1.7 % on the fused layer kernel without it; measured A/B in one session)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-mllvm", "-enable-post-misched=0",
          "-I" + INCLUDE, "-I" + CSRC, "-Wno-unused-result"]
+# attn_bwd_kmajor.hip keeps 256 registers of dK / dV accumulators per lane: its other MFMA results (S, dP, dQ) must be free
+# to live in the ordinary registers, which the compiler's default (every MFMA result of such a kernel in an accumulator
+# register) does not allow -- it spills 227 registers without this option and none with it
+SOURCE_FLAGS = {"attn_bwd_kmajor.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _newer(src, dst):
@@ -37,7 +41,8 @@ def build(force: bool = False, verbose: bool = True, extra_flags=None, suffix: s
         raise SystemExit("VORTA_EXTRA_FLAGS needs VORTA_BUILD_SUFFIX: experimental flags are never built into "
                          "libvorta_hip.so itself")
     lib = LIB if not suffix else os.path.join(CSRC, f"libvorta_hip{suffix}.so")
-    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "attn_fwd_fp8_diag.inc"),
+    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "attn_bwd_kmajor.h"),
+            os.path.join(CSRC, "attn_fwd_fp8_diag.inc"),
             os.path.join(CSRC, "attn_fwd_i8_diag.inc"), os.path.join(CSRC, "attn_fwd_diag.inc"), os.path.join(INCLUDE, "vorta_hip.h")]
     if extra:  # vorta_build_info() of a variant library names its flags
         extra = extra + ['-DVORTA_VARIANT_FLAGS="%s"' % " ".join(extra).replace('"', "'")]
@@ -46,7 +51,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=None, suffix: s
         src = os.path.join(CSRC, s)
         obj = os.path.join(CSRC, s.replace(".hip", f"{suffix}.o"))
         if force or _newer(src, obj) or any(_newer(d, obj) for d in deps):
-            cmd = [hipcc] + FLAGS + extra + ["-c", src, "-o", obj]
+            cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(s, []) + extra + ["-c", src, "-o", obj]
             if verbose:
                 print("[vorta_amd.build]", " ".join(cmd), flush=True)
             subprocess.check_call(cmd)
@@ -85,7 +90,7 @@ def kernel_resources(source: str):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        subprocess.check_call([hipcc] + FLAGS + ["-S", "--cuda-device-only", os.path.join(CSRC, source), "-o", out])
+        subprocess.check_call([hipcc] + FLAGS + SOURCE_FLAGS.get(source, []) + ["-S", "--cuda-device-only", os.path.join(CSRC, source), "-o", out])
         text = open(out).read()
     meta = text[text.index("amdhsa.kernels"):]
     res = {}

@@ -905,17 +905,12 @@ def _f32_tensor(t: torch.Tensor, like: torch.Tensor, name: str) -> _C.Tensor:
     return _tensor(t)
 
 
-def attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, dq: torch.Tensor,
-             dk: torch.Tensor, dv: torch.Tensor, *, do_scale: Optional[torch.Tensor] = None, **kw) -> None:
-    """vorta_attn_bwd (include/vorta_hip.h): the gradient of the attn_fwd launch with the same keywords, ADDED to the float32
-    (H,S,D) buffers dq / dk / dv (the caller zeroes them).  `o` is the forward's output, `d_o` its gradient (16-bit, same
-    shape); `do_scale`: optional 1-D view in the inputs' dtype, one weight per HEAD id (the soft mixture's scores[:, e]).
-    The keywords that only shape the forward's launch (n_splits, block_rows with no q_block_table, the fused-grid hints,
-    tag / flops) are accepted and dropped.  dq is bit-reproducible, dk / dv are not (float atomics)."""
+def _attn_bwd_args(who: str, q, k, v, o, d_o, dq, dk, dv, do_scale, kw) -> _C.AttnBwdArgs:
+    """the vorta_attn_bwd_args of one launch (dq / dk / dv: None for an entry point that does not write them)"""
     if q.dtype not in _DT or not (q.dtype == k.dtype == v.dtype == o.dtype == d_o.dtype):
-        raise ValueError("attn_bwd: q, k, v, o, d_o must share dtype bf16 or fp16 (there is no 8-bit backward)")
+        raise ValueError(f"{who}: q, k, v, o, d_o must share dtype bf16 or fp16 (there is no 8-bit backward)")
     if d_o.shape != o.shape:
-        raise ValueError("attn_bwd: d_o must have the shape of o")
+        raise ValueError(f"{who}: d_o must have the shape of o")
     _require_gpu(d_o, dq, dk, dv, do_scale)
     table = kw.get("q_block_table") is not None
     kw = {key: val for key, val in kw.items() if key not in _BWD_DROPPED or (key == "block_rows" and table)}
@@ -926,10 +921,67 @@ def attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor,
     a.d_o = _tensor(d_o)
     if do_scale is not None:
         if do_scale.dtype != q.dtype or do_scale.dim() != 1:
-            raise ValueError("attn_bwd: do_scale is a 1-D view (one weight per head id) in the inputs' dtype")
+            raise ValueError(f"{who}: do_scale is a 1-D view (one weight per head id) in the inputs' dtype")
         a.do_scale, a.do_scale_stride_h = do_scale.data_ptr(), do_scale.stride(0)
-    a.dq, a.dk, a.dv = _f32_tensor(dq, q, "dq"), _f32_tensor(dk, k, "dk"), _f32_tensor(dv, v, "dv")
+    if dq is not None:
+        a.dq, a.dk, a.dv = _f32_tensor(dq, q, "dq"), _f32_tensor(dk, k, "dk"), _f32_tensor(dv, v, "dv")
+    return a
+
+
+def attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, dq: torch.Tensor,
+             dk: torch.Tensor, dv: torch.Tensor, *, do_scale: Optional[torch.Tensor] = None, **kw) -> None:
+    """vorta_attn_bwd (include/vorta_hip.h): the gradient of the attn_fwd launch with the same keywords, ADDED to the float32
+    (H,S,D) buffers dq / dk / dv (the caller zeroes them).  `o` is the forward's output, `d_o` its gradient (16-bit, same
+    shape); `do_scale`: optional 1-D view in the inputs' dtype, one weight per HEAD id (the soft mixture's scores[:, e]).
+    The keywords that only shape the forward's launch (n_splits, block_rows with no q_block_table, the fused-grid hints,
+    tag / flops) are accepted and dropped.  dq is bit-reproducible, dk / dv are not (float atomics)."""
+    a = _attn_bwd_args("attn_bwd", q, k, v, o, d_o, dq, dk, dv, do_scale, kw)
     _C.check(_C.lib().vorta_attn_bwd(C.byref(a), _stream()), "vorta_attn_bwd")
+
+
+def attn_bwd_stats_shape(n_heads: int, n_q: int) -> Tuple[int, int, int]:
+    """shape of the float32 statistics workspace of a launch with n_heads head SLOTS and n_q query positions"""
+    return (n_heads, n_q, 2)
+
+
+def _kmajor_args(who: str, bwd: _C.AttnBwdArgs, stats: torch.Tensor, n_key_lists: int) -> _C.AttnBwdKmajorArgs:
+    need = attn_bwd_stats_shape(bwd.fwd.n_heads, bwd.fwd.n_q)
+    if stats.dtype != torch.float32 or stats.dim() != 3 or stats.shape[0] < need[0] or tuple(stats.shape[1:]) != need[1:] \
+            or not stats.is_contiguous():
+        raise ValueError(f"{who}: stats must be a contiguous float32 tensor of shape {need} (attn_bwd_stats_shape)")
+    _require_gpu(stats)
+    a = _C.AttnBwdKmajorArgs()
+    a.struct_size = C.sizeof(_C.AttnBwdKmajorArgs)
+    a.n_key_lists = n_key_lists if bwd.fwd.q_block_table else 0
+    a.bwd = bwd
+    a.stats, a.stats_stride_h = stats.data_ptr(), stats.stride(0)
+    return a
+
+
+def attn_bwd_stats(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor,
+                   stats: Optional[torch.Tensor] = None, *, do_scale: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+    """vorta_attn_bwd_stats (include/vorta_hip.h): pass 1 of the key-major backward.  For the attn_fwd launch with the same
+    keywords (those of `attn_bwd`) it writes stats[y][p] = (lse2, delta) for every head slot y and query position p: the
+    log-sum-exp of the row's scores in the exp2 domain and sum_j P[p][j] (dO_eff[p] . v[j]).  `stats`: float32
+    `attn_bwd_stats_shape(n_heads, n_q)`, allocated when None; returned."""
+    a = _attn_bwd_args("attn_bwd_stats", q, k, v, o, d_o, None, None, None, do_scale, kw)
+    if stats is None:
+        stats = torch.empty(attn_bwd_stats_shape(a.fwd.n_heads, a.fwd.n_q), dtype=torch.float32, device=q.device)
+    ka = _kmajor_args("attn_bwd_stats", a, stats, kw.get("n_key_lists", 0))
+    _C.check(_C.lib().vorta_attn_bwd_stats(C.byref(ka), _stream()), "vorta_attn_bwd_stats")
+    return stats
+
+
+def attn_bwd_key_major(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor,
+                       dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, stats: torch.Tensor, *,
+                       do_scale: Optional[torch.Tensor] = None, **kw) -> None:
+    """vorta_attn_bwd_kmajor (include/vorta_hip.h): pass 2 of the key-major backward -- what `attn_bwd` computes, ADDED to
+    the float32 dq / dk / dv, from the statistics `attn_bwd_stats` wrote for the SAME launch (same tensors, do_scale and
+    keywords, earlier on the same stream).  A workgroup keeps the dK / dV of 256 keys on chip and only dQ is summed across
+    workgroups.  None of dq, dk, dv is bit-reproducible (float atomics)."""
+    a = _attn_bwd_args("attn_bwd_key_major", q, k, v, o, d_o, dq, dk, dv, do_scale, kw)
+    ka = _kmajor_args("attn_bwd_key_major", a, stats, kw.get("n_key_lists", 0))
+    _C.check(_C.lib().vorta_attn_bwd_kmajor(C.byref(ka), _stream()), "vorta_attn_bwd_kmajor")
 
 
 def mix_experts_bwd(xs, d_out: torch.Tensor) -> torch.Tensor:

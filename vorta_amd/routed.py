@@ -500,19 +500,60 @@ def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
     return out
 
 
+ATTENTION_BACKWARDS = ("query_major", "key_major")
+_attention_backward = None  # the process-wide default; None = not set: VORTA_ATTENTION_BACKWARD, else "query_major"
+
+
+def _check_backward(name: str, where: str) -> str:
+    if name not in ATTENTION_BACKWARDS:
+        raise ValueError(f"{where}: unknown attention backward {name!r} (one of {', '.join(ATTENTION_BACKWARDS)})")
+    return name
+
+
+def set_attention_backward(name: str) -> None:
+    """the process-wide attention backward algorithm of the differentiable operators and processors: "query_major"
+    (ops.attn_bwd: dq bit-reproducible) or "key_major" (ops.attn_bwd_stats + ops.attn_bwd_key_major: a quarter of the atomic
+    bytes, nothing bit-reproducible).  Overrides the environment switch VORTA_ATTENTION_BACKWARD."""
+    global _attention_backward
+    _attention_backward = _check_backward(name, "set_attention_backward")
+
+
+def attention_backward(backward: Optional[str] = None) -> str:
+    """the algorithm a call with `backward` uses: its own choice, else set_attention_backward's, else the environment's
+    VORTA_ATTENTION_BACKWARD, else "query_major" """
+    if backward is not None:
+        return _check_backward(backward, "backward")
+    if _attention_backward is not None:
+        return _attention_backward
+    import os
+    return _check_backward(os.environ.get("VORTA_ATTENTION_BACKWARD") or "query_major", "VORTA_ATTENTION_BACKWARD")
+
+
+def _attn_bwd_by(algorithm: str, q, k, v, o, d_out, dq, dk, dv, do_scale=None, **launch) -> None:
+    """the gradient of one recorded launch by either algorithm"""
+    if algorithm == "key_major":
+        stats = ops.attn_bwd_stats(q, k, v, o, d_out, do_scale=do_scale, **launch)
+        ops.attn_bwd_key_major(q, k, v, o, d_out, dq, dk, dv, stats, do_scale=do_scale, **launch)
+    else:
+        ops.attn_bwd(q, k, v, o, d_out, dq, dk, dv, do_scale=do_scale, **launch)
+
+
 def _replay_backward(launches, d_out: torch.Tensor, dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor,
-                     weight_of=None) -> None:
-    """one ops.attn_bwd per recorded forward launch, with the SAME dictionaries (forward and backward cannot disagree on a
-    table); `weight_of(launch, out)` = the per-head weight of the launch's output in the loss (None: 1)"""
+                     weight_of=None, algorithm: str = "query_major") -> None:
+    """one backward per recorded forward launch, with the SAME dictionaries (forward and backward cannot disagree on a
+    table): ops.attn_bwd ("query_major"), or the statistics pass and then the key-major pass ("key_major");
+    `weight_of(launch, out)` = the per-head weight of the launch's output in the loss (None: 1)"""
+    _check_backward(algorithm, "_replay_backward")
     for c in launches:
         c = dict(c)
         q, k, v, o = c.pop("q"), c.pop("k"), c.pop("v"), c.pop("out")
-        ops.attn_bwd(q, k, v, o, d_out, dq, dk, dv, do_scale=None if weight_of is None else weight_of(c, o), **c)
+        _attn_bwd_by(algorithm, q, k, v, o, d_out, dq, dk, dv, do_scale=None if weight_of is None else weight_of(c, o), **c)
 
 
 class _SoftMixture(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, routing_score, geom, model, text_len, text_valid, scale):
+    def forward(ctx, q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward):
+        ctx.algorithm = attention_backward(backward)
         H = q.shape[-3]
         out = torch.empty_like(q)
         bufs = [torch.empty_like(out) for _ in range(3)]
@@ -538,18 +579,18 @@ class _SoftMixture(torch.autograd.Function):
             e = next(i for i, b in enumerate(bufs3) if b.data_ptr() == o.data_ptr())
             return sc[:, e]
 
-        _replay_backward(ctx.launches, g3, acc[0], acc[1], acc[2], weight_of)
+        _replay_backward(ctx.launches, g3, acc[0], acc[1], acc[2], weight_of, ctx.algorithm)
         grads = [torch.empty_like(q3) for _ in range(3)]
         ops.cast_grads(acc, grads)
         d_sc = torch.zeros_like(routing_score)  # batch items > 0 are not read by the forward
         d_sc[0] = dscores.to(routing_score.dtype)
         dq, dk, dv = (g.view(q.shape) for g in grads)
-        return dq, dk, dv, d_sc, None, None, None, None, None
+        return dq, dk, dv, d_sc, None, None, None, None, None, None
 
 
 def soft_mixture_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,
                                     geom: RoutedGeometry, *, model: str, text_len: int = 0, text_valid: int = 0,
-                                    scale: Optional[float] = None) -> torch.Tensor:
+                                    scale: Optional[float] = None, backward: Optional[str] = None) -> torch.Tensor:
     """`soft_mixture_attention` as a differentiable operator (router training: the loss reaches the routing scores and,
     through q, k, v, every earlier layer).  The forward is the same launches and gives the same bits; it keeps q, k, v, the
     scores, the three expert outputs and the launches as recorded.  The backward zeroes three float32 (H,N,D) buffers,
@@ -557,13 +598,16 @@ def soft_mixture_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.T
     the weight scores[:, e] of its expert, and rounds dq, dk, dv once (ops.cast_grads).  The coreset keep / drop lists and
     the sliding-tile tables are constants of the backward (the reference ranks with argsort: no gradient flows through the
     selection there either, coreset_select.py:98-124).  dk / dv are not bit-reproducible (float atomics); dq and dscores are.
-    q, k, v: contiguous (1,H,N,D), like the forward's."""
-    return _SoftMixture.apply(q, k, v, routing_score, geom, model, text_len, text_valid, scale)
+    `backward`: "query_major" (the above) or "key_major" (per launch ops.attn_bwd_stats, then ops.attn_bwd_key_major: dq is
+    a sum of float atomics too); None follows `set_attention_backward` / VORTA_ATTENTION_BACKWARD, read when the forward
+    runs.  The forward is the same either way.  q, k, v: contiguous (1,H,N,D), like the forward's."""
+    return _SoftMixture.apply(q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward)
 
 
 class _Dense(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, kv_valid, q_valid, scale):
+    def forward(ctx, q, k, v, kv_valid, q_valid, scale, backward):
+        ctx.algorithm = attention_backward(backward)
         out = torch.empty_like(q)
         Sq, Skv = q.shape[-2], k.shape[-2]
         launch = dict(n_q=Sq, n_kv=Skv if kv_valid is None else kv_valid, q_valid=Sq if q_valid is None else q_valid,
@@ -578,18 +622,20 @@ class _Dense(torch.autograd.Function):
         q, k, v, out = ctx.saved_tensors
         f = ops.fold_heads
         acc = [torch.zeros(f(x).shape, dtype=torch.float32, device=q.device) for x in (q, k, v)]
-        ops.attn_bwd(f(q), f(k), f(v), f(out), f(d_out.contiguous()), acc[0], acc[1], acc[2], **ctx.launch)
+        _attn_bwd_by(ctx.algorithm, f(q), f(k), f(v), f(out), f(d_out.contiguous()), acc[0], acc[1], acc[2], **ctx.launch)
         grads = [torch.empty_like(x) for x in (q, k, v)]
         ops.cast_grads(acc[:1], [f(grads[0])])
         ops.cast_grads(acc[1:], [f(grads[1]), f(grads[2])])
-        return grads[0], grads[1], grads[2], None, None, None
+        return grads[0], grads[1], grads[2], None, None, None, None
 
 
 def dense_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, kv_valid: Optional[int] = None,
-                             q_valid: Optional[int] = None, scale: Optional[float] = None) -> torch.Tensor:
+                             q_valid: Optional[int] = None, scale: Optional[float] = None,
+                             backward: Optional[str] = None) -> torch.Tensor:
     """`dense_attention` (the teacher path, use_original_attn=True: hunyuan.py:167-176, wan.py:134-145) as a differentiable
-    operator: the same launch forward, ops.attn_bwd + ops.cast_grads backward.  (B,H,Sq,D) x (B,H,Skv,D), contiguous."""
-    return _Dense.apply(q, k, v, kv_valid, q_valid, scale)
+    operator: the same launch forward, ops.attn_bwd + ops.cast_grads backward.  (B,H,Sq,D) x (B,H,Skv,D), contiguous.
+    `backward`: as for `soft_mixture_attention_autograd`."""
+    return _Dense.apply(q, k, v, kv_valid, q_valid, scale, backward)
 
 
 def _norm_rope_forward(x: torch.Tensor, weight, eps: float, cos, sin, rope_tokens, across_heads: bool) -> torch.Tensor:
