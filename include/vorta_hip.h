@@ -44,7 +44,9 @@ extern "C" {
                                    9 also carries vorta_qk_norm_rope_bwd (a pure addition: every earlier call means what it meant;
                                    a binding asks for the symbol and for vorta_sizeof(16) to tell the two libraries apart)
                                    and the key-major backward, vorta_attn_bwd_stats / vorta_attn_bwd_kmajor (a pure addition too:
-                                   a binding asks for the symbols and for vorta_attn_bwd_kmajor_args_size()) */
+                                   a binding asks for the symbols and for vorta_attn_bwd_kmajor_args_size())
+                                   and the deterministic backward, vorta_attn_bwd_dq / vorta_attn_bwd_dkv (two more symbols, on
+                                   the key-major argument block) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -225,6 +227,35 @@ typedef struct vorta_attn_bwd_kmajor_args {
 int vorta_attn_bwd_stats(const vorta_attn_bwd_kmajor_args* args, void* hip_stream);
 int vorta_attn_bwd_kmajor(const vorta_attn_bwd_kmajor_args* args, void* hip_stream);
 int vorta_attn_bwd_kmajor_args_size(void); /* (vorta_sizeof keeps its 17 indices: a library without these entry points lacks the symbol) */
+
+/*
+ * vorta_attn_bwd_dq + vorta_attn_bwd_dkv (ABI 9, a pure addition: no new struct, no new vorta_sizeof index; a binding asks for
+ * the two symbols) -- the SAME gradient as vorta_attn_bwd by a third, DETERMINISTIC algorithm: no float atomic anywhere and no
+ * protocol between workgroups.  Both take the argument block of the key-major backward, with bwd, stats, stats_stride_h and
+ * n_key_lists as described there, and both read the statistics vorta_attn_bwd_stats wrote for the SAME launch earlier on the
+ * same stream:
+ *   1. vorta_attn_bwd_stats, as above.
+ *   2. vorta_attn_bwd_dq (csrc/attn_bwd_dq.hip): query-major, the statistics pass's grid -- a workgroup owns 128 query
+ *      positions, sweeps the group's keys once and adds scale dQ to its dq rows with a plain read-add-write, one workgroup
+ *      per row as in vorta_attn_bwd.  It reads bwd.dq only: bwd.dk / bwd.dv are neither validated nor touched.
+ *   3. vorta_attn_bwd_dkv (csrc/attn_bwd_dkv.hip): the key-major sweep without its dQ half -- a workgroup owns 256 keys of
+ *      one (head slot, key list), keeps their dK and dV on chip over the list's queries and adds them to the dk / dv rows
+ *      with a plain read-add-write.  It issues ONE KERNEL LAUNCH PER KEY LIST -- n_key_lists launches with a table, the
+ *      number of groups without one -- on hip_stream, in list order; each has one workgroup per (head slot, 256-key block).
+ *      It reads bwd.dk and bwd.dv only: bwd.dq is neither validated nor touched.
+ * The buffers are ADDED to (the caller zeroes them); rows and heads the launch does not name, and query positions at or past
+ * q_valid_eff, receive nothing.
+ * PRECONDITION (of _dkv; every table this project builds meets it): the first n_kv_eff rows of any ONE key list are distinct,
+ * and head_list names distinct heads -- inside one launch every (head, key row) then has a single writer.  Rows that
+ * DIFFERENT key lists share (the overlapping windows of the sliding tile), and the launches of the mixture's experts into the
+ * same buffers, are summed in stream order.  _dq needs what vorta_attn_bwd needs: no dq row named by two positions.
+ * REPRODUCIBILITY: dq, dk and dv are bit-reproducible from run to run: no atomic in either kernel, one writer per row inside
+ * a launch with a fixed summation order of its own, and stream order between launches.
+ * Error codes as for vorta_attn_bwd_kmajor, except that _dq requires a valid dq only and _dkv a valid dk and dv only (looked
+ * at before anything is launched, also when n_heads == 0, which is VORTA_OK and launches nothing).
+ */
+int vorta_attn_bwd_dq(const vorta_attn_bwd_kmajor_args* args, void* hip_stream);
+int vorta_attn_bwd_dkv(const vorta_attn_bwd_kmajor_args* args, void* hip_stream);
 
 /*
  * fp8 (e4m3) path -- BASELINE.json configs[4] "fp8 MFMA QK^T/PV path".  The reference has no fp8 code: this path serves

@@ -204,6 +204,8 @@ SYMBOLS = {
     "vorta_attn_bwd_stats": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
     "vorta_attn_bwd_kmajor": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
     "vorta_attn_bwd_kmajor_args_size": (C.c_int, []),
+    "vorta_attn_bwd_dq": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
+    "vorta_attn_bwd_dkv": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
     "vorta_mix_experts_bwd": (C.c_int, [C.POINTER(MixBwdArgs), _vp]),
     "vorta_cast_grads": (C.c_int, [C.POINTER(CastArgs), _vp]),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
@@ -243,8 +245,8 @@ def lib():
         try:
             fn = getattr(h, name)
         except AttributeError:
-            # ABI 9 gained vorta_qk_norm_rope_bwd and the key-major backward without a new number: an older ABI-9 build
-            # (VORTA_HIP_LIB) lacks them
+            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward without a new number: an
+            # older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libvorta_hip.so")
-SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
+SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_bwd_dq.hip", "attn_bwd_dkv.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
            "sta_tables.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "permute.hip"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent fp32 adds of the softmax row sum into v_pk_add_f32 plus the
 # v_mov pairs to feed them -- more instructions on the VALU issue port that bounds the attention loop (+2 % without)
@@ -23,7 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # attn_bwd_kmajor.hip keeps 256 registers of dK / dV accumulators per lane: its other MFMA results (S, dP, dQ) must be free
 # to live in the ordinary registers, which the compiler's default (every MFMA result of such a kernel in an accumulator
 # register) does not allow -- it spills 227 registers without this option and none with it
-SOURCE_FLAGS = {"attn_bwd_kmajor.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# (attn_bwd_dkv.hip is that sweep without its dQ half: the same 256 accumulator registers, the same option)
+SOURCE_FLAGS = {"attn_bwd_kmajor.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                "attn_bwd_dkv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _newer(src, dst):

@@ -924,7 +924,9 @@ def _attn_bwd_args(who: str, q, k, v, o, d_o, dq, dk, dv, do_scale, kw) -> _C.At
             raise ValueError(f"{who}: do_scale is a 1-D view (one weight per head id) in the inputs' dtype")
         a.do_scale, a.do_scale_stride_h = do_scale.data_ptr(), do_scale.stride(0)
     if dq is not None:
-        a.dq, a.dk, a.dv = _f32_tensor(dq, q, "dq"), _f32_tensor(dk, k, "dk"), _f32_tensor(dv, v, "dv")
+        a.dq = _f32_tensor(dq, q, "dq")
+    if dk is not None or dv is not None:
+        a.dk, a.dv = _f32_tensor(dk, k, "dk"), _f32_tensor(dv, v, "dv")
     return a
 
 
@@ -982,6 +984,29 @@ def attn_bwd_key_major(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: tor
     a = _attn_bwd_args("attn_bwd_key_major", q, k, v, o, d_o, dq, dk, dv, do_scale, kw)
     ka = _kmajor_args("attn_bwd_key_major", a, stats, kw.get("n_key_lists", 0))
     _C.check(_C.lib().vorta_attn_bwd_kmajor(C.byref(ka), _stream()), "vorta_attn_bwd_kmajor")
+
+
+def attn_bwd_dq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, dq: torch.Tensor,
+                stats: torch.Tensor, *, do_scale: Optional[torch.Tensor] = None, **kw) -> None:
+    """vorta_attn_bwd_dq (include/vorta_hip.h): the dQ pass of the deterministic backward -- the dq of `attn_bwd`, ADDED to
+    the float32 dq, from the statistics `attn_bwd_stats` wrote for the SAME launch (same tensors, do_scale and keywords,
+    earlier on the same stream).  Query-major, one workgroup per dq row, no atomics: bit-reproducible.  dk / dv are not
+    touched (`attn_bwd_dkv` gives them)."""
+    a = _attn_bwd_args("attn_bwd_dq", q, k, v, o, d_o, dq, None, None, do_scale, kw)
+    ka = _kmajor_args("attn_bwd_dq", a, stats, kw.get("n_key_lists", 0))
+    _C.check(_C.lib().vorta_attn_bwd_dq(C.byref(ka), _stream()), "vorta_attn_bwd_dq")
+
+
+def attn_bwd_dkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, dk: torch.Tensor,
+                 dv: torch.Tensor, stats: torch.Tensor, *, do_scale: Optional[torch.Tensor] = None, **kw) -> None:
+    """vorta_attn_bwd_dkv (include/vorta_hip.h): the dK / dV pass of the deterministic backward -- the dk and dv of
+    `attn_bwd`, ADDED to the float32 dk / dv, from the statistics `attn_bwd_stats` wrote for the SAME launch.  One kernel
+    launch per key list, in list order; a workgroup keeps the dK / dV of 256 keys on chip and is the only writer of their
+    rows in its launch, no atomics: bit-reproducible, given that the rows of one key list are distinct and head_list names
+    distinct heads (true of every table this package builds).  dq is not touched (`attn_bwd_dq` gives it)."""
+    a = _attn_bwd_args("attn_bwd_dkv", q, k, v, o, d_o, None, dk, dv, do_scale, kw)
+    ka = _kmajor_args("attn_bwd_dkv", a, stats, kw.get("n_key_lists", 0))
+    _C.check(_C.lib().vorta_attn_bwd_dkv(C.byref(ka), _stream()), "vorta_attn_bwd_dkv")
 
 
 def mix_experts_bwd(xs, d_out: torch.Tensor) -> torch.Tensor:

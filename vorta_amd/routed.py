@@ -500,7 +500,7 @@ def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
     return out
 
 
-ATTENTION_BACKWARDS = ("query_major", "key_major")
+ATTENTION_BACKWARDS = ("query_major", "key_major", "deterministic")
 _attention_backward = None  # the process-wide default; None = not set: VORTA_ATTENTION_BACKWARD, else "query_major"
 
 
@@ -512,8 +512,10 @@ def _check_backward(name: str, where: str) -> str:
 
 def set_attention_backward(name: str) -> None:
     """the process-wide attention backward algorithm of the differentiable operators and processors: "query_major"
-    (ops.attn_bwd: dq bit-reproducible) or "key_major" (ops.attn_bwd_stats + ops.attn_bwd_key_major: a quarter of the atomic
-    bytes, nothing bit-reproducible).  Overrides the environment switch VORTA_ATTENTION_BACKWARD."""
+    (ops.attn_bwd: dq bit-reproducible), "key_major" (ops.attn_bwd_stats + ops.attn_bwd_key_major: a quarter of the atomic
+    bytes, nothing bit-reproducible) or "deterministic" (ops.attn_bwd_stats + ops.attn_bwd_dq + ops.attn_bwd_dkv: no atomics,
+    dq, dk and dv bit-reproducible).  Overrides the environment switch VORTA_ATTENTION_BACKWARD.  This switch is the only
+    selector: torch.use_deterministic_algorithms is not consulted."""
     global _attention_backward
     _attention_backward = _check_backward(name, "set_attention_backward")
 
@@ -530,10 +532,14 @@ def attention_backward(backward: Optional[str] = None) -> str:
 
 
 def _attn_bwd_by(algorithm: str, q, k, v, o, d_out, dq, dk, dv, do_scale=None, **launch) -> None:
-    """the gradient of one recorded launch by either algorithm"""
+    """the gradient of one recorded launch by one of ATTENTION_BACKWARDS"""
     if algorithm == "key_major":
         stats = ops.attn_bwd_stats(q, k, v, o, d_out, do_scale=do_scale, **launch)
         ops.attn_bwd_key_major(q, k, v, o, d_out, dq, dk, dv, stats, do_scale=do_scale, **launch)
+    elif algorithm == "deterministic":
+        stats = ops.attn_bwd_stats(q, k, v, o, d_out, do_scale=do_scale, **launch)
+        ops.attn_bwd_dq(q, k, v, o, d_out, dq, stats, do_scale=do_scale, **launch)
+        ops.attn_bwd_dkv(q, k, v, o, d_out, dk, dv, stats, do_scale=do_scale, **launch)
     else:
         ops.attn_bwd(q, k, v, o, d_out, dq, dk, dv, do_scale=do_scale, **launch)
 
@@ -541,7 +547,8 @@ def _attn_bwd_by(algorithm: str, q, k, v, o, d_out, dq, dk, dv, do_scale=None, *
 def _replay_backward(launches, d_out: torch.Tensor, dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor,
                      weight_of=None, algorithm: str = "query_major") -> None:
     """one backward per recorded forward launch, with the SAME dictionaries (forward and backward cannot disagree on a
-    table): ops.attn_bwd ("query_major"), or the statistics pass and then the key-major pass ("key_major");
+    table): ops.attn_bwd ("query_major"), the statistics pass and then the key-major pass ("key_major"), or the statistics
+    pass, the dQ pass and the dK / dV pass ("deterministic");
     `weight_of(launch, out)` = the per-head weight of the launch's output in the loss (None: 1)"""
     _check_backward(algorithm, "_replay_backward")
     for c in launches:
@@ -599,8 +606,10 @@ def soft_mixture_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.T
     the sliding-tile tables are constants of the backward (the reference ranks with argsort: no gradient flows through the
     selection there either, coreset_select.py:98-124).  dk / dv are not bit-reproducible (float atomics); dq and dscores are.
     `backward`: "query_major" (the above) or "key_major" (per launch ops.attn_bwd_stats, then ops.attn_bwd_key_major: dq is
-    a sum of float atomics too); None follows `set_attention_backward` / VORTA_ATTENTION_BACKWARD, read when the forward
-    runs.  The forward is the same either way.  q, k, v: contiguous (1,H,N,D), like the forward's."""
+    a sum of float atomics too) or "deterministic" (per launch ops.attn_bwd_stats, ops.attn_bwd_dq, ops.attn_bwd_dkv: no
+    atomics -- dq, dk, dv and dscores are all bit-reproducible, the launches meeting in the shared buffers in stream order);
+    None follows `set_attention_backward` / VORTA_ATTENTION_BACKWARD, read when the forward runs.  The forward is the same
+    whichever it is.  q, k, v: contiguous (1,H,N,D), like the forward's."""
     return _SoftMixture.apply(q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward)
 
 
@@ -634,7 +643,8 @@ def dense_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
                              backward: Optional[str] = None) -> torch.Tensor:
     """`dense_attention` (the teacher path, use_original_attn=True: hunyuan.py:167-176, wan.py:134-145) as a differentiable
     operator: the same launch forward, ops.attn_bwd + ops.cast_grads backward.  (B,H,Sq,D) x (B,H,Skv,D), contiguous.
-    `backward`: as for `soft_mixture_attention_autograd`."""
+    `backward`: "query_major", "key_major" or "deterministic" (bit-reproducible dq, dk, dv), as for
+    `soft_mixture_attention_autograd`."""
     return _Dense.apply(q, k, v, kv_valid, q_valid, scale, backward)
 
 
