@@ -3,8 +3,8 @@
 // instead of a first sweep of its own; vorta_attn_bwd_dkv (csrc/attn_bwd_dkv.hip) gives dk and dv.
 //
 // Query-major, no atomics: a workgroup (4 waves) owns 128 query positions of one (head slot, group) -- the statistics pass's
-// grid and decomposition -- and walks the group's key list once in 64-key blocks.  A wave forms, for its 32 queries and with
-// the key on the MFMA lane (csrc/attn_bwd_kmajor.h: the statistics pass forms the same numbers the same way),
+// grid and decomposition -- and walks the group's key list once in 64-key blocks (the frame is the statistics pass's: the
+// QUERY-BLOCK PIECES section of csrc/attn_bwd_kmajor.h).  A wave forms, for its 32 queries and with the key on the MFMA lane,
 //     S = Q . K^T, dP = dO_eff . V^T      (accumulator: 16 queries in a lane's registers, one key per lane and half)
 //     P = exp2(c s - lse2)                dS = P (dP - delta)
 // writes dS, 16 bits, as a [key][query] image of its own (64 keys x 32 queries; no other wave reads it, so no barrier serves
@@ -41,135 +41,55 @@ __global__ __launch_bounds__(KNT) void attn_bwd_dq_kernel(const KmParams kp) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub
   using V8 = typename MF<T>::v8;
   using V4 = typename MF<T>::v4;
-  constexpr int CH = (KVB * 16) / KNT;  // 16-byte chunks of one K / V tile per thread (4)
-  constexpr int ROWSTEP = KNT / 16;     // rows between a thread's consecutive chunks (16)
   const Params& p = kp.p;
 
   __shared__ __attribute__((aligned(16))) char smem[DQ_LDS];
 
-  // ---- work decomposition (the statistics pass's) ----
-  const int wg = live_order(p, blockIdx.x, gridDim.x, p.xcd_remap);
-  const int n_qb = p.n_groups * p.blocks_per_group;
-  const int qb = wg % n_qb;
-  const int y = wg / n_qb;
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  int grp, p0, pend;
-  if (p.q_block_table) {
-    const int32_t* t = p.q_block_table + 3 * (qb / kp.sub);
-    grp = t[0]; p0 = t[1] + (qb % kp.sub) * SQB; pend = t[2];
-  } else {
-    q_block_of(p, qb, SQB, grp, p0, pend);
-  }
+  int y, head, grp, p0, pend;
+  if (!q_block_work(kp, y, head, grp, p0, pend)) return;
   const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
   pend = min(pend, p.n_q);
   if (p0 >= pend || p0 >= q_valid) return;  // (workgroup-uniform) no position of this block takes a gradient
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r32 = lane & 31;
   const int hh = lane >> 5;
 
   const int n_kv = p.n_kv_dev ? max(1, min(*p.n_kv_dev, p.n_kv)) : p.n_kv;
   const int nblk = (n_kv + KVB - 1) / KVB;
   const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int lrow0 = tid >> 4;
-  const int lcc = tid & 15;
 
-  // ---- prologue: LDS images of Q and dO_eff ----
-  {
-    float w = 1.f;
-    if (kp.do_scale) w = (float)((const T*)kp.do_scale)[(int64_t)head * kp.do_scale_sh];
-    const char* qh = p.q + (int64_t)head * p.q_sh + lcc * 16;
-    const char* gh = kp.d_o + (int64_t)head * kp.do_sh + lcc * 16;
-    for (int i = 0; i < SQB / ROWSTEP; ++i) {
-      const int row = lrow0 + i * ROWSTEP;
-      const int pos = p0 + row;
-      const bool ok = pos < pend && pos < q_valid;
-      const int ldp = min(pos, pend - 1);
-      const int64_t r = q_rows ? (int64_t)q_rows[ldp] : (int64_t)(p.q_row_offset + ldp);
-      const int dst = tile_off(row, lcc * 8);
-      *(u32x4*)(smem + Q_OFF + dst) = *(const u32x4*)(qh + r * p.q_ss);
-      const V8 g0 = *(const V8*)(gh + r * kp.do_ss);
-      *(V8*)(smem + DO_OFF + dst) = do_eff_chunk<T>(kp, g0, gh, y, pos, w, ok);
-    }
-  }
+  load_q_images<T>(kp, smem, Q_OFF, DO_OFF, y, head, q_rows, p0, pend, q_valid);
   __syncthreads();
-
-  // ---- this lane's query row as the A operand: fragments of q and dO_eff ----
-  const int my_q = wave * 32 + r32;
   V8 qf[8], gf[8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-    qf[ks] = *(const V8*)(smem + Q_OFF + tile_off(my_q, (2 * ks + hh) * 8));
-    gf[ks] = *(const V8*)(smem + DO_OFF + tile_off(my_q, (2 * ks + hh) * 8));
-  }
+  q_frags<T>(smem, Q_OFF, DO_OFF, wave, qf, gf);
 
-  // ---- the statistics of this lane's 16 queries: register i of an accumulator = query (i & 3) + 8 (i >> 2) + 4 hh of the wave
+  // ---- the statistics of this lane's 16 queries: register i of an accumulator = query acc_row(i, hh) of the wave
   // (a position that takes no gradient: lse2 = 1e30, so that P = exp2(.. - 1e30) = 0) ----
   const float* st = kp.stats + (int64_t)y * kp.stats_sh;
   float lse2[16], delta[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int pos = p0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+    const int pos = p0 + wave * 32 + acc_row(i, hh);
     float2 sd = make_float2(1e30f, 0.f);
     if (pos < pend && pos < q_valid) sd = *(const float2*)(st + 2 * (int64_t)pos);
     lse2[i] = sd.x; delta[i] = sd.y;
   }
 
-  // ---- K / V loader (global -> registers one block ahead -> LDS) ----
   const int32_t* kv_rows =
       p.kv_rows ? p.kv_rows + (int64_t)y * p.kv_rows_sh + (int64_t)grp * p.kv_rows_sg : nullptr;
-  const char* kbase = p.k + (int64_t)head * p.k_sh + lcc * 16;
-  const char* vbase = p.v + (int64_t)head * p.v_sh + lcc * 16;
-  int t_wr[CH];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) t_wr[i] = tile_off(lrow0 + i * ROWSTEP, lcc * 8);
-  u32x4 kreg[CH], vreg[CH];
-  int64_t nrow[CH];
-#define FETCH_ROWS(blk_)                                                          \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    const int pos_ = min((blk_) * KVB + lrow0 + i_ * ROWSTEP, n_kv - 1);          \
-    nrow[i_] = kv_rows ? (int64_t)kv_rows[pos_] : (int64_t)(p.kv_row_offset + pos_); \
-  }
-#define ISSUE_KV()                                                                \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    kreg[i_] = *(const u32x4*)(kbase + nrow[i_] * p.k_ss);                        \
-    vreg[i_] = *(const u32x4*)(vbase + nrow[i_] * p.v_ss);                        \
-  }
-#define WRITE_KV()                                                                \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    *(u32x4*)(smem + K_OFF + t_wr[i_]) = kreg[i_];                                \
-    *(u32x4*)(smem + V_OFF + t_wr[i_]) = vreg[i_];                                \
-  }
-
-  // a key's fragments as the B operand: key row r32 (+32), 8 channels (row + 32 keeps row & 15: same offset + 32 rows)
+  KvLoader kv(p, kv_rows, head, n_kv);
   int k_rd[8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_rd[ks] = tile_off(r32, (2 * ks + hh) * 8);
-#define SCORES(d0_, d1_, off_, a_)                                                \
-  {                                                                               \
-    _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) { d0_[i_] = 0.f; d1_[i_] = 0.f; } \
-    _Pragma("unroll") for (int ks_ = 0; ks_ < 8; ++ks_) {                         \
-      const V8 b0_ = *(const V8*)(smem + (off_) + k_rd[ks_]);                     \
-      const V8 b1_ = *(const V8*)(smem + (off_) + k_rd[ks_] + 32 * ROWB);         \
-      d0_ = MF<T>::mfma(a_[ks_], b0_, d0_);                                       \
-      d1_ = MF<T>::mfma(a_[ks_], b1_, d1_);                                       \
-    }                                                                             \
-  }
+  frag_bases(k_rd);
 
-  // transposed reads (ds_read_b64_tr_b16): a lane addresses row k0 + 4 hh + (lane & 15) / 4, elements n0 + 16 (lane / 16 & 1)
-  // + 4 (lane & 3) of a row-major [k][n] image and receives, for n = n0 + r32, the four k = k0 + 4 hh + 0..3; two reads
-  // (k0, k0 + 8) fill the eight k slots of a lane -- the same k order on both operands of the dQ product
-  const int tr_row = 4 * hh + ((lane & 15) >> 2);
-  const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  // transposed reads (attn_bwd_kmajor.h tr_row): the same k order on both operands of the dQ product
   int ktr[2][4];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) ktr[h][dt] = K_OFF + tile_off(tr_row + 8 * h, 32 * dt + tr_col);
-  const int dtr = DS_OFF + (wave * KVB + tr_row) * DSS + tr_col * 2;
+    for (int dt = 0; dt < 4; ++dt) ktr[h][dt] = K_OFF + tile_off(tr_row() + 8 * h, 32 * dt + tr_col());
+  const int dtr = DS_OFF + (wave * KVB + tr_row()) * DSS + tr_col() * 2;
   // the [key][query] image of dS: this lane's key row, queries 4 hh + 0..3 of every group of eight
   char* const srow = smem + DS_OFF + (wave * KVB + r32) * DSS + hh * 8;
 
@@ -182,18 +102,18 @@ __global__ __launch_bounds__(KNT) void attn_bwd_dq_kernel(const KmParams kp) {
     for (int i = 0; i < 16; ++i) dq[dt][i] = 0.f;
 
   // ---- the key sweep ----
-  FETCH_ROWS(0);
-  ISSUE_KV();
+  kv.rows(0);
+  kv.issue();
   for (int blk = 0; blk < nblk; ++blk) {
-    WRITE_KV();
+    kv.write(smem, K_OFF, V_OFF);
     __syncthreads();
     if (blk + 1 < nblk) {
-      FETCH_ROWS(blk + 1);
-      ISSUE_KV();
+      kv.rows(blk + 1);
+      kv.issue();
     }
     f32x16 s0, s1, g0, g1;
-    SCORES(s0, s1, K_OFF, qf)
-    SCORES(g0, g1, V_OFF, gf)
+    scores<T>(smem, K_OFF, k_rd, qf, s0, s1);
+    scores<T>(smem, V_OFF, k_rd, gf, g0, g1);
     const bool dead0 = blk * KVB + r32 >= n_kv, dead1 = blk * KVB + 32 + r32 >= n_kv;  // (the tail of the last block)
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
@@ -231,16 +151,12 @@ __global__ __launch_bounds__(KNT) void attn_bwd_dq_kernel(const KmParams kp) {
     }
     __syncthreads();  // every wave is done with the K / V tiles
   }
-#undef FETCH_ROWS
-#undef ISSUE_KV
-#undef WRITE_KV
-#undef SCORES
 
   // ---- epilogue: dq[r(p)] += scale dQ (one writer per row) ----
   float* dqh = kp.dq + (int64_t)head * kp.dq_sh + r32;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int pos = p0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+    const int pos = p0 + wave * 32 + acc_row(i, hh);
     if (pos < pend && pos < q_valid) {
       const int64_t row = q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
       float* dst = dqh + row * kp.dq_ss;
@@ -263,11 +179,6 @@ extern "C" int vorta_attn_bwd_dq(const vorta_attn_bwd_kmajor_args* a, void* hip_
   if (!f32_rows_ok(a->bwd.dq)) return VORTA_EINVAL;  // (dk / dv are not looked at)
   const Params& p = kp.p;
   if (p.n_heads == 0) return VORTA_OK;
-  const int64_t total = (int64_t)p.wg_per_slot * p.n_heads;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (a->bwd.fwd.dtype == VORTA_BF16) hipLaunchKernelGGL(attn_bwd_dq_kernel<__bf16>, dim3((unsigned)total), dim3(KNT), 0, st, kp);
-  else hipLaunchKernelGGL(attn_bwd_dq_kernel<_Float16>, dim3((unsigned)total), dim3(KNT), 0, st, kp);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+  return launch_km(a, attn_bwd_dq_kernel<__bf16>, attn_bwd_dq_kernel<_Float16>, (int64_t)p.wg_per_slot * p.n_heads, hip_stream,
+                   kp);
 }

@@ -7,12 +7,10 @@
 //
 // One workgroup (4 waves) = one 256-key block of one (head slot, group) key list; wave w keeps keys 64 w .. 64 w + 63.  It
 // sweeps the query positions of THAT group in 32-row slices (with a q_block_table: every table row of the group, found by
-// scanning the table).  Per slice, with the key on the MFMA lane (csrc/attn_bwd_kmajor.h: the statistics pass forms the same
-// numbers the same way):
-//     S = Q . K^T, dP = dO_eff . V^T      (accumulator: 16 queries in a lane's registers, one key per lane and half)
-//     P = exp2(c s - lse2)                dS = P (dP - delta)
-//     dV[key][d] += P^T . dO_eff          dK[key][d] += dS^T . Q      (the accumulators ARE the A operands; Q and dO_eff come
-//                                                                      out of their LDS images through transposed reads)
+// scanning the table).  The sweep's pieces -- the K image, the V fragments, the slice loader, the S / dP / P / dS step and the
+// dV / dK products -- are the KEY-BLOCK SWEEP section of csrc/attn_bwd_kmajor.h, shared with csrc/attn_bwd_dkv.hip.  Per slice:
+//     S = Q . K^T, dP = dO_eff . V^T      P = exp2(c s - lse2)      dS = P (dP - delta)             (sweep_scores)
+//     dV[key][d] += P^T . dO_eff          dK[key][d] += dS^T . Q                                    (sweep_dkv)
 //     dS goes to LDS once, 16 bits, as a [key][query] image; after a barrier every wave takes 32 channels of
 //     dQ_slice[q][d] = sum over all 256 keys of dS[q][key] K[key][d]    (the sum over the four waves is the MFMA's own)
 //     and adds scale dQ_slice to the fp32 dq rows with vector float atomics (global_atomic_add_f32): one register of the
@@ -44,38 +42,11 @@ using namespace vorta_attn_km;
 
 constexpr int DSS = QSL * 2 + 16;  // bytes per key row of the dS image (the pad spreads the rows over the banks)
 // the small images first: every read below is ONE lane-constant base register plus an immediate (16 bits reach 64 KiB)
-constexpr int Q_OFF = 0;
-constexpr int DO_OFF = Q_OFF + QSL * ROWB;
-constexpr int DS_OFF = DO_OFF + QSL * ROWB;
+constexpr int DS_OFF = SL_DO + QSL * ROWB;     // (the slice buffer -- Q, dO_eff -- is at 0)
 constexpr int ST_OFF = DS_OFF + KMB * DSS;     // [32] (lse2, delta)
 constexpr int ROW_OFF = ST_OFF + QSL * 8;      // [2][32] int64 dq row of a slice's position, -1 = none (two slices in flight)
 constexpr int K_OFF = ROW_OFF + 2 * QSL * 8;
 constexpr int KM_LDS = K_OFF + KMB * ROWB;
-
-// The next 32-row slice of group grp below q_valid; r = -1 before the first call (r: the table row, or 0).  Table rows of one
-// group need not be contiguous or ordered.  Workgroup-uniform.
-__device__ __forceinline__ bool next_slice(const KmParams& kp, int grp, int q_valid, int& r, int& p0, int& end) {
-  const Params& p = kp.p;
-  if (r >= 0) {
-    p0 += QSL;
-    if (p0 < end) return true;
-  }
-  if (!p.q_block_table) {
-    if (r >= 0) return false;
-    r = 0;
-    p0 = grp * p.q_group_len;
-    end = min(min(p0 + p.q_group_len, p.n_q), q_valid);
-    return p0 < end;
-  }
-  for (++r; r < kp.n_tab_rows; ++r) {
-    const int32_t* t = p.q_block_table + 3 * r;
-    if (t[0] != grp) continue;
-    p0 = t[1];
-    end = min(min(t[2], p.n_q), q_valid);
-    if (p0 < end) return true;
-  }
-  return false;
-}
 
 template <typename T>
 __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp) {
@@ -99,13 +70,10 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
   int sl_r = -1, sl_p0 = 0, sl_end = 0;
   if (!next_slice(kp, grp, q_valid, sl_r, sl_p0, sl_end)) return;  // the group has no query below q_valid
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r32 = lane & 31;
   const int hh = lane >> 5;
-  const int lrow0 = tid >> 4;
-  const int lcc = tid & 15;
   const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
   const int32_t* kv_rows =
       p.kv_rows ? p.kv_rows + (int64_t)y * p.kv_rows_sh + (int64_t)grp * p.kv_rows_sg : nullptr;
@@ -113,96 +81,18 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
   float w = 1.f;
   if (kp.do_scale) w = (float)((const T*)kp.do_scale)[(int64_t)head * kp.do_scale_sh];
 
-  // ---- the K image of this key block (rows past n_kv repeat the last key: finite, and masked below) ----
-  {
-    const char* kbase = p.k + (int64_t)head * p.k_sh + lcc * 16;
-#pragma unroll 1
-    for (int b = 0; b < KMB / 64; ++b) {
-      u32x4 kreg[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int pos = min(kb * KMB + 64 * b + lrow0 + 16 * i, n_kv - 1);
-        const int64_t row = kv_rows ? (int64_t)kv_rows[pos] : (int64_t)(p.kv_row_offset + pos);
-        kreg[i] = *(const u32x4*)(kbase + row * p.k_ss);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *(u32x4*)(smem + K_OFF + tile_off(64 * b + lrow0 + 16 * i, lcc * 8)) = kreg[i];
-    }
-  }
-  // ---- this lane's two keys: fragments of v (B operand of dP) ----
-  const int key0 = wave * 64 + r32;  // row of the K image; the second key is 32 rows on
+  load_k_image(p, smem, K_OFF, kv_rows, head, kb, n_kv);
+  const int key0 = wave * 64 + r32;  // this lane's row of the K image; its second key is 32 rows on
   V8 vf[2][8];
-#pragma unroll
-  for (int kh = 0; kh < 2; ++kh) {
-    const int pos = min(kb * KMB + key0 + 32 * kh, n_kv - 1);
-    const int64_t row = kv_rows ? (int64_t)kv_rows[pos] : (int64_t)(p.kv_row_offset + pos);
-    const char* vr = p.v + (int64_t)head * p.v_sh + row * p.v_ss;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) vf[kh][ks] = *(const V8*)(vr + (2 * ks + hh) * 16);
-  }
+  load_v_frags<T>(p, kv_rows, head, kb * KMB + key0, n_kv, vf);
+  SliceLoader<T, true> ld(kp, q_rows, y, head, w);
 
-  // ---- slice loader: global -> registers one slice ahead -> LDS ----
-  const char* qh = p.q + (int64_t)head * p.q_sh + lcc * 16;
-  const char* gh = kp.d_o + (int64_t)head * kp.do_sh + lcc * 16;
-  const float* st = kp.stats + (int64_t)y * kp.stats_sh;
-  u32x4 qreg[2];
-  V8 greg[2];
-  float2 sreg;
-  int64_t rreg;
-#define ISSUE_SLICE(p0_, end_)                                                                   \
-  {                                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                           \
-      const int ldp_ = min((p0_) + lrow0 + 16 * i_, (end_) - 1);                                 \
-      const int64_t r_ = q_rows ? (int64_t)q_rows[ldp_] : (int64_t)(p.q_row_offset + ldp_);      \
-      qreg[i_] = *(const u32x4*)(qh + r_ * p.q_ss);                                              \
-      greg[i_] = *(const V8*)(gh + r_ * kp.do_ss);                                               \
-    }                                                                                            \
-    if (tid < QSL) {                                                                             \
-      const int pos_ = (p0_) + tid;                                                              \
-      sreg = make_float2(1e30f, 0.f); /* a position outside the slice: P = exp2(.. - 1e30) = 0 */ \
-      rreg = -1;                                                                                 \
-      if (pos_ < (end_)) {                                                                       \
-        sreg = *(const float2*)(st + 2 * (int64_t)pos_);                                         \
-        rreg = q_rows ? (int64_t)q_rows[pos_] : (int64_t)(p.q_row_offset + pos_);                \
-      }                                                                                          \
-    }                                                                                            \
-  }
-#define WRITE_SLICE(p0_, end_, par_)                                                             \
-  {                                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                           \
-      const int row_ = lrow0 + 16 * i_;                                                          \
-      const int pos_ = (p0_) + row_;                                                             \
-      const int dst_ = tile_off(row_, lcc * 8);                                                  \
-      *(u32x4*)(smem + Q_OFF + dst_) = qreg[i_];                                                 \
-      *(V8*)(smem + DO_OFF + dst_) = do_eff_chunk<T>(kp, greg[i_], gh, y, pos_, w, pos_ < (end_)); \
-    }                                                                                            \
-    if (tid < QSL) {                                                                             \
-      *(float2*)(smem + ST_OFF + tid * 8) = sreg;                                                \
-      *(int64_t*)(smem + ROW_OFF + (par_) * QSL * 8 + tid * 8) = rreg;                           \
-    }                                                                                            \
-  }
-
-  // transposed reads (ds_read_b64_tr_b16): a lane addresses row k0 + 4 hh + (lane & 15) / 4, elements n0 + 16 (lane / 16 & 1)
-  // + 4 (lane & 3) of a row-major [k][n] image and receives, for n = n0 + r32, the four k = k0 + 4 hh + 0..3; two reads
-  // (k0, k0 + 8) fill the eight k slots of a lane -- the order of an accumulator's registers (8 b + j: query 16 b + 4 hh +
-  // (j & 3) + 8 (j >> 2)), so an accumulator and such a pair of reads are the two operands of one product
-  const int tr_row = 4 * hh + ((lane & 15) >> 2);
-  const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const SweepBases lb(wave, K_OFF);
   const int d0 = 32 * wave;  // dQ: this wave's channels
-  // lane-constant LDS bases; everything else is an immediate (tile_off(row + 16 n, e) = tile_off(row, e) + 16 n ROWB)
-  int rd[8], krd[8], trd[2][4], ktr[2];
+  int ktr[2];                // transposed reads of the K image (attn_bwd_kmajor.h tr_row), as lane-constant as lb's
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-    rd[ks] = tile_off(r32, (2 * ks + hh) * 8);   // a query's (Q / dO_eff image) fragment ks
-    krd[ks] = K_OFF + wave * 64 * ROWB + rd[ks]; // this lane's first key (row key0: the same row & 15); the second is 32 rows on
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) trd[h][dt] = tile_off(tr_row + 8 * h, 32 * dt + tr_col);
-    ktr[h] = K_OFF + tile_off(tr_row + 8 * h, d0 + tr_col);
-  }
-  const int dtr = DS_OFF + tr_row * DSS + tr_col * 2;
+  for (int h = 0; h < 2; ++h) ktr[h] = K_OFF + tile_off(tr_row() + 8 * h, d0 + tr_col());
+  const int dtr = DS_OFF + tr_row() * DSS + tr_col() * 2;
   const int strd = ST_OFF + 4 * hh * 8;
 
   f32x16 dk[2][4], dv[2][4];  // [key half][32 channels]: rows = the half's keys, this lane's column = channel 32 dt + r32
@@ -213,8 +103,8 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
 #pragma unroll
       for (int i = 0; i < 16; ++i) { dk[kh][dt][i] = 0.f; dv[kh][dt][i] = 0.f; }
 
-  ISSUE_SLICE(sl_p0, sl_end)
-  WRITE_SLICE(sl_p0, sl_end, 0)
+  ld.issue(sl_p0, sl_end);
+  ld.write(smem, sl_p0, sl_end, 0, ST_OFF, ROW_OFF);
   float* dqh = kp.dq + (int64_t)head * kp.dq_sh + d0 + r32;
 
   bool have = true;
@@ -222,31 +112,13 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
     __syncthreads();  // this slice's images are in place (first turn: the K image too); the dS image is free
     int nx_r = sl_r, nx_p0 = sl_p0, nx_end = sl_end;
     const bool have_next = next_slice(kp, grp, q_valid, nx_r, nx_p0, nx_end);
-    if (have_next) ISSUE_SLICE(nx_p0, nx_end)
+    if (have_next) ld.issue(nx_p0, nx_end);
 
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
-      // S and dP of 32 queries x this wave's 32 keys of the half
-      f32x16 s, g;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { s[i] = 0.f; g[i] = 0.f; }
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const V8 aq = *(const V8*)(smem + rd[ks] + Q_OFF);
-        const V8 ag = *(const V8*)(smem + rd[ks] + DO_OFF);
-        const V8 bk = *(const V8*)(smem + krd[ks] + 32 * kh * ROWB);
-        s = MF<T>::mfma(aq, bk, s);
-        g = MF<T>::mfma(ag, vf[kh][ks], g);
-      }
       const bool dead = kb * KMB + key0 + 32 * kh >= n_kv;  // (the tail of the last key block)
       V8 pb[2], dsb[2];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float2 sd = *(const float2*)(smem + strd + ((i & 3) + 8 * (i >> 2)) * 8);
-        const float pv = dead ? 0.f : expo(s[i], c, sd.x);
-        pb[i >> 3][i & 7] = (T)pv;
-        dsb[i >> 3][i & 7] = (T)(pv * (g[i] - sd.y));
-      }
+      sweep_scores<T>(smem, smem, lb, kh, vf[kh], strd, dead, c, pb, dsb);
       // the [key][query] image of dS: register group rg holds queries 8 rg + 4 hh + 0..3 of this lane's key
       char* srow = smem + DS_OFF + (key0 + 32 * kh) * DSS + hh * 8;
 #pragma unroll
@@ -256,24 +128,10 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
         for (int j = 0; j < 4; ++j) x[j] = dsb[rg >> 1][4 * (rg & 1) + j];
         *(V4*)(srow + 16 * rg) = x;
       }
-      // dV[key][d] += P^T . dO_eff, dK[key][d] += dS^T . Q
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const int oa = trd[0][dt] + 16 * b * ROWB, oc = trd[1][dt] + 16 * b * ROWB;
-          const V4 lo = MF<T>::tr(smem + DO_OFF + oa), hi = MF<T>::tr(smem + DO_OFF + oc);
-          const V4 lo2 = MF<T>::tr(smem + Q_OFF + oa), hi2 = MF<T>::tr(smem + Q_OFF + oc);
-          V8 xg, xq;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { xg[j] = lo[j]; xg[4 + j] = hi[j]; xq[j] = lo2[j]; xq[4 + j] = hi2[j]; }
-          dv[kh][dt] = MF<T>::mfma(pb[b], xg, dv[kh][dt]);
-          dk[kh][dt] = MF<T>::mfma(dsb[b], xq, dk[kh][dt]);
-        }
-      }
+      sweep_dkv<T>(smem, lb, pb, dsb, dv[kh], dk[kh]);
     }
     __syncthreads();  // the dS image is complete; every wave is done with the Q / dO_eff images and the statistics
-    if (have_next) WRITE_SLICE(nx_p0, nx_end, (it + 1) & 1)
+    if (have_next) ld.write(smem, nx_p0, nx_end, 0, ST_OFF, ROW_OFF + ((it + 1) & 1) * QSL * 8);
 
     // dQ_slice[q][d0 + r32] over all 256 keys
     {
@@ -292,15 +150,13 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
       const char* rows = smem + ROW_OFF + (it & 1) * QSL * 8 + 4 * hh * 8;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int64_t row = *(const int64_t*)(rows + ((i & 3) + 8 * (i >> 2)) * 8);
+        const int64_t row = *(const int64_t*)(rows + acc_row(i, 0) * 8);
         if (row >= 0) unsafeAtomicAdd(dqh + row * kp.dq_ss, acc[i] * kp.scale);
       }
     }
     have = have_next;
     sl_r = nx_r; sl_p0 = nx_p0; sl_end = nx_end;
   }
-#undef ISSUE_SLICE
-#undef WRITE_SLICE
 
   // ---- epilogue: dk[row(key)] += scale dK, dv[row(key)] += dV ----
   float* dvh = kp.dv + (int64_t)head * kp.dv_sh + r32;
@@ -309,7 +165,7 @@ __global__ __launch_bounds__(KNT) void attn_bwd_kmajor_kernel(const KmParams kp)
   for (int kh = 0; kh < 2; ++kh) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int pos = kb * KMB + wave * 64 + 32 * kh + (i & 3) + 8 * (i >> 2) + 4 * hh;
+      const int pos = kb * KMB + wave * 64 + 32 * kh + acc_row(i, hh);
       if (pos < n_kv) {
         const int64_t row = kv_rows ? (int64_t)kv_rows[pos] : (int64_t)(p.kv_row_offset + pos);
 #pragma unroll
@@ -332,13 +188,8 @@ extern "C" int vorta_attn_bwd_kmajor(const vorta_attn_bwd_kmajor_args* a, void* 
   Params& p = kp.p;
   if (p.n_heads == 0) return VORTA_OK;
   p.wg_per_slot = kp.n_lists * kp.n_kblocks;  // this kernel's workgroups per head slot (live_order)
-  const int64_t total = (int64_t)p.wg_per_slot * p.n_heads;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (a->bwd.fwd.dtype == VORTA_BF16) hipLaunchKernelGGL(attn_bwd_kmajor_kernel<__bf16>, dim3((unsigned)total), dim3(KNT), 0, st, kp);
-  else hipLaunchKernelGGL(attn_bwd_kmajor_kernel<_Float16>, dim3((unsigned)total), dim3(KNT), 0, st, kp);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+  return launch_km(a, attn_bwd_kmajor_kernel<__bf16>, attn_bwd_kmajor_kernel<_Float16>, (int64_t)p.wg_per_slot * p.n_heads,
+                   hip_stream, kp);
 }
 
 extern "C" int vorta_attn_bwd_kmajor_args_size(void) { return (int)sizeof(vorta_attn_bwd_kmajor_args); }

@@ -4,7 +4,9 @@
 // the MFMA lane as in the key-major pass (csrc/attn_bwd_kmajor.h says why the two must agree).
 //
 // Query-major, no atomics: a workgroup (4 waves) owns 128 query positions of one (head slot, group) -- the decomposition of
-// vorta_attn_bwd -- and walks the group's key list once in 64-key blocks.  A wave forms, for its 32 queries,
+// vorta_attn_bwd -- and walks the group's key list once in 64-key blocks.  The frame -- decomposition, Q / dO_eff prologue,
+// K / V loader, scores() -- is the QUERY-BLOCK PIECES section of csrc/attn_bwd_kmajor.h, shared with csrc/attn_bwd_dq.hip.  A
+// wave forms, for its 32 queries,
 //     S = Q . K^T and dP = dO_eff . V^T        (accumulator: 16 queries in a lane's registers, ONE key per lane and half),
 // and every lane runs the online softmax of ITS key stripe (keys lane, lane + 32, lane + 64, ... of the list) for its 16
 // queries: running maximum m, l = sum exp2(c (s - m)), d = sum exp2(c (s - m)) dP.  The 32 stripes of a query are merged once,
@@ -44,31 +46,16 @@ template <typename T>
 __global__ __launch_bounds__(KNT) void attn_bwd_stats_kernel(const KmParams kp) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub
   using V8 = typename MF<T>::v8;
-  constexpr int CH = (KVB * 16) / KNT;  // 16-byte chunks of one K / V tile per thread (4)
-  constexpr int ROWSTEP = KNT / 16;     // rows between a thread's consecutive chunks (16)
   const Params& p = kp.p;
 
   __shared__ __attribute__((aligned(16))) char smem[STATS_LDS];
 
-  // ---- work decomposition (vorta_attn_bwd's) ----
-  const int wg = live_order(p, blockIdx.x, gridDim.x, p.xcd_remap);
-  const int n_qb = p.n_groups * p.blocks_per_group;
-  const int qb = wg % n_qb;
-  const int y = wg / n_qb;
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  int grp, p0, pend;
-  if (p.q_block_table) {
-    const int32_t* t = p.q_block_table + 3 * (qb / kp.sub);
-    grp = t[0]; p0 = t[1] + (qb % kp.sub) * SQB; pend = t[2];
-  } else {
-    q_block_of(p, qb, SQB, grp, p0, pend);
-  }
+  int y, head, grp, p0, pend;
+  if (!q_block_work(kp, y, head, grp, p0, pend)) return;
   if (p0 >= pend) return;  // (workgroup-uniform)
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r32 = lane & 31;
   const int hh = lane >> 5;
 
@@ -76,97 +63,36 @@ __global__ __launch_bounds__(KNT) void attn_bwd_stats_kernel(const KmParams kp) 
   const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
   const int nblk = (n_kv + KVB - 1) / KVB;
   const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int lrow0 = tid >> 4;
-  const int lcc = tid & 15;
 
-  // ---- prologue: LDS images of Q and dO_eff ----
-  {
-    float w = 1.f;
-    if (kp.do_scale) w = (float)((const T*)kp.do_scale)[(int64_t)head * kp.do_scale_sh];
-    const char* qh = p.q + (int64_t)head * p.q_sh + lcc * 16;
-    const char* gh = kp.d_o + (int64_t)head * kp.do_sh + lcc * 16;
-    for (int i = 0; i < SQB / ROWSTEP; ++i) {
-      const int row = lrow0 + i * ROWSTEP;
-      const int pos = p0 + row;
-      const bool ok = pos < pend && pos < q_valid;
-      const int ldp = min(pos, pend - 1);
-      const int64_t r = q_rows ? (int64_t)q_rows[ldp] : (int64_t)(p.q_row_offset + ldp);
-      const int dst = tile_off(row, lcc * 8);
-      *(u32x4*)(smem + Q_OFF + dst) = *(const u32x4*)(qh + r * p.q_ss);
-      const V8 g0 = *(const V8*)(gh + r * kp.do_ss);
-      *(V8*)(smem + DO_OFF + dst) = do_eff_chunk<T>(kp, g0, gh, y, pos, w, ok);
-    }
-  }
+  load_q_images<T>(kp, smem, Q_OFF, DO_OFF, y, head, q_rows, p0, pend, q_valid);
   __syncthreads();
-
-  // ---- this lane's query row as the A operand: fragments of q and dO_eff ----
-  const int my_q = wave * 32 + r32;
   V8 qf[8], gf[8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-    qf[ks] = *(const V8*)(smem + Q_OFF + tile_off(my_q, (2 * ks + hh) * 8));
-    gf[ks] = *(const V8*)(smem + DO_OFF + tile_off(my_q, (2 * ks + hh) * 8));
-  }
+  q_frags<T>(smem, Q_OFF, DO_OFF, wave, qf, gf);
 
-  // ---- K / V loader (global -> registers one block ahead -> LDS) ----
   const int32_t* kv_rows =
       p.kv_rows ? p.kv_rows + (int64_t)y * p.kv_rows_sh + (int64_t)grp * p.kv_rows_sg : nullptr;
-  const char* kbase = p.k + (int64_t)head * p.k_sh + lcc * 16;
-  const char* vbase = p.v + (int64_t)head * p.v_sh + lcc * 16;
-  int t_wr[CH];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) t_wr[i] = tile_off(lrow0 + i * ROWSTEP, lcc * 8);
-  u32x4 kreg[CH], vreg[CH];
-  int64_t nrow[CH];
-#define FETCH_ROWS(blk_)                                                          \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    const int pos_ = min((blk_) * KVB + lrow0 + i_ * ROWSTEP, n_kv - 1);          \
-    nrow[i_] = kv_rows ? (int64_t)kv_rows[pos_] : (int64_t)(p.kv_row_offset + pos_); \
-  }
-#define ISSUE_KV()                                                                \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    kreg[i_] = *(const u32x4*)(kbase + nrow[i_] * p.k_ss);                        \
-    vreg[i_] = *(const u32x4*)(vbase + nrow[i_] * p.v_ss);                        \
-  }
-#define WRITE_KV()                                                                \
-  _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) {                             \
-    *(u32x4*)(smem + K_OFF + t_wr[i_]) = kreg[i_];                                \
-    *(u32x4*)(smem + V_OFF + t_wr[i_]) = vreg[i_];                                \
-  }
-
-  // a key's fragments as the B operand: key row r32 (+32), 8 channels (row + 32 keeps row & 15: same offset + 32 rows)
+  KvLoader kv(p, kv_rows, head, n_kv);
   int k_rd[8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_rd[ks] = tile_off(r32, (2 * ks + hh) * 8);
-#define SCORES(d0_, d1_, off_, a_)                                                \
-  {                                                                               \
-    _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) { d0_[i_] = 0.f; d1_[i_] = 0.f; } \
-    _Pragma("unroll") for (int ks_ = 0; ks_ < 8; ++ks_) {                         \
-      const V8 b0_ = *(const V8*)(smem + (off_) + k_rd[ks_]);                     \
-      const V8 b1_ = *(const V8*)(smem + (off_) + k_rd[ks_] + 32 * ROWB);         \
-      d0_ = MF<T>::mfma(a_[ks_], b0_, d0_);                                       \
-      d1_ = MF<T>::mfma(a_[ks_], b1_, d1_);                                       \
-    }                                                                             \
-  }
+  frag_bases(k_rd);
 
   const float c = p.scale_log2;
 
-  // ---- the key sweep: register i of an accumulator = query (i & 3) + 8 (i >> 2) + 4 hh of the wave, this lane's key ----
+  // ---- the key sweep: register i of an accumulator = query acc_row(i, hh) of the wave, this lane's key ----
   float m_run[16], l_run[16], d_run[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) { m_run[i] = -1e30f; l_run[i] = 0.f; d_run[i] = 0.f; }
-  FETCH_ROWS(0);
-  ISSUE_KV();
+  kv.rows(0);
+  kv.issue();
   for (int blk = 0; blk < nblk; ++blk) {
-    WRITE_KV();
+    kv.write(smem, K_OFF, V_OFF);
     __syncthreads();
     if (blk + 1 < nblk) {
-      FETCH_ROWS(blk + 1);
-      ISSUE_KV();
+      kv.rows(blk + 1);
+      kv.issue();
     }
     f32x16 s0, s1, g0, g1;
-    SCORES(s0, s1, K_OFF, qf)
-    SCORES(g0, g1, V_OFF, gf)
+    scores<T>(smem, K_OFF, k_rd, qf, s0, s1);
+    scores<T>(smem, V_OFF, k_rd, gf, g0, g1);
     const bool dead0 = blk * KVB + r32 >= n_kv, dead1 = blk * KVB + 32 + r32 >= n_kv;  // (the tail of the last block)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -181,10 +107,6 @@ __global__ __launch_bounds__(KNT) void attn_bwd_stats_kernel(const KmParams kp) 
     }
     __syncthreads();
   }
-#undef FETCH_ROWS
-#undef ISSUE_KV
-#undef WRITE_KV
-#undef SCORES
 
   // ---- merge the 32 key stripes of every query (the lanes of one half), write (lse2, delta) ----
   float* st = kp.stats + (int64_t)y * kp.stats_sh;
@@ -197,7 +119,7 @@ __global__ __launch_bounds__(KNT) void attn_bwd_stats_kernel(const KmParams kp) 
     const bool some = l_tot > 0.f;
     const float lse2 = rounded_mul(m_all, c) + (some ? __builtin_amdgcn_logf(l_tot) : 0.f);
     const float delta = d_tot * (some ? 1.f / l_tot : 0.f);
-    const int pos = p0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+    const int pos = p0 + wave * 32 + acc_row(i, hh);
     if (r32 == i && pos < pend) *(float2*)(st + 2 * (int64_t)pos) = make_float2(lse2, delta);
   }
 #endif
@@ -211,11 +133,6 @@ extern "C" int vorta_attn_bwd_stats(const vorta_attn_bwd_kmajor_args* a, void* h
   if (rc != VORTA_OK) return rc;
   const Params& p = kp.p;
   if (p.n_heads == 0) return VORTA_OK;
-  const int64_t total = (int64_t)p.wg_per_slot * p.n_heads;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (a->bwd.fwd.dtype == VORTA_BF16) hipLaunchKernelGGL(attn_bwd_stats_kernel<__bf16>, dim3((unsigned)total), dim3(KNT), 0, st, kp);
-  else hipLaunchKernelGGL(attn_bwd_stats_kernel<_Float16>, dim3((unsigned)total), dim3(KNT), 0, st, kp);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+  return launch_km(a, attn_bwd_stats_kernel<__bf16>, attn_bwd_stats_kernel<_Float16>, (int64_t)p.wg_per_slot * p.n_heads,
+                   hip_stream, kp);
 }
