@@ -15,7 +15,8 @@ def set_attention_backward(name: str) -> None:
     """"query_major" (the default: vorta_attn_bwd, dq bit-reproducible), "key_major" (a softmax-statistics pass, then a
     kernel that keeps dK / dV on chip and sums only dQ across workgroups) or "deterministic" (the statistics pass, a dQ pass
     and a dK / dV pass with one writer per row and no atomics: dq, dk and dv bit-reproducible) for the differentiable
-    operators and processors.  Also: VORTA_ATTENTION_BACKWARD in the environment (vorta_amd/routed.py).  This switch is
-    the only selector; torch.use_deterministic_algorithms does not change it."""
+    operators and processors, on one GPU and under sequence parallelism (there per rank: a sum across ranks is the training
+    loop's).  Also: VORTA_ATTENTION_BACKWARD in the environment (vorta_amd/routed.py).  This switch is the only selector;
+    torch.use_deterministic_algorithms does not change it."""
     from .routed import set_attention_backward as _set
     _set(name)

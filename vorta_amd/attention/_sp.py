@@ -222,6 +222,8 @@ def sp_wan_dense(proc, attn, q, k, v, enc_img, is_cross_attn: bool):
 # experts), so the heads are placed in their natural order: H / P per rank, or -- where P does not divide H -- one more on the
 # first H % P ranks (UlyssesLayout(counts=...)).  VORTA_SP_PLACEMENT, VORTA_SP_GROUPS, VORTA_SP_KV_SPLITS and the precision
 # switch do not apply: one slot group, one key split, the dtype of q, k, v -- what the single-GPU training forward pins.
+# The attention backward is NOT pinned: `backward=` / routed.set_attention_backward / VORTA_ATTENTION_BACKWARD choose among the
+# three algorithms as on one GPU (the statistics-based kernels take the receive layout as it is).
 def _mixture_placement(H: int, P: int):
     if H < P:
         raise ValueError(f"{H} heads cannot cover {P} sequence-parallel ranks")
@@ -262,8 +264,10 @@ class _RecvSoftMixture(torch.autograd.Function):
     """routed.`_SoftMixture` on receive buffers: q, k, v in, the mixed output out, all (rows_total, D) of one layout"""
 
     @staticmethod
-    def forward(ctx, qb, kb, vb, scores, lay, geom, model, T, te, scale):
+    def forward(ctx, qb, kb, vb, scores, lay, geom, model, T, te, scale, backward=None):
+        from ..routed import attention_backward
         from ..ulysses.autograd import new_recv_buffer
+        ctx.algorithm = attention_backward(backward)  # read when the forward runs, as routed._SoftMixture reads it
         ebufs = [new_recv_buffer(lay) for _ in range(3)]
         ob = new_recv_buffer(lay)
         launches: list = []
@@ -284,15 +288,15 @@ class _RecvSoftMixture(torch.autograd.Function):
         ptrs = [b.data_ptr() for b in ebufs]
         # float32 accumulators laid out like the receive buffers: a launch adds through the same row tables and head stride
         acc = [torch.zeros((lay.rows_total, lay.D), dtype=torch.float32, device=qb.device) for _ in range(3)]
-        # (the query-major backward whatever routed.set_attention_backward / VORTA_ATTENTION_BACKWARD say: pinned like the
-        # other choices of this mode)
+        # (the algorithm the forward resolved; the statistics-based kernels take the same row tables and head stride -- what
+        # "deterministic" needs of this layout, one writer per accumulator row inside a launch: DESIGN.md 6.8)
         _replay_backward(ctx.launches, hv(g), hv(acc[0]), hv(acc[1]), hv(acc[2]),
-                         lambda _, o: sc[:, ptrs.index(o.data_ptr())], algorithm="query_major")
+                         lambda _, o: sc[:, ptrs.index(o.data_ptr())], algorithm=ctx.algorithm)
         grads = [torch.empty_like(qb) for _ in range(3)]
         ops.cast_grads([_flat(lay, a) for a in acc], [_flat(lay, x) for x in grads])
         d_sc = torch.zeros_like(scores)
         d_sc[0] = dsc.to(scores.dtype)
-        return grads[0], grads[1], grads[2], d_sc, None, None, None, None, None, None
+        return grads[0], grads[1], grads[2], d_sc, None, None, None, None, None, None, None
 
 
 def sp_soft_mixture_attention(q, k, v, T: int, routing_score: torch.Tensor, *, model: str, text_valid: int = 0,
@@ -318,16 +322,25 @@ def sp_soft_mixture_attention(q, k, v, T: int, routing_score: torch.Tensor, *, m
 
 def sp_soft_mixture_attention_autograd(q, k, v, T: int, routing_score: torch.Tensor, *, model: str, text_valid: int = 0,
                                        lowres_group_info=None, window_size=(3, 3, 3), tile_size=(6, 8, 8),
-                                       latent_shape=None, scale: Optional[float] = None) -> torch.Tensor:
+                                       latent_shape=None, scale: Optional[float] = None,
+                                       backward: Optional[str] = None) -> torch.Tensor:
     """`sp_soft_mixture_attention` as a differentiable operator (`routed.soft_mixture_attention_autograd` on the local heads
     between a differentiable exchange, ulysses/autograd.py).  The backward exchanges d_out to head shards, takes the score
-    gradients (ops.mix_experts_bwd), replays the recorded launches through ops.attn_bwd into float32 buffers laid out like
-    the receive buffers, rounds once (ops.cast_grads) and sends dq, dk, dv back in one exchange.  Text rows of dq, dk, dv and
+    gradients (ops.mix_experts_bwd), replays the recorded launches into float32 buffers laid out like the receive buffers,
+    rounds once (ops.cast_grads) and sends dq, dk, dv back in one exchange.  Text rows of dq, dk, dv and
     d routing_score are non-zero for this rank's heads only: their sum over the ranks is the single-process gradient.
-    Every buffer an autograd node keeps is allocated by this call (the next layer overwrites the shared ones)."""
+    Every buffer an autograd node keeps is allocated by this call (the next layer overwrites the shared ones).
+    `backward`: "query_major" (ops.attn_bwd), "key_major" (ops.attn_bwd_stats + ops.attn_bwd_key_major) or "deterministic"
+    (ops.attn_bwd_stats + ops.attn_bwd_dq + ops.attn_bwd_dkv: no float atomic -- on every rank dq, dk, dv and the score
+    gradients repeat bit for bit; a sum ACROSS ranks, the training loop's all-reduce of text-row and score
+    gradients, is outside that claim), as for `routed.soft_mixture_attention_autograd`; None follows
+    `routed.set_attention_backward` / VORTA_ATTENTION_BACKWARD, else "query_major".  It is resolved when the forward runs,
+    and an unknown name is refused before a layout is built or a collective runs.  The forward is the same whichever it is."""
+    from ..routed import attention_backward
     from ..ulysses.autograd import gather_heads_autograd, scatter_heads_autograd
+    algorithm = attention_backward(backward)
     lay, order, geom, (h0, h1) = _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape)
     qb, kb, vb = scatter_heads_autograd(lay, [q[0], k[0], v[0]], order)
     te = text_valid if model == "hunyuan" else 0
-    ob = _RecvSoftMixture.apply(qb, kb, vb, routing_score[:1, h0:h1], lay, geom, model, T, te, scale)
+    ob = _RecvSoftMixture.apply(qb, kb, vb, routing_score[:1, h0:h1], lay, geom, model, T, te, scale, algorithm)
     return gather_heads_autograd(lay, ob, order, token_major=True)[None]

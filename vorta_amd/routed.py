@@ -515,7 +515,10 @@ def set_attention_backward(name: str) -> None:
     (ops.attn_bwd: dq bit-reproducible), "key_major" (ops.attn_bwd_stats + ops.attn_bwd_key_major: a quarter of the atomic
     bytes, nothing bit-reproducible) or "deterministic" (ops.attn_bwd_stats + ops.attn_bwd_dq + ops.attn_bwd_dkv: no atomics,
     dq, dk and dv bit-reproducible).  Overrides the environment switch VORTA_ATTENTION_BACKWARD.  This switch is the only
-    selector: torch.use_deterministic_algorithms is not consulted."""
+    selector: torch.use_deterministic_algorithms is not consulted.  It holds on one GPU and under sequence parallelism alike
+    (`sp_soft_mixture_attention_autograd`, the Train processors' sequence-parallel grad mode): an operator reads it when its
+    forward runs.  Under sequence parallelism "deterministic" makes every RANK's gradients repeat bit for bit; what a training
+    loop sums across ranks afterwards (text-row and score gradients) is that loop's own order."""
     global _attention_backward
     _attention_backward = _check_backward(name, "set_attention_backward")
 
@@ -744,6 +747,7 @@ def sp_soft_mixture_attention(q, k, v, T, routing_score, **kw) -> torch.Tensor:
 
 
 def sp_soft_mixture_attention_autograd(q, k, v, T, routing_score, **kw) -> torch.Tensor:
-    """`soft_mixture_attention_autograd` under sequence parallelism (differentiable exchange): attention/_sp.py"""
+    """`soft_mixture_attention_autograd` under sequence parallelism (differentiable exchange): attention/_sp.py; `backward=`
+    as there (None: `set_attention_backward` / VORTA_ATTENTION_BACKWARD, read when the forward runs)"""
     from .attention._sp import sp_soft_mixture_attention_autograd as fn
     return fn(q, k, v, T, routing_score, **kw)
