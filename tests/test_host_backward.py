@@ -72,6 +72,45 @@ def test_backward_argument_validation_happens_before_any_launch():
     assert lib.vorta_cast_grads(ctypes.byref(c), None) == _C.VORTA_EINVAL
 
 
+# what each of the five attention-backward entry points looks at besides q, k, v, o (the statistics pass writes no gradient;
+# the two deterministic passes each look at their own buffers only)
+_LOOKS_AT = {"vorta_attn_bwd": ("d_o", "dq", "dk", "dv"), "vorta_attn_bwd_stats": ("d_o",),
+             "vorta_attn_bwd_kmajor": ("d_o", "dq", "dk", "dv"), "vorta_attn_bwd_dq": ("d_o", "dq"),
+             "vorta_attn_bwd_dkv": ("d_o", "dk", "dv")}
+_DEFECTS = ("pointer off 16 bytes", "stride_s no multiple", "stride_h no multiple", "stride_s under 128")
+# asserted already: here above, in tests/test_host_backward_key_major.py and in tests/test_host_backward_deterministic.py
+_ALREADY = {(e, "d_o", "stride_s no multiple") for e in _LOOKS_AT} | {
+    ("vorta_attn_bwd", "dk", "pointer off 16 bytes"), ("vorta_attn_bwd_kmajor", "dk", "pointer off 16 bytes"),
+    ("vorta_attn_bwd_dq", "dq", "pointer off 16 bytes"), ("vorta_attn_bwd_dkv", "dk", "pointer off 16 bytes"),
+    ("vorta_attn_bwd_dkv", "dv", "pointer off 16 bytes")}
+
+
+@pytest.mark.parametrize("entry,operand,defect", [(e, o, d) for e, ops in _LOOKS_AT.items() for o in ops for d in _DEFECTS
+                                                  if (e, o, d) not in _ALREADY])
+def test_stride_and_alignment_refusals(entry, operand, defect):
+    """d_o (16-bit: 8 elements per 16 bytes) and dq / dk / dv (float: 4) are read and written 16 bytes at a time, 128 channels
+    a row: a pointer or a stride that breaks that is refused before any launch (the fake addresses are never dereferenced)"""
+    from vorta_amd import _C
+    from test_host_backward_key_major import _valid_args
+    if entry == "vorta_attn_bwd":
+        a = _valid_bwd_args()
+        bwd = a
+    else:
+        a = _valid_args()
+        bwd = a.bwd
+    t = getattr(bwd, operand)
+    per16 = 8 if operand == "d_o" else 4  # elements in 16 bytes
+    if defect == "pointer off 16 bytes":
+        t.ptr = 0x10000 + 8
+    elif defect == "stride_s no multiple":
+        t.stride_s = 128 + per16 // 2
+    elif defect == "stride_h no multiple":
+        t.stride_h = 64 * 128 + per16 // 2
+    else:
+        t.stride_s = 128 - per16  # (still whole 16-byte units: only the row length is wrong)
+    assert getattr(_C.lib(), entry)(ctypes.byref(a), None) == _C.VORTA_EINVAL
+
+
 def test_python_surface():
     from vorta_amd import ops, routed
     import inspect
