@@ -273,12 +273,13 @@ class _RecvSoftMixture(torch.autograd.Function):
         launches: list = []
         _recv_mixture_forward(lay, geom, qb, kb, vb, scores, ebufs, ob, model, T, te, scale, record=launches)
         ctx.save_for_backward(qb, kb, vb, scores, *ebufs)
-        ctx.launches, ctx.lay = launches, lay
+        from ..routed import _unbind_launches
+        ctx.launches, ctx.lay = _unbind_launches(launches, ebufs), lay  # (a head view starts where its buffer starts)
         return ob
 
     @staticmethod
     def backward(ctx, d_ob):
-        from ..routed import _replay_backward
+        from ..routed import _bind_launches, _replay_backward
         qb, kb, vb, scores, *ebufs = ctx.saved_tensors
         lay = ctx.lay
         hv = lay.head_view
@@ -290,7 +291,8 @@ class _RecvSoftMixture(torch.autograd.Function):
         acc = [torch.zeros((lay.rows_total, lay.D), dtype=torch.float32, device=qb.device) for _ in range(3)]
         # (the algorithm the forward resolved; the statistics-based kernels take the same row tables and head stride -- what
         # "deterministic" needs of this layout, one writer per accumulator row inside a launch: DESIGN.md 6.8)
-        _replay_backward(ctx.launches, hv(g), hv(acc[0]), hv(acc[1]), hv(acc[2]),
+        launches = _bind_launches(ctx.launches, hv(qb), hv(kb), hv(vb), [hv(b) for b in ebufs])
+        _replay_backward(launches, hv(g), hv(acc[0]), hv(acc[1]), hv(acc[2]),
                          lambda _, o: sc[:, ptrs.index(o.data_ptr())], algorithm=ctx.algorithm)
         grads = [torch.empty_like(qb) for _ in range(3)]
         ops.cast_grads([_flat(lay, a) for a in acc], [_flat(lay, x) for x in grads])

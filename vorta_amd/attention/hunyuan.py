@@ -71,7 +71,9 @@ def _linear_into(lin: torch.nn.Linear, x2d: torch.Tensor, dst: torch.Tensor) -> 
         torch.mm(x2d, lin.weight.t(), out=dst)
 
 
-def _joint_projectable(x: torch.Tensor, e: torch.Tensor, lins) -> bool:
+def _joint_projectable(x: torch.Tensor, e: torch.Tensor, lins, grad: bool = False) -> bool:
+    """grad=True: would the inference call of these modules on these inputs take the joint projection?  (asked by the
+    training forward, which cannot use `out=` but projects the same row ranges, for the same bits)"""
     if not JOINT_PROJECTION or x.shape[0] != 1 or not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float16):
         return False
     if e.dtype != x.dtype or not all(type(m) is torch.nn.Linear and m.weight.dtype == x.dtype for m in lins):
@@ -81,8 +83,8 @@ def _joint_projectable(x: torch.Tensor, e: torch.Tensor, lins) -> bool:
     if any(m.weight.device != x.device or hasattr(m, "_hf_hook") or m._forward_hooks or m._forward_pre_hooks for m in lins):
         return False
     # `out=` is an inference-only form: autograd refuses it as soon as an argument requires grad
-    return not (torch.is_grad_enabled() and (x.requires_grad or e.requires_grad or
-                                             any(m.weight.requires_grad for m in lins)))
+    return grad or not (torch.is_grad_enabled() and (x.requires_grad or e.requires_grad or
+                                                     any(m.weight.requires_grad for m in lins)))
 
 
 def _valid_keys(attention_mask: torch.Tensor) -> torch.Tensor:
@@ -137,11 +139,17 @@ class HunyuanVideoFlashAttnProcessor:
         joint = None if grad else self._project_joint(attn, hidden_states, encoder_hidden_states, rope, single_stream)
         if joint is not None:
             return (*joint, T)
-        if single_stream:
-            hidden_states = torch.cat([hidden_states, encoder_hidden_states], dim=1)
-        q = attn.to_q(hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
-        k = attn.to_k(hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
-        v = attn.to_v(hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
+        if single_stream and grad and self._joint_applies(attn, hidden_states, encoder_hidden_states, True, grad=True):
+            # the inference call projects the video and the text rows in a GEMM each (_project_joint); one GEMM over the
+            # concatenated rows rounds differently (seen in fp16).  The training forward gives the inference bits.
+            q, k, v = (torch.cat([lin(hidden_states), lin(encoder_hidden_states)], dim=1).unflatten(2, (attn.heads, -1))
+                       .transpose(1, 2) for lin in (attn.to_q, attn.to_k, attn.to_v))
+        else:
+            if single_stream:
+                hidden_states = torch.cat([hidden_states, encoder_hidden_states], dim=1)
+            q = attn.to_q(hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
+            k = attn.to_k(hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
+            v = attn.to_v(hidden_states).unflatten(2, (attn.heads, -1)).transpose(1, 2)
         n_video = q.shape[2] - (T if single_stream else 0)
         if q.shape[0] == 1 and _fusable_norm(attn.norm_q, q, 128) and _fusable_norm(attn.norm_k, k, 128):
             # one in-place HIP pass per tensor: norm everywhere, rotation on the video tokens only
@@ -174,24 +182,32 @@ class HunyuanVideoFlashAttnProcessor:
         return q, k, v, T
 
     @staticmethod
+    def _joint_applies(attn, hidden_states, encoder_hidden_states, single_stream: bool, grad: bool = False) -> bool:
+        """do the modules and inputs allow `_project_joint`?  (grad=True: would they, in the inference call)"""
+        vid = (attn.to_q, attn.to_k, attn.to_v)
+        txt = vid if single_stream else (attn.add_q_proj, attn.add_k_proj, attn.add_v_proj)
+        if not _joint_projectable(hidden_states, encoder_hidden_states, vid + txt, grad):
+            return False
+        H, out_f = attn.heads, attn.to_q.out_features
+        probe = hidden_states.new_empty((1, H, 1, out_f // H))
+        norms = (attn.norm_q, attn.norm_k) if single_stream else (attn.norm_q, attn.norm_k, attn.norm_added_q,
+                                                                   attn.norm_added_k)
+        if out_f // H != 128 or not all(_fusable_norm(n, probe, 128) for n in norms):
+            return False
+        return all(m.out_features == out_f for m in vid + txt)
+
+    @staticmethod
     def _project_joint(attn, hidden_states, encoder_hidden_states, rope, single_stream: bool):
         """Fused-norm case: the video and text projections land in ONE (1, S+T, H*D) buffer per tensor, written by the
         GEMMs -- no `torch.cat([q, eq], dim=2)` pass over q, k, v in a dual-stream block (hunyuan.py:106-134), no concat
         of the block inputs in a single-stream one (hunyuan.py:47-48); qk-norm + RoPE run in place on the row ranges.
         None when the modules do not allow it (the caller then takes the reference's route)."""
+        if not HunyuanVideoFlashAttnProcessor._joint_applies(attn, hidden_states, encoder_hidden_states, single_stream):
+            return None
         vid = (attn.to_q, attn.to_k, attn.to_v)
         txt = vid if single_stream else (attn.add_q_proj, attn.add_k_proj, attn.add_v_proj)
-        if not _joint_projectable(hidden_states, encoder_hidden_states, vid + txt):
-            return None
         S_, T, H = hidden_states.shape[1], encoder_hidden_states.shape[1], attn.heads
         out_f = attn.to_q.out_features
-        probe = hidden_states.new_empty((1, H, 1, out_f // H))
-        norms = (attn.norm_q, attn.norm_k) if single_stream else (attn.norm_q, attn.norm_k, attn.norm_added_q,
-                                                                   attn.norm_added_k)
-        if out_f // H != 128 or not all(_fusable_norm(n, probe, 128) for n in norms):
-            return None
-        if any(m.out_features != out_f for m in vid + txt):
-            return None
         x2d, e2d = hidden_states[0], encoder_hidden_states[0]
         qkv = []
         for lin, elin in zip(vid, txt):

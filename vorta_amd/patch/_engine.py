@@ -16,12 +16,20 @@ attaches to them with module hooks instead:
 
 Nothing is patched at class level, so two differently patched models can live in one process (the reference
 overwrites `Class.forward`, SURVEY.md §8b "not re-entrant").
+
+Training (`train_router=True`, processors built with `differentiable=True`, grad mode on): the scores come from
+`Router.forward_autograd` and carry a graph to the router weights (`RoutePlan.compute_autograd`); what the blocks of one
+forward need lives in that forward's `ForwardState`, which a block recomputed under gradient checkpointing finds again
+(`StepContext.state_for`); `original_attention(model)` is the dense teacher pass, `routing_scores_of(model)` hands the
+caller's losses the scores.
 """
 from __future__ import annotations
 
+import contextlib
 import inspect
+import weakref
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -85,9 +93,21 @@ class RoutePlan:
         self._experts_host = None
         self.tau = float(tau)
 
+    def trainable(self) -> bool:
+        return any(p.requires_grad for r in self.routers for p in r.parameters())
+
+    def compute_autograd(self, temb: torch.Tensor) -> torch.Tensor:
+        """(L, B, H, E) scores with a graph to every router's weights and to `temb` (not detached: a trainable timestep
+        embedder gets its gradient): `Router.forward_autograd` layer by layer, its roundings and its bits.  The hard
+        dispatch lists are not computed: the soft-mixture processors do not read them."""
+        return torch.stack([r.forward_autograd(temb) for r in self.routers])
+
     @property
     def ready(self) -> bool:
         return self._out is not None
+
+    def all_scores(self) -> torch.Tensor:
+        return self._out[0]  # (L, B, H, E)
 
     def scores(self, layer: int) -> torch.Tensor:
         return self._out[0][layer]  # (B, H, E)
@@ -103,15 +123,60 @@ class RoutePlan:
         return self._experts_host[layer]
 
 
+@dataclass(eq=False)
+class ForwardState:
+    """What the attention blocks of ONE forward of a patched model are handed: the keyword set (for Hunyuan with the
+    sliding-tile descriptor in it), this forward's scores and the teacher flag.  A block recomputed during `backward()`
+    (gradient checkpointing) is handed the same objects again, whatever forwards ran in between."""
+    kwargs: Optional[Dict[str, Any]] = None      # self_attention_kwargs of this forward, completed
+    teacher: bool = False                        # forward under `original_attention`: dense attention, no route plan
+    scores: Optional[torch.Tensor] = None        # (L, B, H, E); with a graph on the training path
+    layer_scores: List[torch.Tensor] = field(default_factory=list)  # its per-layer views, made once
+    head_routing: bool = False                   # the plan's dispatch lists belong to these scores (inference path)
+
+
+class _KeepState(torch.autograd.Function):
+    """Identity on the model output whose graph node owns the forward's `ForwardState`: the state lives exactly as long
+    as something can still run a backward (and so a recompute) through this forward, and not a moment longer."""
+
+    @staticmethod
+    def forward(ctx, x, state):
+        ctx.state = state
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return grad, None
+
+
+def _rotary_key(rotary) -> Optional[torch.Tensor]:
+    if isinstance(rotary, (tuple, list)):
+        rotary = rotary[0] if rotary else None
+    return rotary if isinstance(rotary, torch.Tensor) else None
+
+
 @dataclass
 class StepContext:
-    """Per-model state shared by the hooks and the bound processors."""
+    """Per-model state shared by the hooks and the bound processors.
+
+    Per-forward state: `current` is the `ForwardState` of the running forward (strong, from the model's pre hook to its
+    post hook).  Every bound processor call inside it also files the state under the rotary table it was handed --
+    `records`: id(table) -> (weak table, weak states).  A NON-REENTRANT checkpoint replays a block with the very argument
+    tensors of its forward, so the recomputed block finds its own forward's state by that table, after the post hook has
+    run and whichever forwards (the teacher's, the next step's) ran since.  The state itself is owned by the graph of the
+    model output (`_KeepState`), so it is released with the last tensor that could run that backward; nothing here holds
+    it strongly and there is no cycle through the model.  A reentrant checkpoint replays with detached copies of the
+    arguments, finds no record and is refused with an error that says so."""
     plan: Optional[RoutePlan] = None
-    kwargs: Optional[Dict[str, Any]] = None           # self_attention_kwargs of the running forward
+    current: Optional[ForwardState] = None
+    records: Dict[int, Tuple[Any, List[Any]]] = field(default_factory=dict)
+    teacher: bool = False                             # inside `original_attention(model)`
+    differentiable: bool = False                      # the bound processors were built with differentiable=True
+    student: Any = None                               # weak reference to the latest student forward's state
+    student_scores: Optional[torch.Tensor] = None     # its scores, detached (what outlives the graph)
     default_kwargs: Optional[Dict[str, Any]] = None   # set by the pipeline call; used when the forward gets none
     return_routing_scores: bool = False
     default_return_routing_scores: bool = False
-    captured: bool = False                            # timestep embedding seen in this forward
     collected: List[Any] = field(default_factory=list)  # per-step score lists gathered for the pipeline call
     step_token: Any = None       # callable -> object identifying the running denoising step (pipeline call)
     last_token: Any = None
@@ -120,6 +185,29 @@ class StepContext:
     needs_tau: bool = True       # hard top-1 dispatch (Eval processors); False for the soft mixture (Train)
     sp_token_shard: bool = False  # pipeline calls: the model gets the WHOLE latent and shards its token sequence itself
     sp_coherent: bool = False     # this pipeline call's ranks were seen to hold the same tokens (install_token_shard)
+
+    def state_for(self, rotary) -> Optional[ForwardState]:
+        """the state of the forward a processor call belongs to: the running forward's (in grad mode filed under `rotary`
+        for a later recompute), else the one filed under `rotary` by the forward that made the table; None when there is
+        neither"""
+        key = _rotary_key(rotary)
+        hit = self.records.get(id(key)) if key is not None else None
+        if hit is not None and hit[0]() is not key:  # the address of a table that is gone
+            hit = None
+        state = self.current
+        if state is not None:
+            if key is not None and torch.is_grad_enabled() and (hit is None or all(s() is not state for s in hit[1])):
+                # a rope that caches its table hands one object to many forwards: keep those whose state is still alive
+                alive = [s for s in hit[1] if s() is not None] if hit is not None else []
+                records, kid = self.records, id(key)
+                wkey = hit[0] if hit is not None else weakref.ref(key, lambda _, r=records, k=kid: r.pop(k, None))
+                records[kid] = (wkey, alive + [weakref.ref(state)])
+            return state
+        alive = [x for x in (s() for s in hit[1]) if x is not None] if hit is not None else []
+        if len(alive) > 1:
+            raise RuntimeError("a block is recomputed with a rotary table that two forwards with live graphs share: the "
+                               "per-forward state is filed under that table and cannot tell them apart")
+        return alive[0] if alive else None
 
 
 class BoundProcessor:
@@ -139,23 +227,31 @@ class BoundProcessor:
                  rotary_emb=None, use_original_attn: bool = False):
         rotary = image_rotary_emb if self.rotary_name == "image_rotary_emb" else rotary_emb
         ctx = self.ctx
-        if use_original_attn:
+        state = ctx.state_for(rotary)
+        if state is None:
+            raise RuntimeError("this attention block runs outside a forward of its patched transformer and no earlier "
+                               "forward is on record for its rotary table.  A block recomputed by gradient checkpointing "
+                               "finds its forward by the argument tensors it is replayed with: use the non-reentrant "
+                               "form (torch.utils.checkpoint.checkpoint(..., use_reentrant=False)), which replays them "
+                               "unchanged; the reentrant form replays detached copies and cannot be served")
+        if use_original_attn or state.teacher:
             if "use_original_attn" in self._accepted:
                 return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary,
                                   use_original_attn=True)
             return self.dense(attn, hidden_states, encoder_hidden_states, attention_mask, rotary)
-        if ctx.kwargs is None:
+        if state.kwargs is None:
             raise ValueError("this transformer was patched with apply_vorta_transformer: pass `self_attention_kwargs` "
                              "(prepare_*_self_attn_kwargs) to its forward, or run it through vorta_pipeline_call")
-        if ctx.plan is None or not ctx.captured:
+        if ctx.plan is None or state.scores is None:
             raise RuntimeError("routes of this step are not available: the timestep embedder of the model was not "
                                "called before its first attention block")
-        kw = {k: v for k, v in ctx.kwargs.items() if k in self._accepted}
-        kw["routing_score"] = ctx.plan.scores(self.layer)
-        if "head_routing" in self._accepted:
-            kw["head_routing"] = ctx.plan.routing(self.layer)
-        if "experts_host" in self._accepted and SP_STATE.enabled:
-            kw["experts_host"] = ctx.plan.experts_host(self.layer)
+        kw = {k: v for k, v in state.kwargs.items() if k in self._accepted}
+        kw["routing_score"] = state.layer_scores[self.layer]
+        if state.head_routing:
+            if "head_routing" in self._accepted:
+                kw["head_routing"] = ctx.plan.routing(self.layer)
+            if "experts_host" in self._accepted and SP_STATE.enabled:
+                kw["experts_host"] = ctx.plan.experts_host(self.layer)
         return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
 
 
@@ -200,19 +296,23 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
         sak = extra.get("self_attention_kwargs")
         if sak is None:
             sak = ctx.default_kwargs
-        if sak is not None and prepare_kwargs is not None:
+        if sak is not None and prepare_kwargs is not None and not ctx.teacher:
             sak = prepare_kwargs(module, args, kwargs, sak)
-        ctx.kwargs = sak
+        ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
-        ctx.captured = False
         ctx.forwards += 1
         return args, kwargs
 
     def post(module, args, kwargs, output):
+        state, ctx.current = ctx.current, None
+        if output is None:  # the forward raised (always_call): no later recompute may take its state for the running one
+            return None
         scores: List[torch.Tensor] = []
-        if ctx.return_routing_scores and ctx.plan is not None and ctx.plan.ready:
+        if state.scores is not None:
+            ctx.student, ctx.student_scores = weakref.ref(state), state.scores.detach()
+        if ctx.return_routing_scores and state.scores is not None:
             # one device read for all layers (the reference does `.detach().cpu()` per block, modeling_hunyuan.py:297)
-            all_scores = ctx.plan._out[0].detach().cpu()
+            all_scores = state.scores.detach().cpu()
             scores = [all_scores[i] for i in range(all_scores.shape[0])]
             # under the pipeline call only the first (conditional) forward of a step is recorded, as the reference
             # passes return_routing_scores=False to the guidance forward (pipeline_hunyuan.py:424-437)
@@ -220,14 +320,15 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
             if token is None or token is not ctx.last_token:
                 ctx.collected.append(scores)
                 ctx.last_token = token  # keeps the object alive, so `is` cannot match a recycled id
-        ctx.kwargs = None
+        sample = output[0] if isinstance(output, tuple) else output.sample if hasattr(output, "sample") else output
+        if torch.is_grad_enabled() and sample.requires_grad:  # a backward may recompute blocks of this forward
+            sample = _KeepState.apply(sample, state)
         if isinstance(output, tuple):
-            return (output[0], None, None, None, scores)
-        sample = output.sample if hasattr(output, "sample") else output
+            return (sample, None, None, None, scores)
         return RoutedTransformerModelOutput(sample=sample, routing_scores=scores)
 
     add_hook(model, model.register_forward_pre_hook(pre, with_kwargs=True))
-    add_hook(model, model.register_forward_hook(post, with_kwargs=True))
+    add_hook(model, model.register_forward_hook(post, with_kwargs=True, always_call=True))
 
 
 def install_timestep_capture(embedder: nn.Module, model: nn.Module, ctx: StepContext) -> None:
@@ -236,19 +337,62 @@ def install_timestep_capture(embedder: nn.Module, model: nn.Module, ctx: StepCon
     forward (Hunyuan's token_replace variant embeds a second, zero timestep, modeling_hunyuan.py:633-637)."""
 
     def hook(module, args, output):
-        if ctx.captured or ctx.plan is None or ctx.kwargs is None:
+        state = ctx.current
+        if state is None or state.scores is not None or state.teacher or ctx.plan is None or state.kwargs is None:
             return None
-        tau = ctx.kwargs.get("tau_sparse")
+        if torch.is_grad_enabled() and ctx.differentiable and ctx.plan.trainable():
+            state.scores = ctx.plan.compute_autograd(output)  # the training path: a graph to the routers
+            state.layer_scores = list(state.scores.unbind(0))
+            return None
+        tau = state.kwargs.get("tau_sparse")
         if tau is None:
             if ctx.needs_tau:
                 raise ValueError("self_attention_kwargs has no `tau_sparse` "
                                  "(prepare_*_self_attn_kwargs(..., tau_sparse=...))")
             tau = 0.0  # soft-mixture processors use the scores only; the dispatch lists go unused
         ctx.plan.compute(output, tau)
-        ctx.captured = True
+        state.scores = ctx.plan.all_scores()
+        if torch.is_grad_enabled() and ctx.differentiable:
+            # frozen routers inside a training graph: a recompute must not read what a later forward wrote into the
+            # plan's fixed buffers
+            state.scores = state.scores.clone()
+        else:
+            state.head_routing = True
+        state.layer_scores = list(state.scores.unbind(0))
         return None
 
     add_hook(model, embedder.register_forward_hook(hook))
+
+
+@contextlib.contextmanager
+def original_attention(model: nn.Module):
+    """The teacher pass at model level: while active, every forward of `model` (patched with apply_vorta_transformer)
+    runs each block's attention dense (`use_original_attn=True`, modeling_hunyuan.py:251-285,426-428) and computes no
+    route plan; `self_attention_kwargs` may be left out.  Under torch.no_grad() on the student's inputs this is the
+    reference's `ref_hidden_states` stream.  The flag is read once per forward, into that forward's state: a student
+    block recomputed later stays a student block, inside this context too."""
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("original_attention: the model was not patched with apply_vorta_transformer")
+    previous, ctx.teacher = ctx.teacher, True
+    try:
+        yield model
+    finally:
+        ctx.teacher = previous
+
+
+def routing_scores_of(model: nn.Module) -> torch.Tensor:
+    """(L, B, H, E) routing scores of the model's latest student forward, for the caller's losses (the reference's
+    `reg_loss` is `mean(scores[..., 0] ** 2)` per layer, modeling_hunyuan.py:301-305).  They carry the graph to the router
+    weights when that forward built one (grad mode, trainable routers, differentiable processors) and its output is
+    still alive; detached otherwise."""
+    ctx = context_of(model)
+    if ctx.student_scores is None:
+        raise RuntimeError("routing_scores_of: no routed forward of this model has run yet")
+    state = ctx.student() if ctx.student is not None else None
+    if state is not None and state.scores is not None and state.scores.requires_grad:
+        return state.scores
+    return ctx.student_scores
 
 
 def install_sp_rope(rope: nn.Module, model: nn.Module, frame_dim: int = 2) -> None:

@@ -75,6 +75,7 @@ def apply_vorta_transformer(model, train_router: bool = False, checkpoint_file: 
     E.clear_hooks(model)
     kw = dict(attn_processor_kwargs or {})
     kw.update(check_input=True)
+    ctx.differentiable = bool(kw.get("differentiable", False))  # with train_router: the scores carry a graph (_engine.py)
     dense = HunyuanVideoFlashAttnProcessor()
     blocks = _blocks(model)
     for layer, block in enumerate(blocks):

@@ -33,6 +33,7 @@ def apply_vorta_transformer(model, train_router: bool = False, checkpoint_file: 
     E.clear_hooks(model)
     kw = dict(attn_processor_kwargs or {})
     kw.update(check_input=True)
+    ctx.differentiable = bool(kw.get("differentiable", False))  # with train_router: the scores carry a graph (_engine.py)
     blocks = list(model.blocks)
     for layer, block in enumerate(blocks):
         if not hasattr(block, "router"):
@@ -42,7 +43,8 @@ def apply_vorta_transformer(model, train_router: bool = False, checkpoint_file: 
         if train_router:
             block.router.requires_grad_(True)
         E.set_processor(block.attn1, E.BoundProcessor(cls(**kw), ctx, layer, "rotary_emb"))
-        E.set_processor(block.attn2, WanAttnProcessor2_0())
+        # a training graph passes through the cross attention on its way to the earlier blocks' routers
+        E.set_processor(block.attn2, WanAttnProcessor2_0(differentiable=ctx.differentiable))
         kw.update(check_input=False)
     ctx.plan = E.RoutePlan([b.router for b in blocks])
 

@@ -560,6 +560,20 @@ def _replay_backward(launches, d_out: torch.Tensor, dq: torch.Tensor, dk: torch.
         _attn_bwd_by(algorithm, q, k, v, o, d_out, dq, dk, dv, do_scale=None if weight_of is None else weight_of(c, o), **c)
 
 
+def _unbind_launches(launches, outs) -> list:
+    """the recorded launches without q / k / v / out; `expert` keeps which of `outs` a launch wrote.  An autograd node keeps
+    these beside its SAVED q, k, v and expert outputs and binds them again in its backward (`_bind_launches`): inside a
+    checkpointed region the saved tensors are the recomputed ones and the forward's own are gone (and must not be kept
+    alive by the dictionaries).  The tables stay: constants of the backward, equal in a recompute."""
+    ptrs = [o.data_ptr() for o in outs]
+    return [dict({n: x for n, x in c.items() if n not in ("q", "k", "v", "out")}, expert=ptrs.index(c["out"].data_ptr()))
+            for c in launches]
+
+
+def _bind_launches(launches, q, k, v, outs) -> list:
+    return [dict({n: x for n, x in c.items() if n != "expert"}, q=q, k=k, v=v, out=outs[c["expert"]]) for c in launches]
+
+
 class _SoftMixture(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward):
@@ -572,7 +586,7 @@ class _SoftMixture(torch.autograd.Function):
                          text_valid=text_valid, scale=scale, expert_outs=bufs, fp8=False, record=launches)
         ops.mix_experts([b[0] if b.dim() == 4 else b for b in bufs], routing_score, out[0] if out.dim() == 4 else out)
         ctx.save_for_backward(q, k, v, routing_score, *bufs)
-        ctx.launches = launches
+        ctx.launches = _unbind_launches(launches, [b[0] if b.dim() == 4 else b for b in bufs])
         return out
 
     @staticmethod
@@ -589,7 +603,8 @@ class _SoftMixture(torch.autograd.Function):
             e = next(i for i, b in enumerate(bufs3) if b.data_ptr() == o.data_ptr())
             return sc[:, e]
 
-        _replay_backward(ctx.launches, g3, acc[0], acc[1], acc[2], weight_of, ctx.algorithm)
+        launches = _bind_launches(ctx.launches, q3, fold(k), fold(v), bufs3)
+        _replay_backward(launches, g3, acc[0], acc[1], acc[2], weight_of, ctx.algorithm)
         grads = [torch.empty_like(q3) for _ in range(3)]
         ops.cast_grads(acc, grads)
         d_sc = torch.zeros_like(routing_score)  # batch items > 0 are not read by the forward
