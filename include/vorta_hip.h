@@ -46,7 +46,9 @@ extern "C" {
                                    and the key-major backward, vorta_attn_bwd_stats / vorta_attn_bwd_kmajor (a pure addition too:
                                    a binding asks for the symbols and for vorta_attn_bwd_kmajor_args_size())
                                    and the deterministic backward, vorta_attn_bwd_dq / vorta_attn_bwd_dkv (two more symbols, on
-                                   the key-major argument block) */
+                                   the key-major argument block)
+                                   and the per-head expert fidelity, vorta_expert_fidelity (a pure addition: a binding asks for
+                                   the symbol and for vorta_fidelity_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -688,6 +690,57 @@ typedef struct vorta_cast_args {
 } vorta_cast_args;
 
 int vorta_cast_grads(const vorta_cast_args* args, void* hip_stream);
+
+/*
+ * vorta_expert_fidelity (ABI 9, a pure addition: a binding asks for the symbol and for vorta_fidelity_args_size(); vorta_sizeof
+ * keeps its 17 indices) -- how far the sparse experts and the mixed output are from the full expert, per head, from the three
+ * expert outputs the training-time forward already holds (`_combine_attn_outputs`' inputs, hunyuan.py:509-513 == wan.py:296-300;
+ * the reference has no such measurement).  With x0 = x[0] (full attention) and t_0 = x[1] (coreset), t_1 = x[2] (sliding tile),
+ * t_2 = mixed (the output of vorta_mix_experts; optional), over the head's n_rows x 128 elements:
+ *     sq_ref[h]     = sum x0^2                 max_ref[h]    = max |x0|           range_ref[h] = max x0 - min x0   (optional)
+ *     sq_err[h][j]  = sum d_j^2                max_err[h][j] = max |d_j|          d_j = fl(t_j - x0)
+ * all float32; [h][j] with a stride of 3, and column 2 is WRITTEN ONLY when mixed.ptr is given.  One pass: every row of every
+ * buffer is read once, 16 bytes a lane.
+ * ARITHMETIC: the values are widened to float32 (exact); fl() is the one float32 rounding of the difference (it is exact
+ * whenever the exponents of the two 16-bit values are less than 16 apart; in general |fl(d) - d| <= 2^-24 |d|); squares and sums
+ * are float32, maxima are exact maxima of the |fl(d_j)|.  A head with a NaN among its inputs, or an Inf that meets an Inf in a
+ * difference, gets NaN in the sums AND the maxima of the columns it reaches, as a float64 evaluation would; other heads are not
+ * touched.  Squares below 2^-126 (bf16 differences below 2^-63) underflow: the bound below is for data above that.
+ * DETERMINISTIC, in the manner of vorta_mix_experts_bwd: VORTA_FIDELITY_PARTS partials per head over the fixed row ranges
+ * [b per, (b + 1) per), per = ceil(n_rows / PARTS); in a partial, a lane owns 8 channels of every 16th row of the range and adds
+ * one row's 8 squares as a fixed tree to its running sum; lanes meet by shuffles, the four waves through LDS, the partial goes to
+ * the caller's workspace with plain vector stores, and a second launch joins the parts of a head as a fixed shuffle tree.  No
+ * float atomic; maxima and minima take the same path.  The same bits on every run and every stream.
+ * LONGEST CHAIN of float32 roundings a sum passes through = VORTA_FIDELITY_CHAIN(n_rows):
+ *     2 (the rounded difference, squared) + 4 (a row's 8 squares: d^2, one fma, two tree levels) + V (one add per row a lane
+ *     visits, V = ceil(per / 16)) + 6 (wave shuffles) + 2 (four waves) + 6 (64 parts) + 1 (so that the LINEAR bound holds:
+ *     (1 + u)^n - 1 <= (n + 1) u for n <= 4096)
+ * and every term is non-negative, so |sum - exact| <= CHAIN 2^-24 exact.  Hunyuan-129f (119 056 rows): 138, i.e. 8.3e-6; the
+ * bound stays under 1e-4 up to 1.69 million rows a head.
+ * VORTA_EINVAL for a wrong struct_size, negative sizes, a null or misaligned output (4 bytes) or workspace (16 bytes), a null
+ * or misaligned tensor (16-byte aligned rows; a null x is accepted only with n_rows == 0); VORTA_EUNSUPPORTED for a dtype
+ * other than bf16 / fp16 or head_dim != 128.  Everything is looked at before anything is launched.  heads == 0 is VORTA_OK and
+ * launches nothing; n_rows == 0 is VORTA_OK and writes zeros.
+ */
+#define VORTA_FIDELITY_PARTS 64
+#define VORTA_FIDELITY_WS_FLOATS 12 /* per head and part */
+#define VORTA_FIDELITY_CHAIN(n_rows) (((((int64_t)(n_rows) + VORTA_FIDELITY_PARTS - 1) / VORTA_FIDELITY_PARTS + 15) / 16) + 21)
+typedef struct vorta_fidelity_args {
+  uint32_t struct_size; /* = sizeof(vorta_fidelity_args) = vorta_fidelity_args_size() */
+  int32_t dtype, head_dim, heads, n_rows;
+  int32_t reserved;
+  vorta_tensor x[3];   /* (H, n_rows, D) views, strided like vorta_mix_args.x: outputs of expert 0 / 1 / 2 */
+  vorta_tensor mixed;  /* (H, n_rows, D) view, dtype of x; ptr NULL = not given */
+  float* sq_ref;       /* out [heads] */
+  float* max_ref;      /* out [heads] */
+  float* sq_err;       /* out [heads][3] */
+  float* max_err;      /* out [heads][3] */
+  float* range_ref;    /* out [heads], or NULL (what a PSNR over the data range needs) */
+  float* ws;           /* workspace, heads * VORTA_FIDELITY_PARTS * VORTA_FIDELITY_WS_FLOATS floats, 16-byte aligned (caller-owned) */
+} vorta_fidelity_args;
+
+int vorta_expert_fidelity(const vorta_fidelity_args* args, void* hip_stream);
+int vorta_fidelity_args_size(void);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.

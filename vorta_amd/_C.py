@@ -170,8 +170,22 @@ class NormRopeBwdArgs(C.Structure):
     ]
 
 
+class FidelityArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("heads", _i32), ("n_rows", _i32), ("reserved", _i32),
+        ("x", Tensor * 3), ("mixed", Tensor), ("sq_ref", _vp), ("max_ref", _vp), ("sq_err", _vp), ("max_err", _vp),
+        ("range_ref", _vp), ("ws", _vp),
+    ]
+
+
 MIX_BWD_PARTS = 64  # include/vorta_hip.h VORTA_MIX_BWD_PARTS
 NORM_ROPE_BWD_PARTS = 1024  # include/vorta_hip.h VORTA_NORM_ROPE_BWD_PARTS
+FIDELITY_PARTS, FIDELITY_WS_FLOATS = 64, 12  # include/vorta_hip.h VORTA_FIDELITY_PARTS, VORTA_FIDELITY_WS_FLOATS
+
+
+def fidelity_chain(n_rows: int) -> int:
+    """include/vorta_hip.h VORTA_FIDELITY_CHAIN: the longest chain of float32 roundings a sum of vorta_expert_fidelity passes through"""
+    return ((n_rows + FIDELITY_PARTS - 1) // FIDELITY_PARTS + 15) // 16 + 21
 
 # every symbol include/vorta_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -208,6 +222,8 @@ SYMBOLS = {
     "vorta_attn_bwd_dkv": (C.c_int, [C.POINTER(AttnBwdKmajorArgs), _vp]),
     "vorta_mix_experts_bwd": (C.c_int, [C.POINTER(MixBwdArgs), _vp]),
     "vorta_cast_grads": (C.c_int, [C.POINTER(CastArgs), _vp]),
+    "vorta_expert_fidelity": (C.c_int, [C.POINTER(FidelityArgs), _vp]),
+    "vorta_fidelity_args_size": (C.c_int, []),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "vorta_permute_heads": (C.c_int, [C.POINTER(PermuteArgs), _vp]),
     "vorta_abi_version": (C.c_int, []),
@@ -245,8 +261,8 @@ def lib():
         try:
             fn = getattr(h, name)
         except AttributeError:
-            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward without a new number: an
-            # older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward and vorta_expert_fidelity without a
+            # new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
@@ -263,6 +279,9 @@ def lib():
     if h.vorta_attn_bwd_kmajor_args_size() != C.sizeof(AttnBwdKmajorArgs):
         raise VortaHipError(f"struct layout mismatch for AttnBwdKmajorArgs: C {h.vorta_attn_bwd_kmajor_args_size()} "
                             f"vs ctypes {C.sizeof(AttnBwdKmajorArgs)}")
+    if h.vorta_fidelity_args_size() != C.sizeof(FidelityArgs):
+        raise VortaHipError(f"struct layout mismatch for FidelityArgs: C {h.vorta_fidelity_args_size()} "
+                            f"vs ctypes {C.sizeof(FidelityArgs)}")
     _lib = h
     return h
 

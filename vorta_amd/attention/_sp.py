@@ -230,6 +230,13 @@ def _mixture_placement(H: int, P: int):
     return list(range(H)), [H // P + (1 if j < H % P else 0) for j in range(P)]
 
 
+def mixture_head_range(H: int):
+    """[h0, h1): the heads this rank holds in the sequence-parallel soft mixture (natural order, `_mixture_placement`)"""
+    _, counts = _mixture_placement(H, SP_STATE.sp_size)
+    me = SP_STATE.group_local_rank
+    return sum(counts[:me]), sum(counts[:me + 1])
+
+
 def _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape):
     B, H, N, D = q.shape
     if B != 1:
@@ -260,8 +267,45 @@ def _recv_mixture_forward(lay, geom, qb, kb, vb, scores, ebufs, ob, model, T, te
     ops.mix_experts([_flat(lay, b) for b in ebufs], scores[:1].repeat(1, lay.P + 1, 1), _flat(lay, ob))
 
 
+def _recv_fidelity(lay, ebufs, ob) -> "ops.ExpertFidelity":
+    """ops.expert_fidelity of this rank's heads from receive buffers: the kernel sees the (P + 1) Hl segments of `_flat` (every
+    row exactly once) and the per-segment results are combined here, as mix_experts_bwd's are: sums add, maxima meet.  A
+    head's range would need the segments' signed extremes, which the kernel does not hand out: range_ref is not carried.  A
+    sum's chain of roundings is _C.fidelity_chain(Sl) + P here.  The rows of the text segment beyond the text length are
+    zero in all four buffers (`new_buffer`, `new_recv_buffer`), and zeros add nothing to a sum or to a maximum of magnitudes."""
+    f = ops.expert_fidelity([_flat(lay, b) for b in ebufs], _flat(lay, ob))
+    seg = lambda t: t.view(lay.P + 1, lay.Hl, *t.shape[1:])  # noqa: E731
+    return ops.ExpertFidelity(seg(f.sq_ref).sum(0), seg(f.max_ref).amax(0), seg(f.sq_err).sum(0), seg(f.max_err).amax(0), None,
+                              lay.D * (lay.S + lay.T))
+
+
+def gather_fidelity(fid: "ops.ExpertFidelity", H: int) -> "ops.ExpertFidelity":
+    """this rank's statistics ((..., Hl) / (..., Hl, 3), heads `mixture_head_range(H)`) -> all H heads in head order: one
+    all-gather per tensor over the sequence-parallel group, padded to the largest head count (a collective: every rank
+    calls it).  A gloo group gathers host copies."""
+    import torch.distributed as dist
+    P = SP_STATE.sp_size
+    _, counts = _mixture_placement(H, P)
+    staged = dist.get_backend(SP_STATE.group) == "gloo"
+
+    def gather(t, axis):  # `axis`: the head axis
+        pad = t.new_zeros(t.shape[:axis] + (max(counts),) + t.shape[axis + 1:])
+        pad.narrow(axis, 0, t.shape[axis]).copy_(t)
+        src = pad.cpu() if staged else pad.contiguous()
+        parts = [torch.empty_like(src) for _ in range(P)]
+        dist.all_gather(parts, src, group=SP_STATE.group)
+        return torch.cat([p.narrow(axis, 0, c) for p, c in zip(parts, counts)], dim=axis).to(t.device)
+
+    return ops.ExpertFidelity(gather(fid.sq_ref, fid.sq_ref.dim() - 1), gather(fid.max_ref, fid.max_ref.dim() - 1),
+                              gather(fid.sq_err, fid.sq_err.dim() - 2), gather(fid.max_err, fid.max_err.dim() - 2), None, fid.n)
+
+
 class _RecvSoftMixture(torch.autograd.Function):
     """routed.`_SoftMixture` on receive buffers: q, k, v in, the mixed output out, all (rows_total, D) of one layout"""
+
+    # the list `sp_soft_mixture_attention_autograd(fidelity=...)` hands over for the length of its `apply` (the inputs of
+    # `forward` end with the algorithm); a forward recomputed later, under gradient checkpointing, finds None and measures nothing
+    fidelity_sink = None
 
     @staticmethod
     def forward(ctx, qb, kb, vb, scores, lay, geom, model, T, te, scale, backward=None):
@@ -272,6 +316,8 @@ class _RecvSoftMixture(torch.autograd.Function):
         ob = new_recv_buffer(lay)
         launches: list = []
         _recv_mixture_forward(lay, geom, qb, kb, vb, scores, ebufs, ob, model, T, te, scale, record=launches)
+        if _RecvSoftMixture.fidelity_sink is not None:
+            _RecvSoftMixture.fidelity_sink.append(_recv_fidelity(lay, ebufs, ob))
         ctx.save_for_backward(qb, kb, vb, scores, *ebufs)
         from ..routed import _unbind_launches
         ctx.launches, ctx.lay = _unbind_launches(launches, ebufs), lay  # (a head view starts where its buffer starts)
@@ -303,11 +349,13 @@ class _RecvSoftMixture(torch.autograd.Function):
 
 def sp_soft_mixture_attention(q, k, v, T: int, routing_score: torch.Tensor, *, model: str, text_valid: int = 0,
                               lowres_group_info=None, window_size=(3, 3, 3), tile_size=(6, 8, 8), latent_shape=None,
-                              scale: Optional[float] = None) -> torch.Tensor:
+                              scale: Optional[float] = None, fidelity: Optional[list] = None) -> torch.Tensor:
     """`routed.soft_mixture_attention` under sequence parallelism, forward only (no autograd graph).
     q,k,v: (1, H, S/P + T, D) local sequence shard with the replicated text at the end, as `sp_attention`; routing_score
     (B, H, 3), item 0 is read.  Returns the (1, S/P + T, H, D) buffer (text rows: all heads, gathered).  The receive
-    buffers are the cached ones of the inference path."""
+    buffers are the cached ones of the inference path.
+    fidelity: a list that receives one `ops.ExpertFidelity` of THIS RANK's heads [h0, h1) (`mixture_head_range`), over
+    their whole sequences; the caller gathers across ranks.  None: launches and bits are unchanged."""
     with torch.no_grad():
         lay, order, geom, (h0, h1) = _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape)
         _, sb = _layout(lay.H, lay.S, T, lay.D, q.device, q.dtype, lay.counts)
@@ -317,6 +365,8 @@ def sp_soft_mixture_attention(q, k, v, T: int, routing_score: torch.Tensor, *, m
         lay.scatter_heads([x[0, :, :Sl] for x in (q, k, v)], sb.bufs[:3], order, [x[0, :, Sl:] for x in (q, k, v)] if T else None)
         te = text_valid if model == "hunyuan" else 0
         _recv_mixture_forward(lay, geom, *sb.bufs[:3], routing_score[:1, h0:h1], sb.mix_bufs, sb.bufs[3], model, T, te, scale)
+        if fidelity is not None:
+            fidelity.append(_recv_fidelity(lay, sb.mix_bufs, sb.bufs[3]))
         buf = torch.empty((1, Sl + T, lay.H, lay.D), dtype=q.dtype, device=q.device)
         lay.gather_heads(sb.bufs[3], buf[0, :Sl].transpose(0, 1), order, buf[0, Sl:].transpose(0, 1) if T else None)
         return buf
@@ -325,7 +375,7 @@ def sp_soft_mixture_attention(q, k, v, T: int, routing_score: torch.Tensor, *, m
 def sp_soft_mixture_attention_autograd(q, k, v, T: int, routing_score: torch.Tensor, *, model: str, text_valid: int = 0,
                                        lowres_group_info=None, window_size=(3, 3, 3), tile_size=(6, 8, 8),
                                        latent_shape=None, scale: Optional[float] = None,
-                                       backward: Optional[str] = None) -> torch.Tensor:
+                                       backward: Optional[str] = None, fidelity: Optional[list] = None) -> torch.Tensor:
     """`sp_soft_mixture_attention` as a differentiable operator (`routed.soft_mixture_attention_autograd` on the local heads
     between a differentiable exchange, ulysses/autograd.py).  The backward exchanges d_out to head shards, takes the score
     gradients (ops.mix_experts_bwd), replays the recorded launches into float32 buffers laid out like the receive buffers,
@@ -337,12 +387,17 @@ def sp_soft_mixture_attention_autograd(q, k, v, T: int, routing_score: torch.Ten
     gradients repeat bit for bit; a sum ACROSS ranks, the training loop's all-reduce of text-row and score
     gradients, is outside that claim), as for `routed.soft_mixture_attention_autograd`; None follows
     `routed.set_attention_backward` / VORTA_ATTENTION_BACKWARD, else "query_major".  It is resolved when the forward runs,
-    and an unknown name is refused before a layout is built or a collective runs.  The forward is the same whichever it is."""
+    and an unknown name is refused before a layout is built or a collective runs.  The forward is the same whichever it is.
+    `fidelity`: as for `sp_soft_mixture_attention` (this rank's heads; no gradient flows through it)."""
     from ..routed import attention_backward
     from ..ulysses.autograd import gather_heads_autograd, scatter_heads_autograd
     algorithm = attention_backward(backward)
     lay, order, geom, (h0, h1) = _mixture_setup(q, T, model, lowres_group_info, window_size, tile_size, latent_shape)
     qb, kb, vb = scatter_heads_autograd(lay, [q[0], k[0], v[0]], order)
     te = text_valid if model == "hunyuan" else 0
-    ob = _RecvSoftMixture.apply(qb, kb, vb, routing_score[:1, h0:h1], lay, geom, model, T, te, scale, algorithm)
+    previous, _RecvSoftMixture.fidelity_sink = _RecvSoftMixture.fidelity_sink, fidelity
+    try:
+        ob = _RecvSoftMixture.apply(qb, kb, vb, routing_score[:1, h0:h1], lay, geom, model, T, te, scale, algorithm)
+    finally:
+        _RecvSoftMixture.fidelity_sink = previous
     return gather_heads_autograd(lay, ob, order, token_major=True)[None]

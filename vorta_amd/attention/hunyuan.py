@@ -363,7 +363,9 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
                  lowres_group_info: Optional[LowresGroupInfo] = None,
                  flex_attn_mask_func: Optional[SlidingTileDescriptor] = None,
                  window_size: Tuple[int, int, int] = (3, 3, 3), tile_size: Tuple[int, int, int] = (6, 8, 8),
-                 latent_shape: Tuple[int, int, int] = (30, 48, 80)):
+                 latent_shape: Tuple[int, int, int] = (30, 48, 80), fidelity: Optional[list] = None):
+        """fidelity: a list that receives this call's `ops.ExpertFidelity` (the heads this process holds: all of them, or this
+        rank's under sequence parallelism); None: the launches of today"""
         if use_original_attn:
             return HunyuanVideoFlashAttnProcessor.__call__(self, attn, hidden_states, encoder_hidden_states,
                                                            attention_mask, image_rotary_emb)
@@ -376,12 +378,12 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
                 from ._sp import sp_soft_mixture_attention_autograd
                 buf = sp_soft_mixture_attention_autograd(q, k, v, T, routing_score, model="hunyuan", text_valid=te,
                                                          lowres_group_info=lowres_group_info, window_size=window_size,
-                                                         tile_size=tile_size, latent_shape=latent_shape)
+                                                         tile_size=tile_size, latent_shape=latent_shape, fidelity=fidelity)
                 return self._output(attn, buf, T)
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             out = soft_mixture_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), routing_score, geom,
-                                                  model="hunyuan", text_len=T, text_valid=te)
+                                                  model="hunyuan", text_len=T, text_valid=te, fidelity=fidelity)
             return self._output(attn, out.transpose(1, 2), T)
         if torch.is_grad_enabled() and (hidden_states.requires_grad or routing_score.requires_grad):
             raise NotImplementedError("the soft-mixture forward of this build has no backward: call it under "
@@ -395,9 +397,16 @@ class HunyuanVideoFlashAttnProcessorTripleTrain(HunyuanVideoFlashAttnProcessorTr
                 from ._sp import sp_soft_mixture_attention
                 buf = sp_soft_mixture_attention(q, k, v, T, routing_score, model="hunyuan", text_valid=te,
                                                 lowres_group_info=lowres_group_info, window_size=window_size,
-                                                tile_size=tile_size, latent_shape=latent_shape)
+                                                tile_size=tile_size, latent_shape=latent_shape, fidelity=fidelity)
                 return self._output(attn, buf, T)
             buf, out = self._new_out(q)
+            if fidelity is not None:  # (a list is no operator argument: the launcher behind vorta::soft_mixture_attention, directly)
+                from ..routed import soft_mixture_attention
+                geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                    device=q.device)
+                soft_mixture_attention(q, k, v, routing_score, geom, model="hunyuan", text_len=T, text_valid=te, out=out,
+                                       fidelity=fidelity)
+                return self._output(attn, buf, T)
             torch.ops.vorta.soft_mixture_attention(q, k, v, routing_score, out,
                                                    **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size,
                                                                               latent_shape),

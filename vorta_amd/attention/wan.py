@@ -239,7 +239,9 @@ class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
                  lowres_group_info: Optional[LowresGroupInfo] = None,
                  flex_attn_mask_func: Optional[SlidingTileDescriptor] = None,
                  window_size: Tuple[int, int, int] = (3, 3, 3), tile_size: Tuple[int, int, int] = (6, 8, 8),
-                 latent_shape: Tuple[int, int, int] = (20, 30, 52)):
+                 latent_shape: Tuple[int, int, int] = (20, 30, 52), fidelity: Optional[list] = None):
+        """fidelity: a list that receives this call's `ops.ExpertFidelity` (the heads this process holds: all of them, or this
+        rank's under sequence parallelism); None: the launches of today"""
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
@@ -251,12 +253,12 @@ class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
                 from ._sp import sp_soft_mixture_attention_autograd
                 buf = sp_soft_mixture_attention_autograd(q, k, v, 0, routing_score, model="wan",
                                                          lowres_group_info=lowres_group_info, window_size=window_size,
-                                                         tile_size=tile_size, latent_shape=latent_shape)
+                                                         tile_size=tile_size, latent_shape=latent_shape, fidelity=fidelity)
                 return self._output_proj(attn, buf)
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             out = soft_mixture_attention_autograd(q.contiguous(), k.contiguous(), v.contiguous(), routing_score, geom,
-                                                  model="wan")
+                                                  model="wan", fidelity=fidelity)
             return self._output_proj(attn, out.transpose(1, 2))
         if torch.is_grad_enabled() and (hidden_states.requires_grad or routing_score.requires_grad):
             raise NotImplementedError("the soft-mixture forward of this build has no backward: call it under "
@@ -268,9 +270,16 @@ class WanAttnProcessorTripleTrain(WanAttnProcessorTripleEval):
             if SP_STATE.enabled:
                 from ._sp import sp_soft_mixture_attention
                 buf = sp_soft_mixture_attention(q, k, v, 0, routing_score, model="wan", lowres_group_info=lowres_group_info,
-                                                window_size=window_size, tile_size=tile_size, latent_shape=latent_shape)
+                                                window_size=window_size, tile_size=tile_size, latent_shape=latent_shape,
+                                                fidelity=fidelity)
                 return self._output_proj(attn, buf)
             buf, out = self._new_out(q)
+            if fidelity is not None:  # (a list is no operator argument: the launcher behind vorta::soft_mixture_attention, directly)
+                from ..routed import soft_mixture_attention
+                geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                    device=q.device)
+                soft_mixture_attention(q, k, v, routing_score, geom, model="wan", out=out, fidelity=fidelity)
+                return self._output_proj(attn, buf)
             torch.ops.vorta.soft_mixture_attention(q, k, v, routing_score, out,
                                                    **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size,
                                                                               latent_shape), model="wan")

@@ -1030,6 +1030,80 @@ def mix_experts_bwd(xs, d_out: torch.Tensor) -> torch.Tensor:
     return dscores
 
 
+class ExpertFidelity(NamedTuple):
+    """vorta_expert_fidelity's statistics: per head how far the coreset expert (column 0), the sliding-tile expert (column 1)
+    and the mixed output (column 2; NaN when no mixed output was given) are from the full expert x0.  Float32 tensors with
+    any leading dimensions (a layer axis, `vorta.patch.fidelity_of`): sq_ref, max_ref, range_ref (..., H); sq_err, max_err
+    (..., H, 3).  `n` = the elements of a head the sums run over (rows x 128): what turns a sum of squares into a mean."""
+    sq_ref: torch.Tensor                       # sum x0^2
+    max_ref: torch.Tensor                      # max |x0|
+    sq_err: torch.Tensor                       # sum (t_j - x0)^2
+    max_err: torch.Tensor                      # max |t_j - x0|
+    range_ref: Optional[torch.Tensor] = None   # max x0 - min x0
+    n: int = 0
+
+    def rel_error(self) -> torch.Tensor:
+        """sqrt(sq_err / sq_ref), (..., H, 3); a head with sq_ref == 0 gives 0 where sq_err == 0 and inf otherwise"""
+        ref = self.sq_ref.unsqueeze(-1).expand_as(self.sq_err)
+        rel = torch.sqrt(self.sq_err / ref)
+        zero = ref == 0
+        rel = torch.where(zero & (self.sq_err == 0), torch.zeros_like(rel), rel)
+        return torch.where(zero & (self.sq_err > 0), torch.full_like(rel, float("inf")), rel)
+
+    def psnr(self, over: str = "max_abs") -> torch.Tensor:
+        """10 log10(peak^2 / mean squared error) in dB, (..., H, 3): peak = max |x0| (`over="max_abs"`) or the data range
+        max x0 - min x0 (`over="range"`) of the full expert's output; inf where the error is exactly zero"""
+        if over not in ("max_abs", "range"):
+            raise ValueError(f"psnr: over={over!r} (one of 'max_abs', 'range')")
+        if self.n <= 0:
+            raise ValueError("psnr needs the element count `n` of the statistics (ops.expert_fidelity sets it)")
+        peak = self.max_ref if over == "max_abs" else self.range_ref
+        if peak is None:
+            raise ValueError("psnr(over='range') needs range_ref")
+        mse = self.sq_err.double() / self.n
+        return (10.0 * torch.log10(peak.double().unsqueeze(-1) ** 2 / mse)).float()
+
+
+def _fidelity_check(xs, mixed):
+    if len(xs) != 3 or xs[0].dtype not in _DT or xs[0].dim() != 3:
+        raise ValueError("expert_fidelity takes the (H,N,D) outputs of the three experts in bf16 / fp16")
+    for t in list(xs[1:]) + ([mixed] if mixed is not None else []):
+        if t.shape != xs[0].shape or t.dtype != xs[0].dtype:
+            raise ValueError("expert_fidelity: the expert outputs and the mixed output must agree in shape and dtype")
+
+
+def expert_fidelity(bufs, mixed: Optional[torch.Tensor] = None) -> ExpertFidelity:
+    """vorta_expert_fidelity: one deterministic pass over the three experts' outputs `bufs` ((H,N,D) views, or (1,H,N,D)) and,
+    when given, the output of `mix_experts`: per head the squared norm and the largest magnitude of the full expert, and the
+    squared and the largest error of the coreset expert, the sliding-tile expert and the mixed output against it."""
+    xs = [b[0] if b.dim() == 4 else b for b in bufs]
+    if mixed is not None and mixed.dim() == 4:
+        mixed = mixed[0]
+    _require_gpu(mixed, *xs)
+    _fidelity_check(xs, mixed)
+    H, N, D = xs[0].shape
+    dev = xs[0].device
+    a = _C.FidelityArgs()
+    a.struct_size = C.sizeof(_C.FidelityArgs)
+    a.dtype, a.head_dim, a.heads, a.n_rows = _DT[xs[0].dtype], D, H, N
+    for e in range(3):
+        a.x[e] = _tensor(xs[e])
+    if mixed is not None:
+        a.mixed = _tensor(mixed)
+    sq_ref, max_ref, range_ref = (torch.empty((H,), dtype=torch.float32, device=dev) for _ in range(3))
+    sq_err = torch.full((H, 3), float("nan"), dtype=torch.float32, device=dev)  # (the mixed column stays NaN without `mixed`)
+    max_err = torch.full((H, 3), float("nan"), dtype=torch.float32, device=dev)
+    ws = torch.empty(H * _C.FIDELITY_PARTS * _C.FIDELITY_WS_FLOATS, dtype=torch.float32, device=dev)
+    a.sq_ref, a.max_ref, a.range_ref = sq_ref.data_ptr(), max_ref.data_ptr(), range_ref.data_ptr()
+    a.sq_err, a.max_err, a.ws = sq_err.data_ptr(), max_err.data_ptr(), ws.data_ptr()
+    if H > 0:
+        _C.check(_C.lib().vorta_expert_fidelity(C.byref(a), _stream()), "vorta_expert_fidelity")
+    if mixed is not None and N == 0:  # an empty tensor has no address to give: the library saw no mixed output
+        sq_err[:, 2] = 0
+        max_err[:, 2] = 0
+    return ExpertFidelity(sq_ref, max_ref, sq_err, max_err, range_ref, N * D)
+
+
 def cast_grads(srcs, dsts) -> None:
     """vorta_cast_grads: up to three float32 (H,N,D) buffers -> 16-bit (H,N,D) views in one launch, round to nearest even."""
     _require_gpu(*srcs, *dsts)

@@ -21,7 +21,8 @@ Training (`train_router=True`, processors built with `differentiable=True`, grad
 `Router.forward_autograd` and carry a graph to the router weights (`RoutePlan.compute_autograd`); what the blocks of one
 forward need lives in that forward's `ForwardState`, which a block recomputed under gradient checkpointing finds again
 (`StepContext.state_for`); `original_attention(model)` is the dense teacher pass, `routing_scores_of(model)` hands the
-caller's losses the scores.
+caller's losses the scores.  `expert_fidelity(model)` / `fidelity_of(model)` (patch/fidelity.py) measure how far every head's
+sparse experts are from full attention in such a forward.
 """
 from __future__ import annotations
 
@@ -133,6 +134,7 @@ class ForwardState:
     scores: Optional[torch.Tensor] = None        # (L, B, H, E); with a graph on the training path
     layer_scores: List[torch.Tensor] = field(default_factory=list)  # its per-layer views, made once
     head_routing: bool = False                   # the plan's dispatch lists belong to these scores (inference path)
+    fidelity: Optional[Dict[int, Any]] = None    # layer -> ops.ExpertFidelity; a dict only under `expert_fidelity(model)`
 
 
 class _KeepState(torch.autograd.Function):
@@ -185,6 +187,8 @@ class StepContext:
     needs_tau: bool = True       # hard top-1 dispatch (Eval processors); False for the soft mixture (Train)
     sp_token_shard: bool = False  # pipeline calls: the model gets the WHOLE latent and shards its token sequence itself
     sp_coherent: bool = False     # this pipeline call's ranks were seen to hold the same tokens (install_token_shard)
+    measure_fidelity: bool = False  # inside `expert_fidelity(model)` (patch/fidelity.py)
+    fidelity: Optional[Dict[int, Any]] = None  # the statistics of the latest forward that measured (what `fidelity_of` reads)
 
     def state_for(self, rotary) -> Optional[ForwardState]:
         """the state of the forward a processor call belongs to: the running forward's (in grad mode filed under `rotary`
@@ -252,7 +256,13 @@ class BoundProcessor:
                 kw["head_routing"] = ctx.plan.routing(self.layer)
             if "experts_host" in self._accepted and SP_STATE.enabled:
                 kw["experts_host"] = ctx.plan.experts_host(self.layer)
-        return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+        if state.fidelity is None or "fidelity" not in self._accepted:
+            return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+        kw["fidelity"] = sink = []  # under `expert_fidelity(model)`: the soft mixture's statistics, filed under this layer
+        out = self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+        if sink:  # (a cross-attention call measures nothing)
+            state.fidelity[self.layer] = sink[-1]
+        return out
 
 
 def set_processor(attn: nn.Module, processor) -> None:
@@ -298,7 +308,8 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
             sak = ctx.default_kwargs
         if sak is not None and prepare_kwargs is not None and not ctx.teacher:
             sak = prepare_kwargs(module, args, kwargs, sak)
-        ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher)
+        ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher,
+                                   fidelity={} if ctx.measure_fidelity and not ctx.teacher else None)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
         ctx.forwards += 1
         return args, kwargs
@@ -310,6 +321,8 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
         scores: List[torch.Tensor] = []
         if state.scores is not None:
             ctx.student, ctx.student_scores = weakref.ref(state), state.scores.detach()
+        if state.fidelity:
+            ctx.fidelity = state.fidelity  # (small per-head tensors: kept until the next measuring forward)
         if ctx.return_routing_scores and state.scores is not None:
             # one device read for all layers (the reference does `.detach().cpu()` per block, modeling_hunyuan.py:297)
             all_scores = state.scores.detach().cpu()

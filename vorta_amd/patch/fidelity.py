@@ -1,0 +1,159 @@
+"""Per-head expert fidelity of a patched transformer: is a router, or a `tau_sparse`, any good?
+
+The routed method makes one claim per head: that head's sparse expert reproduces what full attention would have written.  The
+training-time forward (the Train processors' soft mixture) holds the data that decides it -- all three expert outputs of every
+head of the layer -- and `ops.expert_fidelity` (vorta_expert_fidelity: one deterministic pass, nothing materialised) reduces it
+to per-head statistics.  The reference has no counterpart: its only signal is the end-to-end loss.
+
+    with expert_fidelity(model):                      # every Train-processor call of a forward files its layer's statistics
+        model(hidden_states, ..., self_attention_kwargs=kw)
+    fid = fidelity_of(model)                          # ops.ExpertFidelity, stacked (L, H, ...); all ranks' heads under SP
+    fid.rel_error()                                   # (L, H, 3): coreset, sliding tile, mixed output against full attention
+    table = routes_from_fidelity(fid, 0.05)           # (L, H) experts: the cheapest within the bound -- no backward pass
+    evaluate_routing(routing_scores_of(model), fid, geometry)   # what the router's own routes cost and lose
+
+Expert ids are the processors': 0 full attention, 1 coreset, 2 sliding tile; columns 0 / 1 of the statistics are experts 1 / 2.
+"""
+from __future__ import annotations
+
+import contextlib
+from typing import Any, Dict, Mapping, Optional, Tuple, Union
+
+import torch
+from torch import nn
+
+from ..ops import ExpertFidelity
+from ._engine import context_of
+
+_COLUMN_OF_EXPERT = {1: 0, 2: 1}  # expert id -> column of sq_err / max_err / rel_error
+
+
+@contextlib.contextmanager
+def expert_fidelity(model: nn.Module):
+    """While active, every forward of `model` (patched with apply_vorta_transformer, Train processors) measures its layers:
+    each soft-mixture call runs `ops.expert_fidelity` on its three expert outputs and its mixed output and files the result
+    under its layer on that forward's `ForwardState` (a block recomputed under gradient checkpointing files the same bits
+    again).  The flag is read once per forward, when it starts; teacher forwards (`original_attention`) measure nothing.
+    Outside the context the forwards launch what they launch today."""
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("expert_fidelity: the model was not patched with apply_vorta_transformer")
+    previous, ctx.measure_fidelity = ctx.measure_fidelity, True
+    try:
+        yield model
+    finally:
+        ctx.measure_fidelity = previous
+
+
+def stack_fidelity(per_layer) -> ExpertFidelity:
+    """a sequence of per-layer `ExpertFidelity` -> one with a leading layer axis"""
+    per_layer = list(per_layer)
+    first = per_layer[0]
+    cat = lambda name: torch.stack([getattr(f, name) for f in per_layer])  # noqa: E731
+    rng = None if any(f.range_ref is None for f in per_layer) else cat("range_ref")
+    return ExpertFidelity(cat("sq_ref"), cat("max_ref"), cat("sq_err"), cat("max_err"), rng, first.n)
+
+
+def fidelity_of(model: nn.Module) -> ExpertFidelity:
+    """The statistics of the model's latest forward under `expert_fidelity(model)`, stacked over the layers in block order:
+    sq_ref, max_ref (L, H); sq_err, max_err (L, H, 3).  Under sequence parallelism a rank measured its own heads over their
+    whole sequences: they are all-gathered over the group here (a collective: every rank calls it) and range_ref is not
+    carried.  Raises when no such forward is on record."""
+    ctx = context_of(model)
+    filed: Optional[Dict[int, ExpertFidelity]] = ctx.fidelity
+    if not filed:
+        raise RuntimeError("fidelity_of: no forward of this model has run under expert_fidelity(model) with soft-mixture "
+                           "(Train) processors")
+    fid = stack_fidelity(filed[layer] for layer in sorted(filed))
+    from ..ulysses import SP_STATE
+    if SP_STATE.enabled:
+        from ..attention._sp import gather_fidelity
+        fid = gather_fidelity(fid, ctx.plan.heads)
+    return fid
+
+
+Geometry = Union[Mapping[str, Any], Any]
+
+
+def _geometry_numbers(geometry: Geometry) -> Tuple[int, int, int, int]:
+    """(S, S_low, tokens per tile, keys a sliding-tile query sees among the video tokens) of a `routed.RoutedGeometry` or of
+    a mapping with latent / tile / window / group / rate (or the self_attention_kwargs spelling: latent_shape, tile_size,
+    window_size, lowres_group_info)"""
+    if isinstance(geometry, Mapping):
+        g = dict(geometry)
+        latent = g.get("latent", g.get("latent_shape"))
+        tile = g.get("tile", g.get("tile_size"))
+        window = g.get("window", g.get("window_size"))
+        info = g.get("lowres_group_info")
+        group = g.get("group", None if info is None else info.window_size)
+        rate = g.get("rate", None if info is None else info.reduction_rate)
+    else:
+        latent, tile, window, group, rate = geometry.latent, geometry.tile, geometry.window, geometry.group, geometry.rate
+    if any(x is None for x in (latent, tile, window, group, rate)):
+        raise ValueError("geometry needs latent, tile, window, group and rate")
+    S = int(latent[0]) * int(latent[1]) * int(latent[2])
+    gsz = int(group[0]) * int(group[1]) * int(group[2])
+    s_low = (S // gsz) * int(gsz * (1 - float(rate)))
+    tok = int(tile[0]) * int(tile[1]) * int(tile[2])
+    n_kv = 1
+    for l, t, w in zip(latent, tile, window):
+        n_kv *= min(int(l) // int(t), int(w))
+    return S, s_low, tok, n_kv * tok
+
+
+def expert_work(geometry: Geometry, text_valid: int = 0, head_dim: int = 128) -> Tuple[float, float, float]:
+    """FLOPs of one head under expert 0 / 1 / 2 by the work formulas of BASELINE.md section 2:
+    F_full = 4 (S + T_eff)^2 D, F_low = 4 (S_low + T_eff)^2 D, F_sl = 4 D [S (n_kv tok + T_eff) + T_eff (S + T_eff)]"""
+    S, s_low, _, keys = _geometry_numbers(geometry)
+    te, D = int(text_valid), int(head_dim)
+    return (4.0 * (S + te) ** 2 * D, 4.0 * (s_low + te) ** 2 * D, 4.0 * D * (S * (keys + te) + te * (S + te)))
+
+
+def routes_from_fidelity(fid: ExpertFidelity, max_rel_error: float, geometry: Optional[Geometry] = None,
+                         text_valid: int = 0) -> torch.Tensor:
+    """(..., H) int64 expert table (on the CPU): per head the CHEAPEST expert whose `rel_error` is within `max_rel_error`
+    (<=), full attention (0) where no sparse expert meets it.  Cost order: sliding tile, coreset, full -- the order the work
+    formulas of BASELINE.md give at every published geometry; with `geometry` the order is computed from them (`expert_work`).
+    A tie takes the cheaper expert.  A NaN error meets no bound.  No backward pass, no router: a table to compare a router's
+    routes against, or to route by."""
+    rel = fid.rel_error().detach().cpu()
+    order = (2, 1)  # sparse experts, cheapest first
+    if geometry is not None:
+        work = expert_work(geometry, text_valid)
+        order = tuple(sorted((1, 2), key=lambda e: (work[e], -e)))
+    table = torch.zeros(rel.shape[:-1], dtype=torch.int64)
+    for e in reversed(order):  # the cheapest is written last: it wins a tie
+        table = torch.where(rel[..., _COLUMN_OF_EXPERT[e]] <= float(max_rel_error), torch.full_like(table, e), table)
+    return table
+
+
+def evaluate_routing(experts_or_scores: torch.Tensor, fid: ExpertFidelity, geometry: Geometry, text_valid: int = 0,
+                     tau_sparse: Optional[float] = None) -> Dict[str, torch.Tensor]:
+    """What a routing costs and what it loses, per layer.  `experts_or_scores`: an integer (L, H) expert table, or floating
+    routing scores (L, H, 3) / (L, B, H, 3) (batch item 0; the processors' rule: the first maximum, full attention where
+    that score is below `tau_sparse`).  Returns CPU tensors of L entries: `worst_rel_error` and `mean_rel_error` of the
+    chosen experts over the heads (a head on full attention contributes 0), `flops_share` = the routed layer's FLOPs over
+    the all-dense layer's by `expert_work`, and the table itself as `experts` (L, H)."""
+    t = experts_or_scores.detach().cpu()
+    if t.is_floating_point():
+        if t.dim() == 4:
+            t = t[:, 0]
+        t = t.float()
+        best = t.max(dim=-1).values
+        experts = torch.where(t == best.unsqueeze(-1), torch.arange(t.shape[-1]), t.shape[-1]).min(dim=-1).values  # first maximum
+        if tau_sparse is not None:
+            experts = torch.where(best < float(tau_sparse), torch.zeros_like(experts), experts)
+    else:
+        experts = t.long()
+    rel = fid.rel_error().detach().cpu()
+    if experts.shape != rel.shape[:-1]:
+        raise ValueError(f"routing table {tuple(experts.shape)} does not match the statistics {tuple(rel.shape[:-1])}")
+    if bool(((experts < 0) | (experts > 2)).any()):
+        raise ValueError("expert ids are 0 (full), 1 (coreset), 2 (sliding tile)")
+    chosen = torch.zeros(experts.shape, dtype=rel.dtype)
+    for e, col in _COLUMN_OF_EXPERT.items():
+        chosen = torch.where(experts == e, rel[..., col], chosen)
+    work = torch.tensor(expert_work(geometry, text_valid), dtype=torch.float64)
+    share = work[experts].sum(-1) / (work[0] * experts.shape[-1])
+    return dict(worst_rel_error=chosen.max(dim=-1).values, mean_rel_error=chosen.mean(dim=-1), flops_share=share.float(),
+                experts=experts)

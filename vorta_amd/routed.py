@@ -483,12 +483,15 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
 
 def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,
                            geom: RoutedGeometry, *, model: str, text_len: int = 0, text_valid: int = 0,
-                           out: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+                           out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                           fidelity: Optional[list] = None) -> torch.Tensor:
     """Training-time FORWARD: every head through all three experts, outputs mixed with the routing
     scores of batch item 0 -- hunyuan.py:375-408,509-513 / wan.py:226-241,296-300.  The three experts over all H
     heads run as one fused grid into three buffers; `vorta_mix_experts` does the weighted sum in one pass.
     No autograd: the library has no backward kernels (router training itself is out of scope).
-    (The differentiable form of this operator is `soft_mixture_attention_autograd`, below.)"""
+    (The differentiable form of this operator is `soft_mixture_attention_autograd`, below.)
+    fidelity: a list that receives one `ops.ExpertFidelity` of this call's H heads (one more pass over the three expert
+    outputs and the mixed output, ops.expert_fidelity); None (default): the launches and the bits of `out` are unchanged."""
     H = q.shape[-3]
     if out is None:
         out = torch.empty_like(q)
@@ -497,6 +500,8 @@ def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
     routed_attention(q, k, v, HeadRouting.every_head_everywhere(H, q.device), geom, model=model, text_len=text_len,
                      text_valid=text_valid, scale=scale, expert_outs=bufs, fp8=False)
     ops.mix_experts([b[0] if b.dim() == 4 else b for b in bufs], routing_score, out[0] if out.dim() == 4 else out)
+    if fidelity is not None:
+        fidelity.append(ops.expert_fidelity(bufs, out))
     return out
 
 
@@ -576,7 +581,7 @@ def _bind_launches(launches, q, k, v, outs) -> list:
 
 class _SoftMixture(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward):
+    def forward(ctx, q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward, fidelity=None):
         ctx.algorithm = attention_backward(backward)
         H = q.shape[-3]
         out = torch.empty_like(q)
@@ -585,6 +590,8 @@ class _SoftMixture(torch.autograd.Function):
         routed_attention(q, k, v, HeadRouting.every_head_everywhere(H, q.device), geom, model=model, text_len=text_len,
                          text_valid=text_valid, scale=scale, expert_outs=bufs, fp8=False, record=launches)
         ops.mix_experts([b[0] if b.dim() == 4 else b for b in bufs], routing_score, out[0] if out.dim() == 4 else out)
+        if fidelity is not None:
+            fidelity.append(ops.expert_fidelity(bufs, out))
         ctx.save_for_backward(q, k, v, routing_score, *bufs)
         ctx.launches = _unbind_launches(launches, [b[0] if b.dim() == 4 else b for b in bufs])
         return out
@@ -610,12 +617,13 @@ class _SoftMixture(torch.autograd.Function):
         d_sc = torch.zeros_like(routing_score)  # batch items > 0 are not read by the forward
         d_sc[0] = dscores.to(routing_score.dtype)
         dq, dk, dv = (g.view(q.shape) for g in grads)
-        return dq, dk, dv, d_sc, None, None, None, None, None, None
+        return dq, dk, dv, d_sc, None, None, None, None, None, None, None
 
 
 def soft_mixture_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,
                                     geom: RoutedGeometry, *, model: str, text_len: int = 0, text_valid: int = 0,
-                                    scale: Optional[float] = None, backward: Optional[str] = None) -> torch.Tensor:
+                                    scale: Optional[float] = None, backward: Optional[str] = None,
+                                    fidelity: Optional[list] = None) -> torch.Tensor:
     """`soft_mixture_attention` as a differentiable operator (router training: the loss reaches the routing scores and,
     through q, k, v, every earlier layer).  The forward is the same launches and gives the same bits; it keeps q, k, v, the
     scores, the three expert outputs and the launches as recorded.  The backward zeroes three float32 (H,N,D) buffers,
@@ -627,8 +635,10 @@ def soft_mixture_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.T
     a sum of float atomics too) or "deterministic" (per launch ops.attn_bwd_stats, ops.attn_bwd_dq, ops.attn_bwd_dkv: no
     atomics -- dq, dk, dv and dscores are all bit-reproducible, the launches meeting in the shared buffers in stream order);
     None follows `set_attention_backward` / VORTA_ATTENTION_BACKWARD, read when the forward runs.  The forward is the same
-    whichever it is.  q, k, v: contiguous (1,H,N,D), like the forward's."""
-    return _SoftMixture.apply(q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward)
+    whichever it is.  q, k, v: contiguous (1,H,N,D), like the forward's.
+    `fidelity`: as for `soft_mixture_attention` -- a list that receives one `ops.ExpertFidelity` (no gradient flows through it;
+    a forward recomputed under gradient checkpointing appends again)."""
+    return _SoftMixture.apply(q, k, v, routing_score, geom, model, text_len, text_valid, scale, backward, fidelity)
 
 
 class _Dense(torch.autograd.Function):

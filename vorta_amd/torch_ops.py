@@ -25,6 +25,7 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::soft_mixture_attention_bwd(q,k,v, scores, d_out, latent, ...) -> (dq, dk, dv, dscores)   its autograd formula
     vorta::qk_norm_rope_grad(x, weight, eps, cos, sin, rope_tokens, across_heads) -> y   out of place, differentiable;
     vorta::qk_norm_rope_bwd(x, g, weight, eps, cos, sin, ...) -> (dx, dweight)   its autograd formula (vorta_qk_norm_rope_bwd)
+    vorta::expert_fidelity(x0,x1,x2, mixed)           -> (sq_ref, max_ref, sq_err, max_err, range_ref)   vorta_expert_fidelity
 """
 from typing import List, Optional, Tuple
 
@@ -141,6 +142,23 @@ def mix_experts(x0: torch.Tensor, x1: torch.Tensor, x2: torch.Tensor, scores: to
 @mix_experts.register_fake
 def _(x0, x1, x2, scores, out) -> None:
     return None
+
+
+@torch.library.custom_op("vorta::expert_fidelity", mutates_args=(), device_types="cuda")
+def expert_fidelity(x0: torch.Tensor, x1: torch.Tensor, x2: torch.Tensor, mixed: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.expert_fidelity on (H,N,D) views: float32 (H,), (H,), (H,3), (H,3), (H,) -- the fields of ops.ExpertFidelity but `n`
+    (= N * D, which a caller knows from the shapes)"""
+    f = ops.expert_fidelity([x0, x1, x2], mixed)
+    return f.sq_ref, f.max_ref, f.sq_err, f.max_err, f.range_ref
+
+
+@expert_fidelity.register_fake
+def _(x0, x1, x2, mixed=None):
+    H = x0.shape[0]
+    f32 = dict(dtype=torch.float32)
+    return (x0.new_empty((H,), **f32), x0.new_empty((H,), **f32), x0.new_empty((H, 3), **f32), x0.new_empty((H, 3), **f32),
+            x0.new_empty((H,), **f32))
 
 
 @torch.library.custom_op("vorta::routed_attention", mutates_args=("out",), device_types="cuda")
