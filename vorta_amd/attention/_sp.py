@@ -210,7 +210,8 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
 def sp_wan_dense(proc, attn, q, k, v, enc_img, is_cross_attn: bool):
     """Dense Wan attention under SP (wan.py:103-149).  Cross attention has replicated K/V (text / image
     tokens): every rank already holds all heads of its query shard and every key, so it needs NO
-    communication at all (the reference does an all-to-all of Q and back, wan.py:111-114,147)."""
+    communication at all (the reference does an all-to-all of Q and back, wan.py:111-114,147).  The same holds in grad
+    mode: `WanAttnProcessor2_0.__call__` takes its local grad path for cross attention and says what a rank ends with."""
     if is_cross_attn:
         return proc._attn(attn, q, k, v, enc_img, True)
     return sp_attention(q, k, v, 0, None, None, model="wan"), None

@@ -57,7 +57,8 @@ class WanAttnProcessor2_0:
 
     def _grad_path(self, sequence_parallel: bool = False) -> bool:
         """build an autograd graph in this call?  `sequence_parallel`: the caller has a differentiable exchange (the soft
-        mixture, attention/_sp.py); the dense attention has none -- the teacher runs under torch.no_grad()"""
+        mixture, attention/_sp.py) or needs none (cross attention: replicated keys); the dense self attention has none --
+        the teacher runs under torch.no_grad()"""
         if not (self.differentiable and torch.is_grad_enabled()):
             return False
         if SP_STATE.enabled and not sequence_parallel:
@@ -143,7 +144,16 @@ class WanAttnProcessor2_0:
         return attn.to_out[1](attn.to_out[0](hidden))
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, rotary_emb=None):
-        if not self._grad_path():  # the default: no autograd graph, whatever the inputs ask for
+        """Cross attention (`encoder_hidden_states` given) in grad mode under sequence parallelism is LOCAL: a rank holds
+        all heads of its query shard and every text / image key (`_sp.sp_wan_dense`), so the grad path below runs on the
+        shard as it is and no collective is issued, forward or backward.  A rank ends with its own rows of
+        d hidden_states, whole; with a PARTIAL gradient of encoder_hidden_states and of to_k / to_v / add_k_proj /
+        add_v_proj / norm_k / norm_added_k (the keys are replicated, the queries that read them are not), which sum over
+        the ranks to the single-process gradient; and with the gradient of to_q / norm_q / to_out from its own rows,
+        which sums over the ranks like that of any parameter applied to a sequence shard.  Dense SELF attention in grad
+        mode under sequence parallelism keeps raising: it has no differentiable exchange."""
+        # the default: no autograd graph, whatever the inputs ask for
+        if not self._grad_path(sequence_parallel=encoder_hidden_states is not None):
             return self._call_no_grad(attn, hidden_states, encoder_hidden_states, attention_mask, rotary_emb)
         if attention_mask is not None:
             raise NotImplementedError("attention_mask is always None on this path (wan.py:141)")

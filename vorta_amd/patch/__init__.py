@@ -7,10 +7,12 @@ The scripts import the entry points from the submodules, as with the reference (
 forwards with hooks (vorta_amd/patch/_engine.py) and import nothing from diffusers at module level.
 
 For router training on a patched model: `original_attention(model)` (the dense teacher pass) and `routing_scores_of(model)`
-(the scores of the latest student forward, with their graph).  For judging a router or a `tau_sparse`:
+(the scores of the latest student forward, with their graph); under sequence parallelism `token_sharded(model)` (whole
+latents in, tokens sharded inside the model) and `all_reduce_router_grads(model)` (the ranks' shares of the router
+gradients, summed).  For judging a router or a `tau_sparse`:
 `expert_fidelity(model)` / `fidelity_of(model)` (per layer and head, how far each sparse expert and the mixed output are from
 full attention) and the host helpers `routes_from_fidelity` / `evaluate_routing` (patch/fidelity.py)."""
-from ._engine import original_attention, routing_scores_of
+from ._engine import all_reduce_router_grads, original_attention, routing_scores_of, token_sharded
 from .fidelity import evaluate_routing, expert_fidelity, expert_work, fidelity_of, routes_from_fidelity
 from .router import Router, load_router_checkpoint
 from .utils import (Pixel2TokenFactory, hunyuan_pixel2token, prepare_hunyuan_self_attn_kwargs,

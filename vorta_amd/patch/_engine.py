@@ -21,7 +21,9 @@ Training (`train_router=True`, processors built with `differentiable=True`, grad
 `Router.forward_autograd` and carry a graph to the router weights (`RoutePlan.compute_autograd`); what the blocks of one
 forward need lives in that forward's `ForwardState`, which a block recomputed under gradient checkpointing finds again
 (`StepContext.state_for`); `original_attention(model)` is the dense teacher pass, `routing_scores_of(model)` hands the
-caller's losses the scores.  `expert_fidelity(model)` / `fidelity_of(model)` (patch/fidelity.py) measure how far every head's
+caller's losses the scores.  Under sequence parallelism the same forward trains frame-sharded or, inside
+`token_sharded(model)`, token-sharded; `all_reduce_router_grads(model)` sums the ranks' shares of the router gradients
+afterwards.  `expert_fidelity(model)` / `fidelity_of(model)` (patch/fidelity.py) measure how far every head's
 sparse experts are from full attention in such a forward.
 """
 from __future__ import annotations
@@ -135,6 +137,7 @@ class ForwardState:
     layer_scores: List[torch.Tensor] = field(default_factory=list)  # its per-layer views, made once
     head_routing: bool = False                   # the plan's dispatch lists belong to these scores (inference path)
     fidelity: Optional[Dict[int, Any]] = None    # layer -> ops.ExpertFidelity; a dict only under `expert_fidelity(model)`
+    token_shard: bool = False                    # sequence parallel: this forward got the WHOLE latent and cuts its tokens itself
 
 
 class _KeepState(torch.autograd.Function):
@@ -149,6 +152,43 @@ class _KeepState(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         return grad, None
+
+
+def all_reduce_sp(tensors: Sequence[torch.Tensor], average: bool = False) -> List[torch.Tensor]:
+    """ONE all-reduce over the sequence-parallel group of `tensors` taken together: summed in float32 (one rounding back to
+    each tensor's dtype), or averaged.  Returns new tensors; a gloo group reduces host copies, as `gather_fidelity` gathers
+    them.  A collective: every rank calls it with tensors of the same shapes in the same order."""
+    import torch.distributed as dist
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    staged = dist.get_backend(SP_STATE.group) == "gloo"
+    buf = flat.cpu() if staged else flat
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=SP_STATE.group)
+    if average:
+        buf = buf / SP_STATE.sp_size
+    buf = buf.to(flat.device)
+    out, at = [], 0
+    for t in tensors:
+        out.append(buf[at:at + t.numel()].view(t.shape).to(t.dtype))
+        at += t.numel()
+    return out
+
+
+class _SumOverRanks(torch.autograd.Function):
+    """Identity on the text rows a joint-attention block (Hunyuan) hands its processor under sequence parallelism, whose
+    backward sums the cotangent over the group.  The exchange's two text conventions do not compose on their own
+    (ulysses/autograd.py): the scatter's backward leaves a rank the text-row gradient of ITS OWN heads (partial: the ranks'
+    sum is the gradient), the gather's backward takes the rank's own heads out of a cotangent it assumes REPLICATED (every
+    rank sees the same loss on the text rows).  One layer alone satisfies both; in a stack, layer l + 1 hands layer l a
+    partial cotangent through the text stream and the other ranks' shares of a head's text rows would be dropped.  Summed
+    here, the text stream between two layers carries the whole cotangent on every rank, which is what the gather reads."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return all_reduce_sp([grad])[0]
 
 
 def _rotary_key(rotary) -> Optional[torch.Tensor]:
@@ -185,8 +225,10 @@ class StepContext:
     descriptor_cache: Dict[Any, Any] = field(default_factory=dict)
     forwards: int = 0
     needs_tau: bool = True       # hard top-1 dispatch (Eval processors); False for the soft mixture (Train)
-    sp_token_shard: bool = False  # pipeline calls: the model gets the WHOLE latent and shards its token sequence itself
-    sp_coherent: bool = False     # this pipeline call's ranks were seen to hold the same tokens (install_token_shard)
+    # pipeline calls and `token_sharded(model)`: the model gets the WHOLE latent and shards its token sequence itself (read
+    # once per forward, into `ForwardState.token_shard`)
+    sp_token_shard: bool = False
+    sp_coherent: bool = False     # this call's / context's ranks were seen to hold the same tokens (install_token_shard)
     measure_fidelity: bool = False  # inside `expert_fidelity(model)` (patch/fidelity.py)
     fidelity: Optional[Dict[int, Any]] = None  # the statistics of the latest forward that measured (what `fidelity_of` reads)
 
@@ -213,15 +255,30 @@ class StepContext:
                                "per-forward state is filed under that table and cannot tell them apart")
         return alive[0] if alive else None
 
+    def token_shard_of(self, args=(), kwargs=None) -> bool:
+        """token-shard mode of the forward a hook call belongs to: the running forward's; for a module recomputed later by
+        a non-reentrant checkpoint, that of the forward on record for a rotary table among its arguments; with neither (a
+        model without the routed forward protocol, a module that is handed no table) the flag as it stands"""
+        state = self.current
+        if state is None and self.records:
+            for v in tuple(args) + tuple((kwargs or {}).values()):
+                key = _rotary_key(v)
+                if key is not None and id(key) in self.records:
+                    state = self.state_for(v)
+                    if state is not None:
+                        break
+        return state.token_shard if state is not None else self.sp_token_shard
+
 
 class BoundProcessor:
     """Adapter between the stock diffusers call `processor(attn, hidden_states, encoder_hidden_states=...,
     attention_mask=..., image_rotary_emb|rotary_emb=...)` and the routed processors' keyword set
     (hunyuan.py:521-539, wan.py:308-328)."""
 
-    def __init__(self, inner, ctx: StepContext, layer: int, rotary_name: str, dense=None):
+    def __init__(self, inner, ctx: StepContext, layer: int, rotary_name: str, dense=None, joint_text: bool = False):
         self.inner = inner
         self.dense = dense  # plain dense processor serving `use_original_attn=True` (the teacher path)
+        self.joint_text = joint_text  # the text rows attend with the video rows and flow on to the next block (Hunyuan)
         self.ctx = ctx
         self.layer = layer
         self.rotary_name = rotary_name
@@ -249,6 +306,10 @@ class BoundProcessor:
         if ctx.plan is None or state.scores is None:
             raise RuntimeError("routes of this step are not available: the timestep embedder of the model was not "
                                "called before its first attention block")
+        if (self.joint_text and SP_STATE.enabled and torch.is_grad_enabled() and encoder_hidden_states is not None
+                and encoder_hidden_states.requires_grad):
+            # a training graph through a stack of joint-attention layers: the text stream carries whole cotangents
+            encoder_hidden_states = _SumOverRanks.apply(encoder_hidden_states)
         kw = {k: v for k, v in state.kwargs.items() if k in self._accepted}
         kw["routing_score"] = state.layer_scores[self.layer]
         if state.head_routing:
@@ -308,8 +369,16 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
             sak = ctx.default_kwargs
         if sak is not None and prepare_kwargs is not None and not ctx.teacher:
             sak = prepare_kwargs(module, args, kwargs, sak)
+        token_shard = bool(ctx.sp_token_shard and SP_STATE.enabled)
+        if SP_STATE.enabled and not token_shard and sak is not None and sak.get("latent_shape") is not None \
+                and int(sak["latent_shape"][0]) % SP_STATE.sp_size:
+            raise ValueError(f"a frame-sharded forward needs the {SP_STATE.sp_size} sequence-parallel ranks to divide the "
+                             f"latent frame count, which is {int(sak['latent_shape'][0])} (latent_shape "
+                             f"{tuple(sak['latent_shape'])}): hand every rank the whole latent inside "
+                             "`token_sharded(model)`, or run the pipeline call, which shards tokens")
         ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher,
-                                   fidelity={} if ctx.measure_fidelity and not ctx.teacher else None)
+                                   fidelity={} if ctx.measure_fidelity and not ctx.teacher else None,
+                                   token_shard=token_shard)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
         ctx.forwards += 1
         return args, kwargs
@@ -408,6 +477,78 @@ def routing_scores_of(model: nn.Module) -> torch.Tensor:
     return ctx.student_scores
 
 
+def installed_routers(model: nn.Module) -> List[nn.Module]:
+    """the Router of every block, in block order, as apply_vorta_transformer installed them"""
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("the model was not patched with apply_vorta_transformer")
+    return list(ctx.plan.routers)
+
+
+def all_reduce_router_grads(model: nn.Module, op: str = "sum") -> None:
+    """After a sequence-parallel backward: ONE all-reduce over the sequence-parallel group of the `.grad` of every parameter
+    of every Router the patch installed, written back in place.  A rank's backward leaves it the score gradients of its own
+    heads and exact zeros elsewhere, so every router holds a partial gradient per rank; `op="sum"` makes
+    them the single-process gradient (accumulated in float32, one rounding to the gradient's dtype).  `op="avg"` divides
+    that sum by the group size: what an averaging data-parallel wrapper does, right for a loss that is a MEAN over the
+    rank's shard.  A term every rank computes identically from replicated values -- the reference's regulariser on
+    `routing_scores_of(model)` -- is counted P times by the sum: the caller divides it by P before `backward()`.
+    A gloo group reduces host copies.  With sequence parallelism disabled this is a no-op.  A collective: every rank calls
+    it, with the same parameter list -- a router parameter without a gradient is an error that names it.
+    NOT covered: the gradients of every other parameter and of `encoder_hidden_states`.  They follow the same rule (a
+    rank holds its share; parameters applied to replicated values behind a gather, such as the output projection under
+    `token_sharded`, hold the whole gradient on every rank) and belong to the training loop."""
+    if op not in ("sum", "avg"):
+        raise ValueError(f"all_reduce_router_grads: op must be 'sum' or 'avg', got {op!r}")
+    routers = installed_routers(model)
+    if not SP_STATE.enabled:
+        return
+    named = [(f"router of block {i}: {n}", p) for i, r in enumerate(routers) for n, p in r.named_parameters()]
+    missing = [n for n, p in named if p.grad is None]
+    if missing:
+        raise RuntimeError("all_reduce_router_grads: no gradient for " + ", ".join(missing) + " on sequence-parallel rank "
+                           f"{SP_STATE.group_local_rank}: every rank must reduce the same list (run backward() first; the "
+                           "routers are trained with train_router=True)")
+    grads = [p.grad for _, p in named]
+    with torch.no_grad():
+        for g, total in zip(grads, all_reduce_sp(grads, average=op == "avg")):
+            g.copy_(total)
+
+
+@contextlib.contextmanager
+def token_sharded(model: nn.Module, check: bool = True):
+    """Token-sharded forwards outside the pipeline call, for a training loop: while active and sequence parallelism is
+    enabled, every forward of `model` (patched with apply_vorta_transformer) takes the WHOLE latent on every rank and
+    shards its token sequence itself, through the hooks the pipeline call uses (`install_token_shard`): any latent whose
+    TOKEN count the ranks divide trains, whatever its frame count (Hunyuan-129f: 33 latent frames, 118 800 tokens).
+    The flag is read once per forward, into that forward's state, as `original_attention` and `expert_fidelity` are: a
+    block recomputed later by a non-reentrant checkpoint sees the mode of its own forward.  `check=True` compares the
+    ranks' tokens (`check_rank_coherence`) at the first cut after entering: one read-back per entry, not per forward;
+    `check=False` skips it.  The previous mode is restored on exit, after an exception too.  Without sequence parallelism
+    the context changes nothing.
+
+    Grad mode.  The cut is a slice and the gather is `ulysses.all_gather`, whose backward hands a rank its own slice of the
+    cotangent.  Every rank sees the whole gathered output and computes the SAME loss on it; a rank's gradients -- of the
+    router weights, of the latent (non-zero on its own tokens), of every parameter in front of the gather -- are then its
+    share, and their sum over the ranks is the single-process gradient (`all_reduce_router_grads` for the routers).  What
+    every rank computes identically from replicated values is counted P times by that sum: the caller divides such a term
+    by P -- the reference's regulariser on `routing_scores_of(model)` -- and a parameter behind the gather (the output
+    projection) holds the whole gradient on every rank.
+
+    Without this context a forward is FRAME-sharded, in grad mode as well: the caller passes its own latent-frame shard,
+    `install_sp_rope` supplies the global rotary table, P must divide the frame count, and the loss is the caller's on its
+    own output shard."""
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("token_sharded: the model was not patched with apply_vorta_transformer")
+    previous = (ctx.sp_token_shard, ctx.sp_coherent)
+    ctx.sp_token_shard, ctx.sp_coherent = True, not check
+    try:
+        yield model
+    finally:
+        ctx.sp_token_shard, ctx.sp_coherent = previous
+
+
 def install_sp_rope(rope: nn.Module, model: nn.Module, frame_dim: int = 2) -> None:
     """Sequence parallelism shards the latent frames (pipeline_hunyuan.py:367-369), but rotary positions are global:
     the reference re-states the rope forward with `num_frames * sp_size` (modeling_hunyuan.py:592-620,
@@ -418,7 +559,7 @@ def install_sp_rope(rope: nn.Module, model: nn.Module, frame_dim: int = 2) -> No
     ctx = context_of(model)
 
     def pre(module, args):
-        if not SP_STATE.enabled or not args or ctx.sp_token_shard:  # token shard: the input already is the global latent
+        if not SP_STATE.enabled or not args or ctx.token_shard_of():  # token shard: the input already is the global latent
             return None
         x = args[0]
         shape = list(x.shape)
@@ -482,7 +623,10 @@ def install_token_shard(model: nn.Module, first_block: nn.Module, gather_before:
     output the stock forward widens to fp32 in front of the output norm -- gathering there moves half the bytes).
     Every rank must enter with the same tokens: the first cut of a pipeline call compares a checksum of the sequence
     over the group and refuses to continue on a mismatch (a generator seeded per rank would otherwise make every rank
-    denoise a different video outside its own chunk)."""
+    denoise a different video outside its own chunk).
+    A training loop asks for the same mode with `token_sharded(model)`; cut and gather carry autograd as they stand (a
+    slice; `ulysses.all_gather`, whose backward is the rank's own slice), and that docstring says what a rank's gradients
+    then are.  The mode is the FORWARD's (`StepContext.token_shard_of`), not the flag's at the moment a hook runs."""
     from ..ulysses import all_gather
     ctx = context_of(model)
     if (gather_before is None) == (gather_after is None):
@@ -495,7 +639,7 @@ def install_token_shard(model: nn.Module, first_block: nn.Module, gather_before:
         return (fn(args[0]),) + tuple(args[1:]), kwargs
 
     def cut(module, args, kwargs):
-        if not (SP_STATE.enabled and ctx.sp_token_shard):
+        if not (SP_STATE.enabled and ctx.token_shard_of(args, kwargs)):
             return None
         P, r = SP_STATE.sp_size, SP_STATE.group_local_rank
 
@@ -503,20 +647,21 @@ def install_token_shard(model: nn.Module, first_block: nn.Module, gather_before:
             S = x.shape[1]
             if S % P:
                 raise ValueError(f"{S} video tokens do not divide over {P} sequence-parallel ranks")
-            if not ctx.sp_coherent:  # once per pipeline call: one read-back of 65 P floats
-                check_rank_coherence(x)
+            if not ctx.sp_coherent:  # once per pipeline call / `token_sharded` entry: one read-back of 65 P floats
+                with torch.no_grad():  # (the comparison gathers through `ulysses.all_gather`, an autograd function)
+                    check_rank_coherence(x)
                 ctx.sp_coherent = True
             n = S // P
             return x[:, r * n:(r + 1) * n]
         return _swap(args, kwargs, f)
 
     def join(module, args, kwargs):
-        if not (SP_STATE.enabled and ctx.sp_token_shard):
+        if not (SP_STATE.enabled and ctx.token_shard_of(args, kwargs)):
             return None
         return _swap(args, kwargs, lambda x: all_gather(x.contiguous(), dim=1))
 
     def join_out(module, args, output):
-        if not (SP_STATE.enabled and ctx.sp_token_shard):
+        if not (SP_STATE.enabled and ctx.token_shard_of(args)):
             return None
         if isinstance(output, tuple):
             return (all_gather(output[0].contiguous(), dim=1),) + tuple(output[1:])

@@ -85,7 +85,7 @@ def apply_vorta_transformer(model, train_router: bool = False, checkpoint_file: 
                 device=ref.device, dtype=router_dtype)
         if train_router:
             block.router.requires_grad_(True)
-        E.set_processor(block.attn, E.BoundProcessor(cls(**kw), ctx, layer, "image_rotary_emb", dense=dense))
+        E.set_processor(block.attn, E.BoundProcessor(cls(**kw), ctx, layer, "image_rotary_emb", dense=dense, joint_text=True))
         kw.update(check_input=False)  # only the first block checks its input (modeling_hunyuan.py:684)
     ctx.plan = E.RoutePlan([b.router for b in blocks])
 
