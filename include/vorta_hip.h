@@ -48,7 +48,9 @@ extern "C" {
                                    and the deterministic backward, vorta_attn_bwd_dq / vorta_attn_bwd_dkv (two more symbols, on
                                    the key-major argument block)
                                    and the per-head expert fidelity, vorta_expert_fidelity (a pure addition: a binding asks for
-                                   the symbol and for vorta_fidelity_args_size()) */
+                                   the symbol and for vorta_fidelity_args_size())
+                                   and partial geometry, vorta_sta_partial_sizes / vorta_sta_build_tables_partial /
+                                   vorta_coreset_select_partial (three more symbols on the existing argument blocks) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -526,6 +528,17 @@ typedef struct vorta_coreset_args {
 } vorta_coreset_args;
 
 int vorta_coreset_select(const vorta_coreset_args* args, void* hip_stream);
+/* Partial geometry (ABI 9, a pure addition): a window `group` that does not divide `latent`.  The windows are the
+ * ng = floor(latent / group) whole ones per dimension the reference's get_group_info keeps when it crops
+ * (coreset_select.py:36-40), G = prod(ng); the C = S - G*g tokens outside the cropped box stay at full resolution.  Same
+ * arguments; the lists are
+ *   keep_rows[y][G*(1+n_keep) + C + n_tail] : [G centres | G x n_keep kept margins | C remainder tokens, ascending | tail]
+ *   keep_rows_kv                            : its window part as for vorta_coreset_select, then the same remainder and tail
+ *   drop_rows[y][G][g-1-n_keep]             : as for vorta_coreset_select (a remainder token is never a duplicate)
+ * Two launches on the stream: the selection over the G windows (the kernel of vorta_coreset_select) and one that writes
+ * the remainder and tail rows.  VORTA_EINVAL when a dimension holds no whole window.  A dividing geometry gives the lists
+ * of vorta_coreset_select. */
+int vorta_coreset_select_partial(const vorta_coreset_args* args, void* hip_stream);
 
 /*
  * vorta_sta_build_tables -- sliding_attn_flex.py:72-134 (mask_mod) + tile.py:7-78 (tile/untile) as tables.
@@ -547,6 +560,20 @@ typedef struct vorta_sta_args {
 
 int vorta_sta_table_sizes(const vorta_sta_args* args, int32_t* n_tiles, int32_t* tok_per_tile, int32_t* n_kv);
 int vorta_sta_build_tables(const vorta_sta_args* args, void* hip_stream);
+/* Partial geometry (ABI 9, a pure addition): a tile that does not divide the latent grid.  nt = ceil(latent / tile) tiles
+ * per dimension, tile i = [i*tile, min((i+1)*tile, latent)); the window rule of vorta_sta_build_tables on that tile grid.
+ *   q_rows [S]                       tile-major position -> token: tiles in raster order, the tokens of a tile in raster
+ *                                    order of its own (possibly thinner) box
+ *   kv_rows[n_lists][list_stride]    one row per DISTINCT key list.  A list is fixed by the first tile (f0,f1,f2) of the
+ *                                    clamped window, f_d in [0, nt_d - cnt_d]; list l = (f0*nf1 + f1)*nf2 + f2.  Its
+ *                                    list_n_kv[l] entries are the tokens of the window's tiles (their union is one box,
+ *                                    listed in raster order) and then the t_eff text rows; entries behind them repeat the
+ *                                    first one.  Lists that hold a thin last tile are shorter: at most 8 lengths.
+ * vorta_sta_partial_sizes is host-only; list_n_kv (host, list_n_kv_cap entries, or NULL) receives the lengths.
+ * row_map as in vorta_sta_build_tables. */
+int vorta_sta_partial_sizes(const vorta_sta_args* args, int32_t* n_tiles, int32_t* n_lists, int32_t* list_stride,
+                            int32_t* list_n_kv, int32_t list_n_kv_cap);
+int vorta_sta_build_tables_partial(const vorta_sta_args* args, void* hip_stream);
 
 /*
  * vorta_router_route -- vorta/patch/router.py:33-43 (Router.forward) + the top-1 / tau rule of

@@ -208,6 +208,10 @@ SYMBOLS = {
     "vorta_coreset_select": (C.c_int, [C.POINTER(CoresetArgs), _vp]),
     "vorta_sta_table_sizes": (C.c_int, [C.POINTER(StaArgs), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "vorta_sta_build_tables": (C.c_int, [C.POINTER(StaArgs), _vp]),
+    "vorta_coreset_select_partial": (C.c_int, [C.POINTER(CoresetArgs), _vp]),
+    "vorta_sta_partial_sizes": (C.c_int, [C.POINTER(StaArgs), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                                          C.POINTER(_i32), _i32]),
+    "vorta_sta_build_tables_partial": (C.c_int, [C.POINTER(StaArgs), _vp]),
     "vorta_router_route": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
@@ -261,8 +265,8 @@ def lib():
         try:
             fn = getattr(h, name)
         except AttributeError:
-            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward and vorta_expert_fidelity without a
-            # new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity and the
+            # partial-geometry entry points without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res

@@ -20,3 +20,12 @@ def set_attention_backward(name: str) -> None:
     torch.use_deterministic_algorithms does not change it."""
     from .routed import set_attention_backward as _set
     _set(name)
+
+
+def set_partial_geometry(on: bool) -> None:
+    """Accept tile and coreset windows that do not divide the latent grid (off by default; also VORTA_PARTIAL_GEOMETRY=0|1):
+    thin last tiles for the sliding-tile expert, the reference's cropped windows plus full-resolution remainder tokens for the
+    coreset expert (DESIGN.md "Partial geometry").  With it on, the published (6,9,8)/(2,3,2) geometry runs at 129 frames.
+    A geometry that divides gives the same tables, launches and bits either way."""
+    from ._partial import set_partial_geometry as _set
+    _set(on)

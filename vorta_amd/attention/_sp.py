@@ -11,6 +11,7 @@ from typing import Optional
 import torch
 
 from .. import ops
+from .._partial import coreset_numbers, divides, partial_geometry, sliding_video_pairs
 from ..routed import HeadRouting, geometry_for, precision_of, routed_attention
 from ..ulysses import SP_STATE
 from ..ulysses.state import PLACEMENTS, default_sp_groups, resolve_placement  # noqa: F401  (one rule for the processors and bench.py)
@@ -153,10 +154,17 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
         cost = [1.0, 1.0, 1.0]
     else:  # expert costs from the geometry alone (the placement comes first: the layout follows from it)
         gw = tuple(int(x) for x in lowres_group_info.window_size)
-        g = gw[0] * gw[1] * gw[2]
-        s_low = (S // g) * int(g * (1 - lowres_group_info.reduction_rate))
-        _, _, n_kv = ops.sta_table_sizes(latent_shape, tile_size, window_size, te)
-        cost = [float(S + te) ** 2, float(s_low + te) ** 2, float(S) * n_kv]
+        if partial_geometry() and not divides(latent_shape, tile_size, gw):
+            # a partial geometry: S_low with its remainder tokens, and the true number of (query, key) pairs
+            # of the sliding expert, whose key lists differ in length -- host integers, no table is built for them
+            s_low = coreset_numbers(latent_shape, gw, lowres_group_info.reduction_rate)[3]
+            cost = [float(S + te) ** 2, float(s_low + te) ** 2,
+                    float(sliding_video_pairs(latent_shape, tile_size, window_size) + S * te)]
+        else:
+            g = gw[0] * gw[1] * gw[2]
+            s_low = (S // g) * int(g * (1 - lowres_group_info.reduction_rate))
+            _, _, n_kv = ops.sta_table_sizes(latent_shape, tile_size, window_size, te)
+            cost = [float(S + te) ** 2, float(s_low + te) ** 2, float(S) * n_kv]
     placement, order, counts, parts = place_heads(experts, cost, P, S, dense_only)
     sp_attention.last_placement = placement  # (what a test or a curious caller reads back)
     lay, sb = _layout(H, S, T, D, q.device, q.dtype, counts, extra_slots=len(order) - H)

@@ -8,6 +8,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .. import ops
+from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
 from ..routed import (HeadRouting, dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
                       soft_mixture_attention_autograd)
@@ -182,7 +183,9 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         self.check_input = check_input
 
     def _check_input(self, hidden_states, lowres_group_info, latent_shape, window_size, tile_size):
-        """wan.py:168-193."""
+        """wan.py:168-193.  With partial geometry switched on (set_partial_geometry) the two divisibility
+        conditions fall away for a geometry that does not divide: one whole coreset window per dimension is needed, and a group
+        info built for this latent shape.  A geometry that divides is checked as ever."""
         if not self.check_input:
             return
         seq_length = hidden_states.shape[1] * SP_STATE.sp_size
@@ -190,6 +193,13 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         group_size = lowres_group_info.center_indices.shape[1] + lowres_group_info.margin_indices.shape[1]
         if seq_length != latent_shape[0] * latent_shape[1] * latent_shape[2]:
             raise ValueError(f"Input sequence length {seq_length} does not match latent shape {latent_shape}.")
+        if partial_geometry() and not divides(latent_shape, tile_size, lowres_group_info.window_size):
+            # a partial geometry: the group info must still be the cropped windows of THIS latent shape
+            want = coreset_numbers(latent_shape, lowres_group_info.window_size, lowres_group_info.reduction_rate)[0]
+            if num_groups != want or tuple(lowres_group_info.latent_shape) != tuple(int(x) for x in latent_shape):
+                raise ValueError(f"Low-res info {num_groups}x{group_size} was not built for latent shape {latent_shape} "
+                                 f"({want} whole windows).")
+            return
         for t_size, l_size in zip(tile_size, latent_shape):
             if l_size % t_size != 0:
                 raise ValueError(

@@ -157,9 +157,43 @@ __global__ __launch_bounds__(256) void coreset_select_kernel(const CParams p) {
   }
 }
 
-}  // namespace
+// partial geometry (vorta_coreset_select_partial): the tokens outside the cropped box of whole windows, ascending, and the
+// tail, written behind the G * (1 + n_keep) window entries of the keep lists
+struct RParams {
+  const int32_t* n_heads_dev; int n_heads;
+  int lat[3], crop[3];
+  int per_frame, n_rest, base;  // remainder tokens of a frame inside the crop's frames; C; first position written
+  int tail_first, n_tail;
+  const int32_t* row_map;
+  int32_t* keep_rows; int64_t keep_sh;
+  int32_t* kv_rows; int64_t kv_sh;
+};
 
-extern "C" int vorta_coreset_select(const vorta_coreset_args* a, void* hip_stream) {
+__global__ __launch_bounds__(256) void coreset_rest_kernel(const RParams p) {
+  const int y = blockIdx.y;
+  if (y >= p.n_heads || (p.n_heads_dev && y >= *p.n_heads_dev)) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.n_rest + p.n_tail) return;
+  int tok;
+  if (i >= p.n_rest) {
+    tok = p.tail_first + (i - p.n_rest);
+  } else if (i < p.crop[0] * p.per_frame) {
+    // a frame the crop reaches: per row h < crop[1] the columns [crop[2], W), then the whole rows h >= crop[1]
+    const int f = i / p.per_frame, r = i - f * p.per_frame;
+    const int right = p.lat[2] - p.crop[2];
+    int h, w;
+    if (r < p.crop[1] * right) { h = r / right; w = p.crop[2] + r - h * right; }
+    else { const int r2 = r - p.crop[1] * right; h = p.crop[1] + r2 / p.lat[2]; w = r2 % p.lat[2]; }
+    tok = (f * p.lat[1] + h) * p.lat[2] + w;
+  } else {
+    tok = p.crop[0] * p.lat[1] * p.lat[2] + (i - p.crop[0] * p.per_frame);  // the frames behind the crop, whole
+  }
+  const int row = p.row_map ? p.row_map[tok] : tok;
+  if (p.keep_rows) p.keep_rows[(int64_t)y * p.keep_sh + p.base + i] = row;
+  if (p.kv_rows) p.kv_rows[(int64_t)y * p.kv_sh + p.base + i] = row;
+}
+
+int select(const vorta_coreset_args* a, void* hip_stream, bool partial) {
   if (!a || a->struct_size != sizeof(vorta_coreset_args)) return VORTA_EINVAL;
   if (a->dtype != VORTA_BF16 && a->dtype != VORTA_FP16) return VORTA_EUNSUPPORTED;
   if (a->head_dim != 128) return VORTA_EUNSUPPORTED;
@@ -174,17 +208,21 @@ extern "C" int vorta_coreset_select(const vorta_coreset_args* a, void* hip_strea
     if (a->latent[i] <= 0 || a->group[i] <= 0) return VORTA_EINVAL;
     // the reference crops partial windows (coreset_select.py:40) but its callers require an exact fit
     // (hunyuan.py:269-272): cropped tokens would never be written by the fused unpool, so refuse them
-    if (a->latent[i] % a->group[i]) return VORTA_EINVAL;
+    if (!partial && a->latent[i] % a->group[i]) return VORTA_EINVAL;
+    if (a->latent[i] < a->group[i]) return VORTA_EINVAL;  // no whole window (partial: G = 0)
     p.lat[i] = a->latent[i]; p.grp[i] = a->group[i]; p.ng[i] = a->latent[i] / a->group[i];
     p.g *= a->group[i]; p.n_groups *= p.ng[i];
   }
   if (p.g > MAX_G || p.g < 2) return VORTA_EUNSUPPORTED;
+  const int64_t n_tokens = (int64_t)p.lat[0] * p.lat[1] * p.lat[2];
+  if (partial && (n_tokens + a->n_tail > 0x7fffffff || a->n_heads > 65535)) return VORTA_EINVAL;  // before any launch
   if (a->n_keep < 0 || a->n_keep > p.g - 1 || a->n_tail < 0) return VORTA_EINVAL;
   p.centre = (p.grp[0] / 2) * p.grp[1] * p.grp[2] + (p.grp[1] / 2) * p.grp[2] + p.grp[2] / 2;
   p.n_keep = a->n_keep;
   p.x = (const char*)a->x.ptr; p.x_sh = a->x.stride_h * 2; p.x_ss = a->x.stride_s * 2;
   p.head_list = a->head_list; p.n_heads_dev = a->n_heads_dev; p.n_heads = a->n_heads;
-  p.tail_first = a->tail_first; p.n_tail = a->n_tail; p.row_map = a->row_map;
+  // partial: the tail follows the remainder tokens, both written by coreset_rest_kernel
+  p.tail_first = a->tail_first; p.n_tail = partial ? 0 : a->n_tail; p.row_map = a->row_map;
   p.keep_rows = a->keep_rows; p.keep_sh = a->keep_rows_stride_h;
   p.drop_rows = a->drop_rows; p.drop_sh = a->drop_rows_stride_h;
   p.kv_rows = a->keep_rows_kv; p.kv_sh = a->keep_rows_kv_stride_h;
@@ -196,6 +234,25 @@ extern "C" int vorta_coreset_select(const vorta_coreset_args* a, void* hip_strea
     hipLaunchKernelGGL(coreset_select_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, p);
   else
     hipLaunchKernelGGL(coreset_select_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, p);
+  if (partial) {
+    RParams r{};
+    for (int i = 0; i < 3; ++i) { r.lat[i] = p.lat[i]; r.crop[i] = p.ng[i] * p.grp[i]; }
+    r.per_frame = p.lat[1] * p.lat[2] - r.crop[1] * r.crop[2];
+    r.n_rest = (int)(n_tokens - (int64_t)p.n_groups * p.g);
+    r.base = p.n_groups * (1 + p.n_keep);
+    r.n_heads_dev = p.n_heads_dev; r.n_heads = p.n_heads;
+    r.tail_first = a->tail_first; r.n_tail = a->n_tail; r.row_map = a->row_map;
+    r.keep_rows = p.keep_rows; r.keep_sh = p.keep_sh; r.kv_rows = p.kv_rows; r.kv_sh = p.kv_sh;
+    const int n = r.n_rest + r.n_tail;
+    if (n > 0)
+      hipLaunchKernelGGL(coreset_rest_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)p.n_heads), dim3(256), 0, st, r);
+  }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
 }
+
+}  // namespace
+
+extern "C" int vorta_coreset_select(const vorta_coreset_args* a, void* hip_stream) { return select(a, hip_stream, false); }
+
+extern "C" int vorta_coreset_select_partial(const vorta_coreset_args* a, void* hip_stream) { return select(a, hip_stream, true); }

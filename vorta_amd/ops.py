@@ -639,16 +639,22 @@ def coreset_select(x: torch.Tensor, latent: Sequence[int], group: Sequence[int],
                    head_list: Optional[torch.Tensor] = None, n_heads: Optional[int] = None,
                    n_heads_dev: Optional[torch.Tensor] = None, tail_first: int = 0, n_tail: int = 0,
                    row_map: Optional[torch.Tensor] = None, want_drop: bool = True, want_keep: bool = True,
-                   want_kv: bool = False):
+                   want_kv: bool = False, partial: bool = False):
     """vorta_coreset_select: returns keep_rows (slots, G*(1+n_keep)+n_tail) [packed: centres, kept margins, tail] and
     drop_rows (slots, G, g-1-n_keep); with `want_kv` a third tensor, the same rows in group-major ascending order (the
-    key-side list: order is free there and neighbours in memory stay neighbours in the list)."""
+    key-side list: order is free there and neighbours in memory stay neighbours in the list).
+    `partial`: vorta_coreset_select_partial -- the G = prod(latent // group) whole windows, then the C = S - G*g tokens
+    outside their box, ascending, then the tail: keep_rows (slots, G*(1+n_keep) + C + n_tail)."""
     _require_gpu(x)
     if n_heads is None:
         n_heads = head_list.numel() if head_list is not None else x.shape[0]
     g = group[0] * group[1] * group[2]
     G = (latent[0] // group[0]) * (latent[1] // group[1]) * (latent[2] // group[2])
     n_list = G * (1 + n_keep) + n_tail
+    if partial:
+        if G == 0:
+            raise ValueError(f"Low-res window {tuple(group)} holds no whole window in latent shape {tuple(latent)}.")
+        n_list += latent[0] * latent[1] * latent[2] - G * g
     keep = torch.empty((n_heads, n_list), dtype=torch.int32, device=x.device) if want_keep else None
     kv = torch.empty((n_heads, n_list), dtype=torch.int32, device=x.device) if want_kv else None
     drop = torch.empty((n_heads, G, g - 1 - n_keep), dtype=torch.int32, device=x.device) if want_drop else None
@@ -667,7 +673,8 @@ def coreset_select(x: torch.Tensor, latent: Sequence[int], group: Sequence[int],
         a.keep_rows_kv, a.keep_rows_kv_stride_h = kv.data_ptr(), kv.stride(0)
     if drop is not None:
         a.drop_rows, a.drop_rows_stride_h = drop.data_ptr(), drop.stride(0)
-    _C.check(_C.lib().vorta_coreset_select(C.byref(a), _stream()), "vorta_coreset_select")
+    name = "vorta_coreset_select_partial" if partial else "vorta_coreset_select"
+    _C.check(getattr(_C.lib(), name)(C.byref(a), _stream()), name)
     return (keep, drop, kv) if want_kv else (keep, drop)
 
 
@@ -701,6 +708,45 @@ def sta_build_tables(latent, tile, window, t_eff: int, device, row_map: Optional
     with torch.cuda.device(dev):
         _C.check(_C.lib().vorta_sta_build_tables(C.byref(a), _stream()), "vorta_sta_build_tables")
     return q_rows, kv_rows
+
+
+def _sta_args(latent, tile, window, t_eff: int):
+    a = _C.StaArgs()
+    a.struct_size = C.sizeof(_C.StaArgs)
+    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
+    a.t_eff = t_eff
+    return a
+
+
+def sta_partial_sizes(latent, tile, window, t_eff: int = 0) -> Tuple[int, int, int, list]:
+    """vorta_sta_partial_sizes: (n_tiles, n_lists, list_stride, [n_kv of every distinct key list]) of a tile that need not
+    divide the latent grid -- host-only geometry query (works without a GPU)."""
+    a = _sta_args(latent, tile, window, t_eff)
+    nt, nl, st = C.c_int32(), C.c_int32(), C.c_int32()
+    fn = _C.lib().vorta_sta_partial_sizes
+    _C.check(fn(C.byref(a), C.byref(nt), C.byref(nl), C.byref(st), None, 0), "vorta_sta_partial_sizes")
+    lens = (C.c_int32 * nl.value)()
+    _C.check(fn(C.byref(a), None, None, None, lens, nl.value), "vorta_sta_partial_sizes")
+    return nt.value, nl.value, st.value, list(lens)
+
+
+def sta_build_tables_partial(latent, tile, window, t_eff: int, device, row_map: Optional[torch.Tensor] = None
+                             ) -> Tuple[torch.Tensor, torch.Tensor, list]:
+    """vorta_sta_build_tables_partial: q_rows (S,) in partial tile-major order, kv_rows (n_lists, list_stride) with one row
+    per distinct key list (list (f0, f1, f2) = the first tile of the clamped window, raster order) and the lists' lengths."""
+    _, n_lists, stride, lens = sta_partial_sizes(latent, tile, window, t_eff)
+    S = latent[0] * latent[1] * latent[2]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _C.VortaHipError("sta_build_tables_partial needs a cuda device")
+    q_rows = torch.empty(S, dtype=torch.int32, device=dev)
+    kv_rows = torch.empty((n_lists, stride), dtype=torch.int32, device=dev)
+    a = _sta_args(latent, tile, window, t_eff)
+    a.row_map = _ptr(row_map)
+    a.q_rows, a.kv_rows = q_rows.data_ptr(), kv_rows.data_ptr()
+    with torch.cuda.device(dev):
+        _C.check(_C.lib().vorta_sta_build_tables_partial(C.byref(a), _stream()), "vorta_sta_build_tables_partial")
+    return q_rows, kv_rows, lens
 
 
 def router_route(temb: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, heads: int, tau: float,

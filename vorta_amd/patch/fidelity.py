@@ -22,6 +22,7 @@ from typing import Any, Dict, Mapping, Optional, Tuple, Union
 import torch
 from torch import nn
 
+from .. import _partial
 from ..ops import ExpertFidelity
 from ._engine import context_of
 
@@ -75,8 +76,8 @@ def fidelity_of(model: nn.Module) -> ExpertFidelity:
 Geometry = Union[Mapping[str, Any], Any]
 
 
-def _geometry_numbers(geometry: Geometry) -> Tuple[int, int, int, int]:
-    """(S, S_low, tokens per tile, keys a sliding-tile query sees among the video tokens) of a `routed.RoutedGeometry` or of
+def _geometry_numbers(geometry: Geometry) -> Tuple[int, int, int, float]:
+    """(S, S_low, tokens per full tile, keys a sliding-tile query sees among the video tokens) of a `routed.RoutedGeometry` or of
     a mapping with latent / tile / window / group / rate (or the self_attention_kwargs spelling: latent_shape, tile_size,
     window_size, lowres_group_info)"""
     if isinstance(geometry, Mapping):
@@ -87,14 +88,20 @@ def _geometry_numbers(geometry: Geometry) -> Tuple[int, int, int, int]:
         info = g.get("lowres_group_info")
         group = g.get("group", None if info is None else info.window_size)
         rate = g.get("rate", None if info is None else info.reduction_rate)
+        partial = _partial.partial_geometry()  # a mapping follows the process-wide switch, as the geometry it names would
     else:
+        partial = getattr(geometry, "is_partial", False)
         latent, tile, window, group, rate = geometry.latent, geometry.tile, geometry.window, geometry.group, geometry.rate
     if any(x is None for x in (latent, tile, window, group, rate)):
         raise ValueError("geometry needs latent, tile, window, group and rate")
     S = int(latent[0]) * int(latent[1]) * int(latent[2])
+    tok = int(tile[0]) * int(tile[1]) * int(tile[2])
+    if partial and not _partial.divides(latent, tile, group):
+        # a partial geometry (with the switch off the figures stay what they were): S_low counts the remainder tokens, and the sliding keys differ per query tile --
+        # their mean over the video queries, so that S * keys is the true number of (query, key) pairs
+        return S, _partial.coreset_numbers(latent, group, rate)[3], tok, _partial.sliding_video_pairs(latent, tile, window) / S
     gsz = int(group[0]) * int(group[1]) * int(group[2])
     s_low = (S // gsz) * int(gsz * (1 - float(rate)))
-    tok = int(tile[0]) * int(tile[1]) * int(tile[2])
     n_kv = 1
     for l, t, w in zip(latent, tile, window):
         n_kv *= min(int(l) // int(t), int(w))

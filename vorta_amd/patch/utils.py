@@ -3,15 +3,23 @@ from typing import Any, Dict, Optional, Tuple
 
 import torch
 
+from .._partial import check_windows, partial_geometry
 from ..attention import create_sliding_tile_attn_mask_func, get_group_info
 
 
 def validate_geometry(kw: Dict[str, Any]) -> None:
     """Fail at configuration time, with the messages the processors raise at the first forward
     (hunyuan.py:260-272), when the `self_attention_kwargs` of a checkpoint's config.json do not fit the latent grid
-    of the requested video size: the published (6,9,8)/(2,3,2) geometry fits 117 frames, not 129."""
+    of the requested video size: the published (6,9,8)/(2,3,2) geometry fits 117 frames, not 129.
+    With partial geometry switched on (vorta_amd.set_partial_geometry / VORTA_PARTIAL_GEOMETRY=1) such a geometry is
+    accepted -- thin last tiles, cropped coreset windows plus remainder tokens (DESIGN.md "Partial geometry") -- and only a
+    coreset window larger than the grid is refused."""
     latent = tuple(int(v) for v in kw["latent_shape"])
     tile = tuple(int(v) for v in kw.get("tile_size", (1, 1, 1)))
+    if partial_geometry():
+        if kw.get("lowres_window_size") is not None:
+            check_windows(latent, kw["lowres_window_size"])
+        return
     for t_size, l_size in zip(tile, latent):
         if l_size % t_size != 0:
             raise ValueError(f"Tile size {tile} (dim={t_size}) does not divide latent shape {latent} (dim={l_size}).")

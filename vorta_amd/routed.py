@@ -2,7 +2,8 @@
 
 Takes post-RoPE q,k,v (B,H,S[+T],D) and a head->expert assignment and enqueues, on the current stream,
 at most:  1 launch for the full-attention heads, 2 selects + 1 launch for the coreset heads, and 1 (+1 for
-Hunyuan's text queries) launch for the sliding-tile heads.  Every launch reads the original q,k,v through
+Hunyuan's text queries) launch for the sliding-tile heads -- on a partial geometry (a tile that does not divide the
+latent grid) one per key-list length, up to eight.  Every launch reads the original q,k,v through
 head lists and row tables and writes its heads directly into the final output: the reference's per-expert
 head gathers (hunyuan.py:612-640), pooled copies (coreset_select.py:68-124), tile/untile permutes
 (tile.py) and boolean index-put (hunyuan.py:642-661) have no counterpart here.
@@ -14,7 +15,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
+from . import _partial, ops
+from ._partial import partial_geometry, set_partial_geometry  # noqa: F401  (the switch: re-exported)
 
 Triple = Tuple[int, int, int]
 
@@ -80,12 +82,28 @@ class RoutedGeometry:
     device: torch.device
     row_map: Optional[torch.Tensor] = None  # zero-copy Ulysses layout (ulysses.py); None = plain (H,S,D)
     _sta: Dict[int, Tuple[torch.Tensor, torch.Tensor, int]] = field(default_factory=dict)
+    # accept a tile / coreset window that does not divide the latent grid (DESIGN.md "Partial geometry"); None = the
+    # process-wide switch (set_partial_geometry / VORTA_PARTIAL_GEOMETRY).  A geometry that divides is built as ever.
+    partial: Optional[bool] = None
 
     def __post_init__(self):
         self.latent, self.tile, self.window, self.group = (tuple(int(v) for v in x) for x in
                                                            (self.latent, self.tile, self.window, self.group))
         self.S = self.latent[0] * self.latent[1] * self.latent[2]
         self.g = self.group[0] * self.group[1] * self.group[2]
+        self.partial = partial_geometry() if self.partial is None else bool(self.partial)
+        # is_partial: the tables, launches and lists below differ from the dividing ones only then
+        self.is_partial = self.partial and not _partial.divides(self.latent, self.tile, self.group)
+        self.n_keep = int(self.g * (1 - self.rate)) - 1  # coreset_select.py:54
+        # the distinct VIDEO key counts of the sliding expert's key lists, longest first (one where the tile divides)
+        self.sta_class_n_kv = _partial.sliding_key_counts(self.latent, self.tile, self.window)
+        if self.is_partial:
+            # G: the whole windows the reference keeps when it crops (coreset_select.py:36-40); C: the tokens outside the
+            # cropped box -- full resolution, never duplicated
+            self.G, _, self.C, self.S_low = _partial.coreset_numbers(self.latent, self.group, self.rate)
+            self.tok = None  # tiles differ in size
+            return
+        self.C = 0
         for l, t in zip(self.latent, self.tile):
             if l % t:
                 # same condition and exception type as hunyuan.py:264-267
@@ -95,12 +113,54 @@ class RoutedGeometry:
             self.G *= l // w
         if self.S != self.G * self.g:
             raise ValueError(f"Input sequence length {self.S} does not match low-res info {self.G}x{self.g}.")
-        self.n_keep = int(self.g * (1 - self.rate)) - 1  # coreset_select.py:54
         self.S_low = self.G * (1 + self.n_keep)
         self.tok = self.tile[0] * self.tile[1] * self.tile[2]
 
+    def sta_partial_launches(self, t_eff: int, block_rows: int = 256):
+        """The sliding-tile expert on a partial geometry: one merged launch per key-list LENGTH (the attention kernel takes
+        one n_kv per launch).  Query tiles of equal key lists form a group, as in `sta_launch_tables`; the groups of one
+        length class are one launch with its own q_rows, key lists and block table, longest class first.  Together the
+        classes hold every query position once (tiles partition the grid, a tile has one key list, a list one length).
+        Returns a list of (q_rows (n_q,), kv_lists (n_lists, stride), stride, n_kv, block_table, n_lists)."""
+        key = ("partial", t_eff, block_rows)
+        if key not in self._sta:
+            q_rows, kv_rows, lens = ops.sta_build_tables_partial(self.latent, self.tile, self.window, t_eff, self.device,
+                                                                 row_map=self.row_map)
+            stride = kv_rows.shape[1]
+            nt, cnt, first = _partial.window_geometry(self.latent, self.tile, self.window)
+            nf = [n - c + 1 for n, c in zip(nt, cnt)]
+            thick = [[min(self.tile[d], self.latent[d] - i * self.tile[d]) for i in range(nt[d])] for d in range(3)]
+            by_list: Dict[int, list] = {}  # key list -> [(first position, tokens)] of its tiles, tile-major
+            start = 0
+            for a in range(nt[0]):
+                for b in range(nt[1]):
+                    for c in range(nt[2]):
+                        n = thick[0][a] * thick[1][b] * thick[2][c]
+                        lid = (first[0][a] * nf[1] + first[1][b]) * nf[2] + first[2][c]
+                        by_list.setdefault(lid, []).append((start, n))
+                        start += n
+            assert start == self.S
+            launches = []
+            for n_kv in sorted({lens[l] for l in by_list}, reverse=True):
+                lids = sorted(l for l in by_list if lens[l] == n_kv)
+                pos, rows, p0 = [], [], 0
+                for g, l in enumerate(lids):
+                    end = p0 + sum(n for _, n in by_list[l])
+                    pos += [torch.arange(s, s + n) for s, n in by_list[l]]
+                    rows += [(g, p, min(p + block_rows, end)) for p in range(p0, end, block_rows)]
+                    p0 = end
+                q_c = q_rows[torch.cat(pos).to(self.device)].contiguous()
+                lists = kv_rows[torch.tensor(lids, device=self.device)].contiguous()
+                table = torch.tensor(rows, dtype=torch.int32).to(self.device)
+                launches.append((q_c, lists, stride, n_kv, table, len(lids)))
+            assert sum(x[0].numel() for x in launches) == self.S
+            self._sta[key] = launches
+        return self._sta[key]
+
     def sta_tables(self, t_eff: int):
         """per query tile: (q_rows (S,), kv_rows (n_tiles, n_kv), n_kv) -- vorta_sta_build_tables"""
+        if self.is_partial:
+            raise ValueError("a partial geometry has no per-tile table of one length: sta_partial_launches")
         if t_eff not in self._sta:
             q_rows, kv_rows = ops.sta_build_tables(self.latent, self.tile, self.window, t_eff, self.device,
                                                    row_map=self.row_map)
@@ -111,6 +171,9 @@ class RoutedGeometry:
         """Build (on the CURRENT stream) every lazily cached device table a routed call with this text length may touch.
         Callers that enqueue routed_attention on several streams call this before they fork: a table built inside one
         stream's call is not ordered against another stream's first use of the cached object."""
+        if self.is_partial:
+            self.sta_partial_launches(t_eff, block_rows if block_rows in (128, 256) else 256)
+            return
         self.sta_tables(t_eff)
         if STA_MERGE and block_rows in (128, 256):
             self.sta_launch_tables(t_eff, block_rows)
@@ -126,13 +189,8 @@ class RoutedGeometry:
         if key not in self._sta:
             q_rows, kv_rows, n_kv = self.sta_tables(t_eff)
             n_tiles = kv_rows.shape[0]
-            # a tile's key list is fixed by the first tile of its clamped window in every dimension
-            # (csrc/sta_tables.hip: centre = min(max(t, half), n - 1 - half), first = max(centre - half, 0)): host integers
-            nt = [l // t for l, t in zip(self.latent, self.tile)]
-            first = []
-            for d in range(3):
-                half = self.window[d] // 2
-                first.append([max(min(max(t, half), nt[d] - 1 - half) - half, 0) for t in range(nt[d])])
+            # a tile's key list is fixed by the first tile of its clamped window in every dimension: host integers
+            nt, _, first = _partial.window_geometry(self.latent, self.tile, self.window)
             ids = [(first[0][a], first[1][b], first[2][c]) for a in range(nt[0]) for b in range(nt[1]) for c in range(nt[2])]
             order = sorted(range(n_tiles), key=lambda i: ids[i])  # stable: tile-major order kept inside a group
             groups = []  # (first tile of the group, number of tiles)
@@ -375,15 +433,16 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         # key side: the same rows as the reference's packed [centres | margins] list (coreset_select.py:116-124) in
         # group-major ascending order -- softmax does not see the order of the keys, the K/V gather does
         gm = CORESET_KV_GROUP_MAJOR
+        pk = dict(partial=True) if geom.is_partial else {}  # + the remainder tokens, before the text (vorta_coreset_select_partial)
         if hy:  # K matched on its own, V follows K (hunyuan.py:433-438)
             keep_q, drop_q = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T,
-                                                row_map=rm, **sl)
+                                                row_map=rm, **pk, **sl)
             kk = ops.coreset_select(k3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=te, row_map=rm,
-                                    want_drop=False, want_keep=not gm, want_kv=gm, **sl)
+                                    want_drop=False, want_keep=not gm, want_kv=gm, **pk, **sl)
             keep_k = kk[2] if gm else kk[0]
         else:   # K and V follow Q's matching (wan.py:250-255): one selection, both lists
             kq = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm,
-                                    want_kv=gm, **sl)
+                                    want_kv=gm, **pk, **sl)
             keep_q, drop_q = kq[0], kq[1]
             keep_k = kq[2] if gm else keep_q
         return [dict(base, out=o_e[1], n_q=geom.S_low + T, n_kv=geom.S_low + te, q_valid=geom.S_low + te, q_rows=keep_q,
@@ -393,7 +452,14 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     # ---- expert 2: sliding-tile attention (hunyuan.py:459-507 / wan.py:272-294) ----
     def expert_sliding():
         sl = slot_of(2, H)
-        if STA_MERGE and sliding_block_rows in (128, 256):
+        if geom.is_partial:
+            # always the merged form, one launch per key-list length (RoutedGeometry.sta_partial_launches)
+            br = sliding_block_rows if sliding_block_rows in (128, 256) else 256
+            calls = [dict(base, out=o_e[2], n_q=q_rows.numel(), n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows,
+                          kv_rows_stride_g=stride, q_block_table=table, n_key_lists=n_lists, tag="sliding",
+                          flops=nheads(2) * 4.0 * D * q_rows.numel() * n_kv, block_rows=br, **sl)
+                     for q_rows, kv_rows, stride, n_kv, table, n_lists in geom.sta_partial_launches(te, br)]
+        elif STA_MERGE and sliding_block_rows in (128, 256):
             q_rows, kv_rows, n_kv, table, n_lists = geom.sta_launch_tables(te, sliding_block_rows)
             calls = [dict(base, out=o_e[2], n_q=S, n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=n_kv,
                           q_block_table=table, n_key_lists=n_lists, tag="sliding", flops=nheads(2) * 4.0 * D * S * n_kv,
@@ -422,6 +488,14 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             calls.append(txt)
         return calls
 
+    def launch_fused(calls):
+        # a partial geometry may bring more launches than one grid takes (up to eight sliding classes): consecutive fused
+        # grids in list order.  Every launch writes rows of its own, so the grouping does not show in the result
+        if record is not None:
+            record.extend(calls)
+        for i in range(0, max(len(calls), 1), ops.MAX_FUSED):
+            ops.attn_fwd_batch(calls[i:i + ops.MAX_FUSED])
+
     def launch(calls):
         if record is not None:
             record.extend(calls)
@@ -445,18 +519,14 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             slot_part = lambda i, hl, which=which: pparts[i][which]  # noqa: E731
             calls = [c for fn, on in experts if on for c in fn()]
             if fused:
-                if record is not None:
-                    record.extend(calls)
-                ops.attn_fwd_batch(calls)
+                launch_fused(calls)
             else:
                 launch(calls)
         return out
     if not concurrent:
         calls = [c for fn, on in experts if on for c in fn()]
         if fused:
-            if record is not None:
-                record.extend(calls)
-            ops.attn_fwd_batch(calls)
+            launch_fused(calls)
         else:
             launch(calls)
         return out
@@ -748,13 +818,16 @@ _GEOMETRY_CACHE: Dict[tuple, RoutedGeometry] = {}
 _GEOMETRY_CACHE_MAX = 48
 
 
-def geometry_for(latent, tile, window, group, rate, device, row_map: Optional[torch.Tensor] = None) -> RoutedGeometry:
-    """Process-wide cache: the tables are built once per geometry, not once per layer call."""
+def geometry_for(latent, tile, window, group, rate, device, row_map: Optional[torch.Tensor] = None,
+                 partial: Optional[bool] = None) -> RoutedGeometry:
+    """Process-wide cache: the tables are built once per geometry, not once per layer call.
+    `partial`: as RoutedGeometry's (None = the process-wide switch, read here)."""
+    partial = partial_geometry() if partial is None else bool(partial)
     key = (tuple(latent), tuple(tile), tuple(window), tuple(group), float(rate), str(device),
-           None if row_map is None else (row_map.data_ptr(), row_map.numel()))
+           None if row_map is None else (row_map.data_ptr(), row_map.numel()), partial)
     g = _GEOMETRY_CACHE.pop(key, None)
     if g is None:
-        g = RoutedGeometry(latent, tile, window, group, rate, torch.device(device), row_map=row_map)
+        g = RoutedGeometry(latent, tile, window, group, rate, torch.device(device), row_map=row_map, partial=partial)
         # bounded: a geometry holds its sliding-tile tables (13 MB at Hunyuan-129f) and, under sequence parallelism, there is one
         # per distinct slot count of a rank (slot groups and uneven placements: up to ~2 H / P of them per resolution); the least
         # recently used one goes when a process has seen more than this many (the row maps they are keyed on are never freed)
