@@ -50,7 +50,9 @@ extern "C" {
                                    and the per-head expert fidelity, vorta_expert_fidelity (a pure addition: a binding asks for
                                    the symbol and for vorta_fidelity_args_size())
                                    and partial geometry, vorta_sta_partial_sizes / vorta_sta_build_tables_partial /
-                                   vorta_coreset_select_partial (three more symbols on the existing argument blocks) */
+                                   vorta_coreset_select_partial (three more symbols on the existing argument blocks)
+                                   and the routed output's fidelity on sampled rows, vorta_sampled_fidelity (a pure addition: a
+                                   binding asks for the symbol and for vorta_sampled_fidelity_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -768,6 +770,66 @@ typedef struct vorta_fidelity_args {
 
 int vorta_expert_fidelity(const vorta_fidelity_args* args, void* hip_stream);
 int vorta_fidelity_args_size(void);
+
+/*
+ * vorta_sampled_fidelity (ABI 9, a pure addition: a binding asks for the symbol and for vorta_sampled_fidelity_args_size();
+ * vorta_sizeof keeps its 17 indices) -- how far the output a ROUTED call wrote is from dense attention, per head, on a sample of
+ * n_rows query rows: `ref` holds the dense reference rows compactly, `out` is the routed output read in place, rows[p] the
+ * physical row of `out` that sample position p names (a caller under sequence parallelism composes it with vorta_seq_row_map's
+ * table).  The reference has no such measurement.  For head slot y < n_heads (< *n_heads_dev when given), head h = head_list ?
+ * head_list[y] : y, over the n_rows x 128 elements  x0 = ref[h][p][:],  t = out[h][rows[p]][:]:
+ *     sq_ref[h] = sum x0^2     max_ref[h] = max |x0|     range_ref[h] = max x0 - min x0 (optional)
+ *     sq_err[h] = sum d^2      max_err[h] = max |d|      d = fl(t - x0)
+ *     row_sq_err[h * n_rows + p] = the sum of row p's 128 d^2 (optional: where in the clip a head is off)
+ * all float32, indexed by the HEAD, not by the slot: heads the launch does not name, and slots at or past *n_heads_dev, keep
+ * what the caller's buffers held.  head_list names distinct heads.  Row addresses are 64-bit: head * stride_h + rows[p] *
+ * stride_s; the row VALUES live on the device and are the caller's contract, as for the attention kernels' tables.
+ * ARITHMETIC, NaN / Inf rule: vorta_expert_fidelity's, with x0 = ref and one error column (values widened exactly, one float32
+ * rounding of the difference, float32 squares and sums, exact maxima; a NaN, or an Inf that meets an Inf, makes the sums AND the
+ * maxima it reaches NaN, for that head only).
+ * DETERMINISTIC: VORTA_SAMPLED_FIDELITY_PARTS partials per head slot over the fixed ranges of sample positions [b per, (b + 1)
+ * per), per = ceil(n_rows / PARTS); a 16-lane quarter wave owns every 16th row of a range, 16 bytes a lane, the next row's
+ * loads in flight; lanes meet by shuffles, the four waves through LDS, the partial goes to the workspace with plain vector
+ * stores and a second launch joins a slot's parts as a fixed shuffle tree.  No float atomic; the same bits on every run and stream.
+ * (16 parts: at n_rows = 2048 a head is 512 KiB a tensor -- 128 rows a workgroup, 8 visits a lane; 24 heads give 384 workgroups.)
+ * LONGEST CHAIN of float32 roundings a sum passes through = VORTA_SAMPLED_FIDELITY_CHAIN(n_rows):
+ *     2 (the rounded difference, squared) + 4 (a row's 8 squares: d^2, one fma, two tree levels) + V (one add per row a lane
+ *     visits, V = ceil(per / 16)) + 6 (wave shuffles) + 2 (four waves) + 4 (16 parts) + 1 (the linear bound's slack, n <= 4096)
+ * and every term is non-negative: |sum - exact| <= CHAIN 2^-24 exact.  n_rows = 2048: 27, i.e. 1.6e-6.  A row's sum takes
+ * VORTA_SAMPLED_FIDELITY_ROW_CHAIN = 2 + 4 + 4 (the quarter wave's shuffles) + 1 roundings.
+ * Error codes as for vorta_expert_fidelity: VORTA_EINVAL for a wrong struct_size, negative sizes, a null or misaligned output
+ * (4 bytes), row table (4 bytes; null only with n_rows == 0), head list or device count (4 bytes) or workspace (16 bytes), a null
+ * or misaligned tensor (16-byte aligned rows; null only with n_rows == 0); VORTA_EUNSUPPORTED for a dtype other than bf16 / fp16
+ * or head_dim != 128.  Everything is looked at before anything is launched.  n_heads == 0 is VORTA_OK and launches nothing;
+ * n_rows == 0 is VORTA_OK and writes zeros for the listed heads.
+ */
+#define VORTA_SAMPLED_FIDELITY_PARTS 16
+#define VORTA_SAMPLED_FIDELITY_WS_FLOATS 8 /* per head slot and part */
+#define VORTA_SAMPLED_FIDELITY_CHAIN(n_rows) \
+  (((((int64_t)(n_rows) + VORTA_SAMPLED_FIDELITY_PARTS - 1) / VORTA_SAMPLED_FIDELITY_PARTS + 15) / 16) + 19)
+#define VORTA_SAMPLED_FIDELITY_ROW_CHAIN 11
+typedef struct vorta_sampled_fidelity_args {
+  uint32_t struct_size; /* = sizeof(vorta_sampled_fidelity_args) = vorta_sampled_fidelity_args_size() */
+  int32_t dtype, head_dim;
+  int32_t n_heads;            /* head slots in this launch (upper bound when n_heads_dev is set) */
+  int32_t n_rows;             /* the sample size n */
+  int32_t reserved;
+  vorta_tensor ref;           /* (H, n_rows, D): the dense reference rows, indexed by the head */
+  vorta_tensor out;           /* (H, S[+T], D) view of the routed output, dtype of ref, read in place */
+  const int32_t* rows;        /* [n_rows]: the physical row of `out` for sample position p */
+  const int32_t* head_list;   /* [n_heads] or NULL */
+  const int32_t* n_heads_dev; /* optional device count: slots >= *n_heads_dev write nothing */
+  float* sq_ref;              /* out, indexed by the head */
+  float* max_ref;             /* out, indexed by the head */
+  float* sq_err;              /* out, indexed by the head */
+  float* max_err;             /* out, indexed by the head */
+  float* range_ref;           /* out, indexed by the head, or NULL */
+  float* row_sq_err;          /* out [head][n_rows], or NULL */
+  float* ws;                  /* workspace, n_heads * PARTS * WS_FLOATS floats, 16-byte aligned (caller-owned) */
+} vorta_sampled_fidelity_args;
+
+int vorta_sampled_fidelity(const vorta_sampled_fidelity_args* args, void* hip_stream);
+int vorta_sampled_fidelity_args_size(void);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.

@@ -178,6 +178,15 @@ class FidelityArgs(C.Structure):
     ]
 
 
+class SampledFidelityArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("n_heads", _i32), ("n_rows", _i32), ("reserved", _i32),
+        ("ref", Tensor), ("out", Tensor), ("rows", _vp), ("head_list", _vp), ("n_heads_dev", _vp),
+        ("sq_ref", _vp), ("max_ref", _vp), ("sq_err", _vp), ("max_err", _vp), ("range_ref", _vp), ("row_sq_err", _vp),
+        ("ws", _vp),
+    ]
+
+
 MIX_BWD_PARTS = 64  # include/vorta_hip.h VORTA_MIX_BWD_PARTS
 NORM_ROPE_BWD_PARTS = 1024  # include/vorta_hip.h VORTA_NORM_ROPE_BWD_PARTS
 FIDELITY_PARTS, FIDELITY_WS_FLOATS = 64, 12  # include/vorta_hip.h VORTA_FIDELITY_PARTS, VORTA_FIDELITY_WS_FLOATS
@@ -186,6 +195,16 @@ FIDELITY_PARTS, FIDELITY_WS_FLOATS = 64, 12  # include/vorta_hip.h VORTA_FIDELIT
 def fidelity_chain(n_rows: int) -> int:
     """include/vorta_hip.h VORTA_FIDELITY_CHAIN: the longest chain of float32 roundings a sum of vorta_expert_fidelity passes through"""
     return ((n_rows + FIDELITY_PARTS - 1) // FIDELITY_PARTS + 15) // 16 + 21
+
+# include/vorta_hip.h VORTA_SAMPLED_FIDELITY_PARTS, VORTA_SAMPLED_FIDELITY_WS_FLOATS, VORTA_SAMPLED_FIDELITY_ROW_CHAIN
+SAMPLED_FIDELITY_PARTS, SAMPLED_FIDELITY_WS_FLOATS, SAMPLED_FIDELITY_ROW_CHAIN = 16, 8, 11
+
+
+def sampled_fidelity_chain(n_rows: int) -> int:
+    """include/vorta_hip.h VORTA_SAMPLED_FIDELITY_CHAIN: the longest chain of float32 roundings a sum of vorta_sampled_fidelity
+    passes through"""
+    return ((n_rows + SAMPLED_FIDELITY_PARTS - 1) // SAMPLED_FIDELITY_PARTS + 15) // 16 + 19
+
 
 # every symbol include/vorta_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -228,6 +247,8 @@ SYMBOLS = {
     "vorta_cast_grads": (C.c_int, [C.POINTER(CastArgs), _vp]),
     "vorta_expert_fidelity": (C.c_int, [C.POINTER(FidelityArgs), _vp]),
     "vorta_fidelity_args_size": (C.c_int, []),
+    "vorta_sampled_fidelity": (C.c_int, [C.POINTER(SampledFidelityArgs), _vp]),
+    "vorta_sampled_fidelity_args_size": (C.c_int, []),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "vorta_permute_heads": (C.c_int, [C.POINTER(PermuteArgs), _vp]),
     "vorta_abi_version": (C.c_int, []),
@@ -265,8 +286,8 @@ def lib():
         try:
             fn = getattr(h, name)
         except AttributeError:
-            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity and the
-            # partial-geometry entry points without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity, the
+            # partial-geometry entry points and vorta_sampled_fidelity without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
@@ -286,6 +307,9 @@ def lib():
     if h.vorta_fidelity_args_size() != C.sizeof(FidelityArgs):
         raise VortaHipError(f"struct layout mismatch for FidelityArgs: C {h.vorta_fidelity_args_size()} "
                             f"vs ctypes {C.sizeof(FidelityArgs)}")
+    if h.vorta_sampled_fidelity_args_size() != C.sizeof(SampledFidelityArgs):
+        raise VortaHipError(f"struct layout mismatch for SampledFidelityArgs: C {h.vorta_sampled_fidelity_args_size()} "
+                            f"vs ctypes {C.sizeof(SampledFidelityArgs)}")
     _lib = h
     return h
 

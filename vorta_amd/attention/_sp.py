@@ -126,9 +126,15 @@ def place_heads(experts, cost, P: int, S: int, dense_only: bool = False, placeme
 
 def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_sparse: Optional[float], *, model: str,
                  text_valid: int = 0, attention_mask=None, lowres_group_info=None, window_size=(3, 3, 3),
-                 tile_size=(6, 8, 8), latent_shape=None, experts_host=None) -> torch.Tensor:
+                 tile_size=(6, 8, 8), latent_shape=None, experts_host=None, fidelity: Optional[list] = None,
+                 fidelity_rows=None, fidelity_heads: str = "sparse") -> torch.Tensor:
     """q,k,v: (1, H, S/P + T, D) local sequence shard with the replicated text at the end.
-    Returns the attention output as a (1, S/P + T, H, D) buffer (text rows: all heads, gathered)."""
+    Returns the attention output as a (1, S/P + T, H, D) buffer (text rows: all heads, gathered).
+    fidelity: a list that receives one `ops.SampledFidelity` over all H heads with the GLOBAL head ids: every slot group's
+    `routed_attention` call measures its local heads through the receive layout (the sampled rows composed with the group's
+    row map), and the heads other ranks hold stay NaN with expert -1 (`gather_routed_fidelity` joins the ranks); heads under
+    the `split` placement are never measured.  The dense reference needs the 16-bit v on this rank: precisions whose v
+    crosses the links as e4m3 are refused.  None: the launches of today."""
     B, H, N, D = q.shape
     assert B == 1
     P = SP_STATE.sp_size
@@ -150,6 +156,14 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
         experts = ops.route_scores(routing_score, tau_sparse)[0].cpu().tolist()
         te = text_valid
     dense_only = lowres_group_info is None
+    # the precision switch (set_attention_precision / VORTA_ATTENTION_PRECISION) is about the ROUTED operator; dense
+    # attention -- --native_attention, the PSNR reference -- stays in the dtype of q,k,v on one GPU and under SP alike
+    precision = precision_of(None) if not dense_only else "native"
+    if fidelity is not None and (dense_only or precision != "native"):
+        # (refused here, before the placement, the layout and the exchange: nothing is allocated, sent or launched)
+        raise ValueError("sp_attention(fidelity=...): " + ("a dense call has no routed output to measure" if dense_only else
+                         f"under precision '{precision}' v crosses the links as e4m3 and the 16-bit dense reference cannot be "
+                         "formed on this rank; measure the 8-bit precisions on one GPU"))
     if dense_only:
         cost = [1.0, 1.0, 1.0]
     else:  # expert costs from the geometry alone (the placement comes first: the layout follows from it)
@@ -184,9 +198,11 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
     if not dense_only and SP_KV_SPLITS != "1":
         kv_splits = auto_kv_splits(local, S, T, s_low) if SP_KV_SPLITS == "auto" else max(1, int(SP_KV_SPLITS))
 
-    # the precision switch (set_attention_precision / VORTA_ATTENTION_PRECISION) is about the ROUTED operator; dense
-    # attention -- --native_attention, the PSNR reference -- stays in the dtype of q,k,v on one GPU and under SP alike
-    precision = precision_of(None) if not dense_only else "native"
+    filed = {}  # slot group -> its routed_attention call's record (local head slots)
+    if fidelity is not None and not torch.is_tensor(fidelity_rows):
+        # the cached table is built here, on the current stream, before the slot groups fork onto theirs (as `prepare` builds)
+        from ..routed import DEFAULT_FIDELITY_ROWS, sample_rows
+        fidelity_rows = sample_rows(S, min(DEFAULT_FIDELITY_ROWS, S) if fidelity_rows is None else fidelity_rows, 0, q.device)
     vwire = sb.begin(lay, precision, SP_V_WIRE or precision != "fp8")  # (SP_V_WIRE: "fp8" only; the others always send e4m3 v)
 
     def attend(g0, g1, gi):
@@ -197,7 +213,9 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
         else:
             routed_attention(qv, kv, vv, _routing(tuple(local[g0:g1]), q.device, ranges_of(g0, g1)), geoms[gi],
                              model=model, text_len=T, text_valid=te, out=ov, operands=sb.operands(sgs[gi]),
-                             kv_splits=kv_splits)
+                             kv_splits=kv_splits,
+                             **({} if fidelity is None else dict(fidelity=filed.setdefault(gi, []), fidelity_rows=fidelity_rows,
+                                                                 fidelity_heads=fidelity_heads)))
 
     def prepare():
         # everything `attend` caches is built here, on the current stream, before the slot groups fork onto theirs
@@ -212,7 +230,46 @@ def sp_attention(q, k, v, T: int, routing_score: Optional[torch.Tensor], tau_spa
     exchange_and_attend(lay, shards, sb.bufs, order, texts, sg, attend,
                         buf[0, :Sl].transpose(0, 1), buf[0, Sl:].transpose(0, 1) if T else None, vwire=vwire,
                         prepare=prepare, parts=parts)
+    if fidelity is not None:
+        mine = order[lay.starts[me]:lay.starts[me + 1]]
+        fidelity.append(_global_routed_fidelity([(filed[gi][-1], mine[g0:g1]) for gi, (g0, g1) in enumerate(sg)], H))
     return buf
+
+
+def _global_routed_fidelity(records, H: int) -> "ops.SampledFidelity":
+    """the slot groups' records (local head slots; `heads`: their global ids) as one record over all H heads: NaN and expert
+    -1 for the heads another rank holds"""
+    first = records[0][0]
+    dev = first.sq_ref.device
+    nan = lambda: torch.full((H,), float("nan"), dtype=torch.float32, device=dev)  # noqa: E731
+    out = ops.SampledFidelity(nan(), nan(), nan(), nan(), nan(), None, first.n, first.rows,
+                              torch.full((H,), -1, dtype=torch.int32, device=dev))
+    for rec, heads in records:
+        idx = torch.tensor(list(heads), dtype=torch.long, device=dev)
+        for name in ("sq_ref", "max_ref", "sq_err", "max_err", "range_ref", "expert"):
+            getattr(out, name).index_copy_(0, idx, getattr(rec, name))
+    return out
+
+
+def gather_routed_fidelity(fid: "ops.SampledFidelity") -> "ops.SampledFidelity":
+    """this rank's statistics ((..., H) with the global head ids, NaN / expert -1 for heads it does not hold: `sp_attention`'s
+    records, or a stack of them over layers) -> every rank's: one all-gather per tensor over the sequence-parallel group (a
+    collective: every rank calls it), a head taken from the first rank that holds it.  A gloo group gathers host copies."""
+    import torch.distributed as dist
+    P = SP_STATE.sp_size
+    staged = dist.get_backend(SP_STATE.group) == "gloo"
+
+    def gather(t):
+        src = t.cpu() if staged else t.contiguous()
+        parts = [torch.empty_like(src) for _ in range(P)]
+        dist.all_gather(parts, src, group=SP_STATE.group)
+        return torch.stack(parts).to(t.device)
+
+    expert = gather(fid.expert)
+    owner = (expert >= 0).int().argmax(0, keepdim=True)
+    pick = lambda t: gather(t).gather(0, owner)[0]  # noqa: E731
+    return ops.SampledFidelity(pick(fid.sq_ref), pick(fid.max_ref), pick(fid.sq_err), pick(fid.max_err), pick(fid.range_ref),
+                               None, fid.n, fid.rows, expert.gather(0, owner)[0])
 
 
 def sp_wan_dense(proc, attn, q, k, v, enc_img, is_cross_attn: bool):

@@ -1150,6 +1150,92 @@ def expert_fidelity(bufs, mixed: Optional[torch.Tensor] = None) -> ExpertFidelit
     return ExpertFidelity(sq_ref, max_ref, sq_err, max_err, range_ref, N * D)
 
 
+class SampledFidelity(NamedTuple):
+    """vorta_sampled_fidelity's statistics: per head how far the rows a ROUTED call wrote are from dense attention in the input
+    dtype, on a sample of `rows.numel()` query rows.  Float32 tensors with any leading dimensions (a layer axis,
+    `vorta.patch.routed_fidelity_of`): sq_ref, max_ref, sq_err, max_err, range_ref (..., H); row_sq_err (..., H, n) or None.
+    Heads that were not measured hold NaN.  `n` = the elements of a head the sums run over (sampled rows x 128); `rows` = the
+    sampled video tokens (int32, ascending; `routed.sample_rows`); `expert` = the head -> expert ids as launched, where the
+    caller knows them (int32 (..., H) on the device; -1: a head no expert list names)."""
+    sq_ref: torch.Tensor                        # sum ref^2
+    max_ref: torch.Tensor                       # max |ref|
+    sq_err: torch.Tensor                        # sum (out - ref)^2
+    max_err: torch.Tensor                       # max |out - ref|
+    range_ref: Optional[torch.Tensor] = None    # max ref - min ref
+    row_sq_err: Optional[torch.Tensor] = None   # a sampled row's 128 squared differences, summed
+    n: int = 0
+    rows: Optional[torch.Tensor] = None
+    expert: Optional[torch.Tensor] = None
+
+    def rel_error(self) -> torch.Tensor:
+        """sqrt(sq_err / sq_ref), (..., H); a head with sq_ref == 0 gives 0 where sq_err == 0 and inf otherwise (the rules of
+        ExpertFidelity.rel_error); NaN for a head that was not measured"""
+        rel = torch.sqrt(self.sq_err / self.sq_ref)
+        zero = self.sq_ref == 0
+        rel = torch.where(zero & (self.sq_err == 0), torch.zeros_like(rel), rel)
+        return torch.where(zero & (self.sq_err > 0), torch.full_like(rel, float("inf")), rel)
+
+    def psnr(self, over: str = "max_abs") -> torch.Tensor:
+        """10 log10(peak^2 / mean squared error) in dB, (..., H): peak = max |ref| (`over="max_abs"`) or the data range
+        max ref - min ref (`over="range"`) of the dense rows; inf where the error is exactly zero"""
+        if over not in ("max_abs", "range"):
+            raise ValueError(f"psnr: over={over!r} (one of 'max_abs', 'range')")
+        if self.n <= 0:
+            raise ValueError("psnr needs the element count `n` of the statistics (ops.sampled_fidelity sets it)")
+        peak = self.max_ref if over == "max_abs" else self.range_ref
+        if peak is None:
+            raise ValueError("psnr(over='range') needs range_ref")
+        mse = self.sq_err.double() / self.n
+        return (10.0 * torch.log10(peak.double() ** 2 / mse)).float()
+
+
+def sampled_fidelity(ref: torch.Tensor, out: torch.Tensor, rows: torch.Tensor, head_list: Optional[torch.Tensor] = None,
+                     n_heads: Optional[int] = None, n_heads_dev: Optional[torch.Tensor] = None, row_errors: bool = False,
+                     into: Optional[SampledFidelity] = None) -> SampledFidelity:
+    """vorta_sampled_fidelity: one deterministic pass over the dense reference rows `ref` (H, n, D) and the rows
+    out[h][rows[p]] of the routed output `out` (H, N, D) (any strides the attention kernels take; read in place), for the heads
+    of `head_list` / `n_heads` / `n_heads_dev` (as `attn_fwd` reads them; default: every head).  `rows`: int32 (n,), the row of
+    `out` for sample position p, every value in [0, N) and every listed head in [0, H): a device contract that no host code
+    checks (it would be a host read).  row_errors: also the per-row sums (H, n).
+    into: a SampledFidelity of an earlier call on the same shapes whose buffers this call writes too (another head list); the
+    statistics of heads no call names stay NaN."""
+    ref, out = (t[0] if t.dim() == 4 else t for t in (ref, out))
+    _require_gpu(ref, out, rows, head_list, n_heads_dev)
+    if ref.dim() != 3 or out.dim() != 3 or ref.dtype not in _DT or out.dtype != ref.dtype or out.shape[0] != ref.shape[0] \
+            or out.shape[2] != ref.shape[2]:
+        raise ValueError("sampled_fidelity takes ref (H,n,D) and out (H,N,D) of one dtype, bf16 or fp16")
+    H, n, D = ref.shape
+    if rows.dim() != 1 or rows.numel() != n:
+        raise ValueError(f"rows {tuple(rows.shape)} does not name one row of `out` for each of the {n} reference rows")
+    dev = ref.device
+    if n_heads is None:
+        n_heads = head_list.numel() if head_list is not None else H
+    if head_list is not None and head_list.numel() < n_heads:
+        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
+    if head_list is None and n_heads > H:
+        raise ValueError(f"n_heads = {n_heads} head slots for {H} heads")
+    if into is None:
+        nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)  # noqa: E731
+        into = SampledFidelity(nan(H), nan(H), nan(H), nan(H), nan(H), nan(H, n) if row_errors else None, n * D, rows)
+    elif into.sq_ref.shape != (H,) or into.n != n * D or (row_errors and into.row_sq_err is None):
+        raise ValueError("sampled_fidelity: `into` holds the statistics of another shape")
+    a = _C.SampledFidelityArgs()
+    a.struct_size = C.sizeof(_C.SampledFidelityArgs)
+    a.dtype, a.head_dim, a.n_heads, a.n_rows = _DT[ref.dtype], D, n_heads, n
+    a.ref, a.out = _tensor(ref), _tensor(out)
+    a.rows, a.head_list, a.n_heads_dev = _ptr(rows), _ptr(head_list), _ptr(n_heads_dev)
+    ws = torch.empty(max(n_heads, 1) * _C.SAMPLED_FIDELITY_PARTS * _C.SAMPLED_FIDELITY_WS_FLOATS, dtype=torch.float32, device=dev)
+    a.sq_ref, a.max_ref = into.sq_ref.data_ptr(), into.max_ref.data_ptr()
+    if into.range_ref is not None:  # (an `into` built without one: the library takes NULL there)
+        a.range_ref = into.range_ref.data_ptr()
+    a.sq_err, a.max_err, a.ws = into.sq_err.data_ptr(), into.max_err.data_ptr(), ws.data_ptr()
+    if row_errors:
+        a.row_sq_err = into.row_sq_err.data_ptr()
+    if n_heads > 0:
+        _C.check(_C.lib().vorta_sampled_fidelity(C.byref(a), _stream()), "vorta_sampled_fidelity")
+    return into
+
+
 def cast_grads(srcs, dsts) -> None:
     """vorta_cast_grads: up to three float32 (H,N,D) buffers -> 16-bit (H,N,D) views in one launch, round to nearest even."""
     _require_gpu(*srcs, *dsts)

@@ -11,9 +11,11 @@ For router training on a patched model: `original_attention(model)` (the dense t
 latents in, tokens sharded inside the model) and `all_reduce_router_grads(model)` (the ranks' shares of the router
 gradients, summed).  For judging a router or a `tau_sparse`:
 `expert_fidelity(model)` / `fidelity_of(model)` (per layer and head, how far each sparse expert and the mixed output are from
-full attention) and the host helpers `routes_from_fidelity` / `evaluate_routing` (patch/fidelity.py)."""
+full attention) and the host helpers `routes_from_fidelity` / `evaluate_routing` (patch/fidelity.py); at inference,
+`routed_fidelity(model)` / `routed_fidelity_of(model)`: the routed output as run against dense attention on sampled rows."""
 from ._engine import all_reduce_router_grads, original_attention, routing_scores_of, token_sharded
-from .fidelity import evaluate_routing, expert_fidelity, expert_work, fidelity_of, routes_from_fidelity
+from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, routed_fidelity, routed_fidelity_of,
+                       routes_from_fidelity)
 from .router import Router, load_router_checkpoint
 from .utils import (Pixel2TokenFactory, hunyuan_pixel2token, prepare_hunyuan_self_attn_kwargs,
                     prepare_wan_self_attn_kwargs, wan_pixel2token)

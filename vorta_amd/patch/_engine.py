@@ -137,6 +137,10 @@ class ForwardState:
     layer_scores: List[torch.Tensor] = field(default_factory=list)  # its per-layer views, made once
     head_routing: bool = False                   # the plan's dispatch lists belong to these scores (inference path)
     fidelity: Optional[Dict[int, Any]] = None    # layer -> ops.ExpertFidelity; a dict only under `expert_fidelity(model)`
+    # layer -> [ops.SampledFidelity per batch item]; a dict only under `routed_fidelity(model)`, whose (n_rows, seed, heads)
+    # this forward read when it started
+    routed_fidelity: Optional[Dict[int, Any]] = None
+    measure_routed: Optional[Tuple[int, int, str]] = None
     token_shard: bool = False                    # sequence parallel: this forward got the WHOLE latent and cuts its tokens itself
 
 
@@ -231,6 +235,8 @@ class StepContext:
     sp_coherent: bool = False     # this call's / context's ranks were seen to hold the same tokens (install_token_shard)
     measure_fidelity: bool = False  # inside `expert_fidelity(model)` (patch/fidelity.py)
     fidelity: Optional[Dict[int, Any]] = None  # the statistics of the latest forward that measured (what `fidelity_of` reads)
+    measure_routed: Optional[Tuple[int, int, str]] = None  # inside `routed_fidelity(model)`: (n_rows, seed, heads)
+    routed_fidelity: Optional[Dict[int, Any]] = None  # the latest measured routed forward's records (`routed_fidelity_of`)
 
     def state_for(self, rotary) -> Optional[ForwardState]:
         """the state of the forward a processor call belongs to: the running forward's (in grad mode filed under `rotary`
@@ -282,7 +288,10 @@ class BoundProcessor:
         self.ctx = ctx
         self.layer = layer
         self.rotary_name = rotary_name
-        self._accepted = set(inspect.signature(inner.__call__).parameters)
+        params = inspect.signature(inner.__call__).parameters
+        self._accepted = set(params)
+        # the processor's own default, for a caller whose kwargs leave `latent_shape` to it (the measured path sizes its sample)
+        self._default_latent = params["latent_shape"].default if "latent_shape" in params else None
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, image_rotary_emb=None,
                  rotary_emb=None, use_original_attn: bool = False):
@@ -317,6 +326,21 @@ class BoundProcessor:
                 kw["head_routing"] = ctx.plan.routing(self.layer)
             if "experts_host" in self._accepted and SP_STATE.enabled:
                 kw["experts_host"] = ctx.plan.experts_host(self.layer)
+        if "fidelity_rows" in self._accepted:  # a hard-routing (Eval) processor: its sink takes the ROUTED output's statistics
+            if state.routed_fidelity is None:
+                return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+            # under `routed_fidelity(model)`: the sample is fixed per (S, n, seed) -- one cached table, no host work per layer
+            from ..routed import sample_rows
+            n_rows, seed, heads = state.measure_routed
+            S = 1
+            for x in kw.get("latent_shape", self._default_latent):
+                S *= int(x)
+            kw["fidelity"] = sink = []
+            kw["fidelity_rows"], kw["fidelity_heads"] = sample_rows(S, min(n_rows, S), seed, hidden_states.device), heads
+            out = self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+            if sink:  # (a cross-attention call measures nothing)
+                state.routed_fidelity[self.layer] = sink
+            return out
         if state.fidelity is None or "fidelity" not in self._accepted:
             return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
         kw["fidelity"] = sink = []  # under `expert_fidelity(model)`: the soft mixture's statistics, filed under this layer
@@ -378,6 +402,8 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
                              "`token_sharded(model)`, or run the pipeline call, which shards tokens")
         ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher,
                                    fidelity={} if ctx.measure_fidelity and not ctx.teacher else None,
+                                   routed_fidelity={} if ctx.measure_routed is not None and not ctx.teacher else None,
+                                   measure_routed=ctx.measure_routed,
                                    token_shard=token_shard)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
         ctx.forwards += 1
@@ -392,6 +418,8 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
             ctx.student, ctx.student_scores = weakref.ref(state), state.scores.detach()
         if state.fidelity:
             ctx.fidelity = state.fidelity  # (small per-head tensors: kept until the next measuring forward)
+        if state.routed_fidelity:
+            ctx.routed_fidelity = state.routed_fidelity  # (likewise)
         if ctx.return_routing_scores and state.scores is not None:
             # one device read for all layers (the reference does `.detach().cpu()` per block, modeling_hunyuan.py:297)
             all_scores = state.scores.detach().cpu()

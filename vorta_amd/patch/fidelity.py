@@ -13,6 +13,17 @@ to per-head statistics.  The reference has no counterpart: its only signal is th
     evaluate_routing(routing_scores_of(model), fid, geometry)   # what the router's own routes cost and lose
 
 Expert ids are the processors': 0 full attention, 1 coreset, 2 sliding tile; columns 0 / 1 of the statistics are experts 1 / 2.
+
+The above is the training-time forward, in 16 bits, at three times the routed step.  What an INFERENCE forward actually wrote --
+hard top-1 routes with their `tau_sparse`, the 8-bit precisions, a partial geometry, a rank's heads -- is measured on a seeded
+sample of video rows per head against dense attention in the input dtype (routed.routed_attention(fidelity=...),
+vorta_sampled_fidelity), cheap enough to stay on during a generation:
+
+    with routed_fidelity(model, n_rows=2048, seed=0, heads="sparse"):   # Eval processors: every routed call files its layer
+        model(hidden_states, ..., self_attention_kwargs=kw)
+    rf = routed_fidelity_of(model)                    # ops.SampledFidelity, stacked (L, H) + `expert` (L, H) as launched
+    rf.rel_error()                                    # (L, H): NaN for heads that were not measured
+    evaluate_routing(rf.expert, rf, geometry)         # a head's error is its measured one
 """
 from __future__ import annotations
 
@@ -23,7 +34,7 @@ import torch
 from torch import nn
 
 from .. import _partial
-from ..ops import ExpertFidelity
+from ..ops import ExpertFidelity, SampledFidelity
 from ._engine import context_of
 
 _COLUMN_OF_EXPERT = {1: 0, 2: 1}  # expert id -> column of sq_err / max_err / rel_error
@@ -70,6 +81,57 @@ def fidelity_of(model: nn.Module) -> ExpertFidelity:
     if SP_STATE.enabled:
         from ..attention._sp import gather_fidelity
         fid = gather_fidelity(fid, ctx.plan.heads)
+    return fid
+
+
+@contextlib.contextmanager
+def routed_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0, heads: str = "sparse"):
+    """While active, every forward of `model` (patched with apply_vorta_transformer, hard-routing Eval processors) measures
+    the routed output it wrote: each routed self-attention call compares `n_rows` sampled video rows per head (the stratified
+    table `routed.sample_rows(S, n_rows, seed)`; every row where the clip has fewer) with dense attention in the input dtype
+    and files an `ops.SampledFidelity` under its layer.  heads: "sparse" = the heads routed to the coreset and sliding-tile
+    experts, "all" = the full-attention heads as well (what an 8-bit precision costs them).  The flag is read once per
+    forward, when it starts; teacher forwards (`original_attention`) measure nothing.  The forward stays free of host
+    synchronisation and graph-capturable: the table is fixed, the gather, the launches and the compare run on the caller's
+    stream.  Outside the context the forwards launch what they launch today."""
+    from ..routed import FIDELITY_HEADS
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("routed_fidelity: the model was not patched with apply_vorta_transformer")
+    if heads not in FIDELITY_HEADS or int(n_rows) < 0:
+        raise ValueError(f"routed_fidelity: heads={heads!r} (one of {FIDELITY_HEADS}), n_rows={n_rows}")
+    previous, ctx.measure_routed = ctx.measure_routed, (int(n_rows), int(seed), heads)
+    try:
+        yield model
+    finally:
+        ctx.measure_routed = previous
+
+
+def stack_routed_fidelity(per_layer) -> SampledFidelity:
+    """a sequence of per-layer `SampledFidelity` -> one with a leading layer axis (row_sq_err is not carried)"""
+    per_layer = list(per_layer)
+    first = per_layer[0]
+    cat = lambda name: torch.stack([getattr(f, name) for f in per_layer])  # noqa: E731
+    return SampledFidelity(cat("sq_ref"), cat("max_ref"), cat("sq_err"), cat("max_err"), cat("range_ref"), None, first.n,
+                           first.rows, cat("expert"))
+
+
+def routed_fidelity_of(model: nn.Module, item: int = 0) -> SampledFidelity:
+    """The statistics of the model's latest forward under `routed_fidelity(model)`, stacked over the layers in block order:
+    sq_ref, max_ref, sq_err, max_err, range_ref (L, H), `expert` (L, H) int32 = the head -> expert ids as launched, `rows` the
+    sampled video tokens.  `item`: the batch item (Wan files one record per item).  Under sequence parallelism a rank measured
+    its own heads: they are all-gathered over the group here (a collective: every rank calls it).  Raises when no such
+    forward is on record."""
+    ctx = context_of(model)
+    filed = ctx.routed_fidelity
+    if not filed:
+        raise RuntimeError("routed_fidelity_of: no forward of this model has run under routed_fidelity(model) with "
+                           "hard-routing (Eval) processors")
+    fid = stack_routed_fidelity(filed[layer][item] for layer in sorted(filed))
+    from ..ulysses import SP_STATE
+    if SP_STATE.enabled:
+        from ..attention._sp import gather_routed_fidelity
+        fid = gather_routed_fidelity(fid)
     return fid
 
 
@@ -134,13 +196,17 @@ def routes_from_fidelity(fid: ExpertFidelity, max_rel_error: float, geometry: Op
     return table
 
 
-def evaluate_routing(experts_or_scores: torch.Tensor, fid: ExpertFidelity, geometry: Geometry, text_valid: int = 0,
-                     tau_sparse: Optional[float] = None) -> Dict[str, torch.Tensor]:
+def evaluate_routing(experts_or_scores: torch.Tensor, fid: Union[ExpertFidelity, SampledFidelity], geometry: Geometry,
+                     text_valid: int = 0, tau_sparse: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """What a routing costs and what it loses, per layer.  `experts_or_scores`: an integer (L, H) expert table, or floating
     routing scores (L, H, 3) / (L, B, H, 3) (batch item 0; the processors' rule: the first maximum, full attention where
     that score is below `tau_sparse`).  Returns CPU tensors of L entries: `worst_rel_error` and `mean_rel_error` of the
     chosen experts over the heads (a head on full attention contributes 0), `flops_share` = the routed layer's FLOPs over
-    the all-dense layer's by `expert_work`, and the table itself as `experts` (L, H)."""
+    the all-dense layer's by `expert_work`, and the table itself as `experts` (L, H).
+    With a `SampledFidelity` (`routed_fidelity_of`) a head's error is its MEASURED one, whatever its expert: the routed output
+    as run against dense attention, so a full-attention head measured under heads="all" contributes what its precision
+    costs; a full-attention head that was not measured contributes 0, a sparse head that was not measured NaN.  The table
+    must then be the routes the record was launched with (its `expert`), wherever the record knows them."""
     t = experts_or_scores.detach().cpu()
     if t.is_floating_point():
         if t.dim() == 4:
@@ -153,13 +219,21 @@ def evaluate_routing(experts_or_scores: torch.Tensor, fid: ExpertFidelity, geome
     else:
         experts = t.long()
     rel = fid.rel_error().detach().cpu()
-    if experts.shape != rel.shape[:-1]:
-        raise ValueError(f"routing table {tuple(experts.shape)} does not match the statistics {tuple(rel.shape[:-1])}")
+    sampled = isinstance(fid, SampledFidelity)
+    if experts.shape != (rel.shape if sampled else rel.shape[:-1]):
+        raise ValueError(f"routing table {tuple(experts.shape)} does not match the statistics "
+                         f"{tuple(rel.shape if sampled else rel.shape[:-1])}")
     if bool(((experts < 0) | (experts > 2)).any()):
         raise ValueError("expert ids are 0 (full), 1 (coreset), 2 (sliding tile)")
-    chosen = torch.zeros(experts.shape, dtype=rel.dtype)
-    for e, col in _COLUMN_OF_EXPERT.items():
-        chosen = torch.where(experts == e, rel[..., col], chosen)
+    if sampled:
+        launched = None if fid.expert is None else fid.expert.detach().cpu().long()
+        if launched is not None and bool(((launched >= 0) & (launched != experts)).any()):
+            raise ValueError("the routing table differs from the routes the sampled statistics were launched with (fid.expert)")
+        chosen = torch.where(torch.isnan(rel) & (experts == 0), torch.zeros_like(rel), rel)
+    else:
+        chosen = torch.zeros(experts.shape, dtype=rel.dtype)
+        for e, col in _COLUMN_OF_EXPERT.items():
+            chosen = torch.where(experts == e, rel[..., col], chosen)
     work = torch.tensor(expert_work(geometry, text_valid), dtype=torch.float64)
     share = work[experts].sum(-1) / (work[0] * experts.shape[-1])
     return dict(worst_rel_error=chosen.max(dim=-1).values, mean_rel_error=chosen.mean(dim=-1), flops_share=share.float(),

@@ -334,6 +334,98 @@ def prepare_operands(precision: str, q: torch.Tensor, k: torch.Tensor, v: torch.
 
 _SIDE_STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
 
+# ---- routed-output fidelity on sampled dense query rows ---------------------------------------------------
+DEFAULT_FIDELITY_ROWS = 2048  # sampled video rows per head: 1.7 % of Hunyuan-129f's 118 800 (by FLOP count, of a dense head)
+FIDELITY_HEADS = ("sparse", "all")
+# key splits of the dense reference launches: n query rows against every key are a few workgroups per head, each with the
+# longest key loop there is, so the keys are cut into this many parts (+ a merge kernel) where every part keeps 8 key blocks
+# (`fidelity_ref_splits`).  The cut follows from the KEY COUNT alone -- not from n, the head count or the form of the head
+# lists -- so the reference rows, whose summation order the cut decides, have the same bits for host and device lists, every
+# sample size and every rank.  1 leaves the keys whole (the A/B of tools/bench_routed_fidelity.py, which sets this in its own
+# process: profiles/routed_fidelity_timing.json)
+FIDELITY_REF_SPLITS = 8
+_SAMPLE_ROWS: Dict[tuple, torch.Tensor] = {}  # (S, n, seed, device) -> table; a table handed out is never evicted (a graph may read it)
+
+
+def fidelity_ref_splits(n_kv: int) -> int:
+    """the key parts of a dense reference launch over `n_kv` keys: FIDELITY_REF_SPLITS, fewer where a part would fall under 8
+    key blocks of 64 (one part under 16 blocks)"""
+    return max(1, min(int(FIDELITY_REF_SPLITS), ((n_kv + 63) // 64) // 8))
+
+
+def sample_rows(S: int, n: int, seed: int = 0, device=None) -> torch.Tensor:
+    """The `n` video tokens of [0, S) on which the routed output is compared with dense attention: a stratified random table,
+    int32 (n,), ascending and distinct by construction.  Stratum i is [floor(i S / n), floor((i + 1) S / n)); one token per
+    stratum, lo + floor(u (hi - lo)) with u = numpy.random.default_rng(seed).random(n), drawn on the host.  Stratified, so
+    that every part of the clip is seen; random inside a stratum, so that no stride locks onto the in-window position of the
+    coreset windows or onto a tile phase.  n == S gives every row; n > S is a ValueError.  Built once per (S, n, seed) and
+    cached, on `device` when one is given (None: the host table); a cached table is never freed, so a captured graph that
+    reads one stays valid."""
+    import numpy as np
+    S, n, seed = int(S), int(n), int(seed)
+    if n > S or n < 0:
+        raise ValueError(f"a sample of {n} rows out of {S} video tokens")
+    key = (S, n, seed, None if device is None else str(torch.device(device)))
+    if key not in _SAMPLE_ROWS:  # (4 n bytes a table, kept for the life of the process: a captured graph reads its address)
+        host = _SAMPLE_ROWS.get(key[:3] + (None,))
+        if host is None:
+            i = np.arange(n, dtype=np.int64)
+            lo, hi = (i * S) // n if n else i, ((i + 1) * S) // n if n else i
+            u = np.random.default_rng(seed).random(n)
+            tok = np.minimum(lo + np.floor(u * (hi - lo)).astype(np.int64), hi - 1)  # (u < 1: the minimum never binds)
+            host = _SAMPLE_ROWS[key[:3] + (None,)] = torch.from_numpy(tok.astype(np.int32))
+        if device is not None:
+            _SAMPLE_ROWS[key] = host.to(device)
+    return _SAMPLE_ROWS[key]
+
+
+def _expert_ids(routing: "HeadRouting", H: int, device) -> torch.Tensor:
+    """head -> expert as the launches read it, int32 (H,) on the device without a host read: -1 for a head no list names
+    (slots at or past a device count are not read); a head split by query range is a full-attention head (0)"""
+    ids = torch.full((H + 1,), -1, dtype=torch.int32, device=device)
+    slot = torch.arange(H, device=device)
+    for e in range(3):
+        count = routing.counts_host[e] if routing.counts_host is not None else routing.counts_dev[e]
+        heads = routing.lists[e][:H].long()
+        ids.scatter_(0, torch.where(slot < count, heads, torch.full_like(heads, H)), torch.full((H,), e, dtype=torch.int32,
+                                                                                                  device=device))
+    for hl, _, _ in routing.partials or ():
+        ids.index_fill_(0, hl.long(), 0)
+    return ids[:H]
+
+
+def _measure_routed(fidelity: list, fidelity_rows, fidelity_heads: str, q3, k3, v3, o3, routing: "HeadRouting",
+                    geom: "RoutedGeometry", te: int, scale: Optional[float]) -> None:
+    """`routed_attention(fidelity=...)`: dense attention in the input dtype on the sampled query rows of the measured heads
+    (the 16-bit q gathered at the rows, every valid key: ops.attn_fwd as expert 0 passes its key side), compared with the
+    rows the routed launches wrote (ops.sampled_fidelity, `out` read in place); files one ops.SampledFidelity"""
+    if fidelity_heads not in FIDELITY_HEADS:
+        raise ValueError(f"fidelity_heads={fidelity_heads!r}: one of {FIDELITY_HEADS}")
+    H, S, rm = q3.shape[0], geom.S, geom.row_map
+    if fidelity_rows is None:
+        fidelity_rows = min(DEFAULT_FIDELITY_ROWS, S)
+    tokens = fidelity_rows if torch.is_tensor(fidelity_rows) else sample_rows(S, fidelity_rows, 0, q3.device)
+    if tokens.dim() != 1 or tokens.dtype != torch.int32 or tokens.numel() > S:
+        raise ValueError("fidelity_rows: a sample size, or an int32 table of video tokens (routed.sample_rows)")
+    n = tokens.numel()
+    rows = tokens if rm is None else rm.index_select(0, tokens)  # the physical rows of q and out
+    q_rows = q3.index_select(1, rows)       # compact (H, n, D): the launch below has no query table
+    ref = torch.empty_like(q_rows)
+    key_side = dict(n_kv=S + te, kv_rows=None if rm is None else rm[:S + te], scale=scale)
+    splits = fidelity_ref_splits(S + te)
+    stats = None
+    for e in ((1, 2) if fidelity_heads == "sparse" else (0, 1, 2)):
+        # (heads split by query range, routing.partials, are in no list: not measured)
+        if routing.counts_host is not None and routing.counts_host[e] == 0:
+            continue
+        slots = routing.slot_args(e, H)
+        if n:
+            ops.attn_fwd(q_rows, k3, v3, ref, n_q=n, q_valid=n, n_splits=splits, tag="fidelity_ref", **key_side, **slots)
+        stats = ops.sampled_fidelity(ref, o3, rows, **slots, into=stats)
+    if stats is None:  # no head to measure: every statistic NaN
+        stats = ops.sampled_fidelity(ref, o3, rows, n_heads=0)
+    fidelity.append(stats._replace(rows=tokens, expert=_expert_ids(routing, H, q3.device)))
+
 
 def _side_streams(device: torch.device):
     idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -348,7 +440,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                      concurrent: bool = False, fused: bool = True, sliding_block_rows: int = 0,
                      expert_outs: Optional[Sequence[torch.Tensor]] = None, fp8=None, fp8_operands=None,
                      operands: Optional[AttnOperands] = None, kv_splits: int = 1,
-                     record: Optional[list] = None) -> torch.Tensor:
+                     record: Optional[list] = None, fidelity: Optional[list] = None, fidelity_rows=None,
+                     fidelity_heads: str = "sparse") -> torch.Tensor:
     """q,k,v: (1,H,S+T,D) [hunyuan: video then text] or (1,H,S,D) [wan].  Returns (1,H,S+T,D).
 
     hunyuan: hunyuan.py:556-605 (TripleEval.__call__ steps 5.1-5.4);  wan: wan.py:351-383.
@@ -369,7 +462,15 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     a sequence-parallel rank whose one or two heads leave the chip under one round of workgroups, where a layer lasts as
     long as one workgroup's key loop; changes the summation order, so it is never chosen silently.
     record: a list that receives the launches as launched -- the dictionaries of ops.attn_fwd keywords (q / k / v / out,
-    tables, head lists, lengths), in launch order; the backward replays them through ops.attn_bwd (`_replay_backward`)."""
+    tables, head lists, lengths), in launch order; the backward replays them through ops.attn_bwd (`_replay_backward`).
+    fidelity: a list that receives one `ops.SampledFidelity` of this call: after the routed launches, dense attention in the
+    input dtype (the ORIGINAL 16-bit q, k, v, whatever the precision) on `fidelity_rows` sampled video rows per head -- a
+    sample size (None: min(DEFAULT_FIDELITY_ROWS, S); `sample_rows` with seed 0) or an int32 table of `sample_rows` -- against
+    the rows this call wrote, per head, as run: hard routes, 8-bit precision, partial geometry, a rank's local heads.
+    fidelity_heads: "sparse" = the heads of experts 1 and 2, "all" = expert 0's as well (what 8 bits cost a full head); heads
+    split by query range are never measured; unmeasured heads hold NaN.  Every launch is on the current stream, nothing is
+    read back (the record's `expert` ids are a device tensor).  None (default): nothing is allocated or launched beyond the
+    routed calls; `out` has the same bits either way.  The reference launches are launches of their own after the routed grid."""
     if q.dim() == 4 and q.shape[0] != 1:
         # hunyuan.py:168 asserts batch 1; Wan's CFG runs two batch-1 forwards (pipeline_wan.py:322-344)
         raise AssertionError(f"Batch size {q.shape[0]} is not supported by routed_attention.")
@@ -380,6 +481,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     if rm is None and N != S + T:
         raise ValueError(f"Input sequence length {N - T} does not match latent shape {geom.latent}.")
     te = text_valid if hy else 0
+    if fidelity is not None and expert_outs is not None:
+        raise ValueError("fidelity= measures the routed output `out`: it does not go with expert_outs")
     if out is None and expert_outs is None:
         out = torch.empty_like(q)
     q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
@@ -503,6 +606,11 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             c = {key: val for key, val in c.items() if key not in ("fused_n_splits", "fused_first")}
             ops.attn_fwd(c.pop("q"), c.pop("k"), c.pop("v"), c.pop("out"), **c)
 
+    def measured(result):
+        if fidelity is not None:
+            _measure_routed(fidelity, fidelity_rows, fidelity_heads, q3, k3, v3, o_e[0], routing, geom, te, scale)
+        return result
+
     if fused and not concurrent and sliding_block_rows == 0:
         # 256-row workgroups let the sliding launch join the fused grid; measured better than a separate
         # 128-row launch with less padding (Hunyuan 129f: 4.77 s vs 4.91 s per step)
@@ -522,14 +630,14 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                 launch_fused(calls)
             else:
                 launch(calls)
-        return out
+        return measured(out)
     if not concurrent:
         calls = [c for fn, on in experts if on for c in fn()]
         if fused:
             launch_fused(calls)
         else:
             launch(calls)
-        return out
+        return measured(out)
     # the experts are independent: fork them onto side streams, join before returning (so every later use of
     # q,k,v,out on the current stream is ordered after them)
     cur = torch.cuda.current_stream(q.device)
@@ -548,7 +656,7 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             done = torch.cuda.Event()
             done.record(st)
         cur.wait_event(done)
-    return out
+    return measured(out)
 
 
 def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,

@@ -26,6 +26,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::qk_norm_rope_grad(x, weight, eps, cos, sin, rope_tokens, across_heads) -> y   out of place, differentiable;
     vorta::qk_norm_rope_bwd(x, g, weight, eps, cos, sin, ...) -> (dx, dweight)   its autograd formula (vorta_qk_norm_rope_bwd)
     vorta::expert_fidelity(x0,x1,x2, mixed)           -> (sq_ref, max_ref, sq_err, max_err, range_ref)   vorta_expert_fidelity
+    vorta::sampled_fidelity(ref, out, rows, head_list, n_heads, n_heads_dev, row_errors)
+                                                      -> (sq_ref, max_ref, sq_err, max_err, range_ref, row_sq_err)   vorta_sampled_fidelity
 """
 from typing import List, Optional, Tuple
 
@@ -159,6 +161,26 @@ def _(x0, x1, x2, mixed=None):
     f32 = dict(dtype=torch.float32)
     return (x0.new_empty((H,), **f32), x0.new_empty((H,), **f32), x0.new_empty((H, 3), **f32), x0.new_empty((H, 3), **f32),
             x0.new_empty((H,), **f32))
+
+
+@torch.library.custom_op("vorta::sampled_fidelity", mutates_args=(), device_types="cuda")
+def sampled_fidelity(ref: torch.Tensor, out: torch.Tensor, rows: torch.Tensor, head_list: Optional[torch.Tensor] = None,
+                     n_heads: int = -1, n_heads_dev: Optional[torch.Tensor] = None, row_errors: bool = False
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.sampled_fidelity on ref (H,n,D), out (H,N,D) and rows (n,): float32 (H,) x 5 and (H,n) -- the tensor fields of
+    ops.SampledFidelity (row_sq_err is (H,0) without `row_errors`); heads the lists do not name hold NaN.  A device contract,
+    checked nowhere (a check would be a host read): every value of `rows` lies in [0, N) and every listed head in [0, H); a
+    value outside reads, and a head outside also writes, out of bounds"""
+    f = ops.sampled_fidelity(ref, out, rows, head_list, None if n_heads < 0 else n_heads, n_heads_dev, row_errors)
+    rows_err = f.row_sq_err if f.row_sq_err is not None else f.sq_ref.new_empty((ref.shape[0], 0))
+    return f.sq_ref, f.max_ref, f.sq_err, f.max_err, f.range_ref, rows_err
+
+
+@sampled_fidelity.register_fake
+def _(ref, out, rows, head_list=None, n_heads=-1, n_heads_dev=None, row_errors=False):
+    H, n = ref.shape[0], ref.shape[1]
+    f32 = dict(dtype=torch.float32)
+    return tuple(ref.new_empty((H,), **f32) for _ in range(5)) + (ref.new_empty((H, n if row_errors else 0), **f32),)
 
 
 @torch.library.custom_op("vorta::routed_attention", mutates_args=("out",), device_types="cuda")
