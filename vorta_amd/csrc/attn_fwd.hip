@@ -244,7 +244,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const Params p) {
     return;
   }
   if (!row_ok) return;
-  const float inv = (my_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
+  // a position past q_valid is written as zero bits whatever its accumulators hold (0 x NaN is NaN, 0 x a negative sum
+  // is -0): a select on the position alone, applied to the converted values.  A position below q_valid keeps its
+  // arithmetic: a NaN row sum still gives a NaN row
+  const bool past = my_p >= q_valid;
+  const float inv = (!past && l_tot > 0.f) ? 1.f / l_tot : 0.f;
   uint2 packed[16];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -253,9 +257,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const Params p) {
       V4 t;
 #pragma unroll
       for (int j = 0; j < 4; ++j) t[j] = (T)(o[dt][4 * rg + j] * inv);
-      packed[dt * 4 + rg] = *(uint2*)&t;
+      packed[dt * 4 + rg] = past ? make_uint2(0u, 0u) : *(uint2*)&t;
     }
   char* obase = p.o + (int64_t)head * p.o_sh + hh * 8;
+  // (a row and its duplicates are stores of the same `packed` values, converted once above.  No barrier as in
+  // attn_combine_kernel pins that here: tried, it changed nothing that a test or the benchmark's outputs could show.
+  // tests/test_hip_attention_fwd_structured.py compares every duplicate row with its source row as bits on each
+  // gather launch, which is what holds the property)
   auto store_row = [&](int64_t row) {
     char* op = obase + row * p.o_ss;
 #pragma unroll
@@ -718,7 +726,11 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
     return;
   }
   if (!e_ok) return;
-  const float inv = (e_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
+  // a position past q_valid is written as zero bits whatever its accumulators hold (0 x NaN is NaN, 0 x a negative sum
+  // is -0): a select on the position alone, applied to the converted values.  A position below q_valid keeps its
+  // arithmetic: a NaN row sum still gives a NaN row
+  const bool past = e_p >= q_valid;
+  const float inv = (!past && l_tot > 0.f) ? 1.f / l_tot : 0.f;
   uint2 packed[16];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -727,9 +739,13 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
       V4 t;
 #pragma unroll
       for (int j = 0; j < 4; ++j) t[j] = (T)(o[dt][4 * rg + j] * inv);
-      packed[dt * 4 + rg] = *(uint2*)&t;
+      packed[dt * 4 + rg] = past ? make_uint2(0u, 0u) : *(uint2*)&t;
     }
   char* obase = p.o + (int64_t)head * p.o_sh + hh_e * 8;
+  // (a row and its duplicates are stores of the same `packed` values, converted once above.  No barrier as in
+  // attn_combine_kernel pins that here: tried, it changed nothing that a test or the benchmark's outputs could show.
+  // tests/test_hip_attention_fwd_structured.py compares every duplicate row with its source row as bits on each
+  // gather launch, which is what holds the property)
   auto store_row = [&](int64_t row) {
     char* op = obase + row * p.o_ss;
 #pragma unroll
