@@ -52,7 +52,9 @@ extern "C" {
                                    and partial geometry, vorta_sta_partial_sizes / vorta_sta_build_tables_partial /
                                    vorta_coreset_select_partial (three more symbols on the existing argument blocks)
                                    and the routed output's fidelity on sampled rows, vorta_sampled_fidelity (a pure addition: a
-                                   binding asks for the symbol and for vorta_sampled_fidelity_args_size()) */
+                                   binding asks for the symbol and for vorta_sampled_fidelity_args_size())
+                                   and the sampled rows of a per-expert measurement, vorta_gather_sample_rows (a pure addition:
+                                   a binding asks for the symbol and for vorta_gather_sample_rows_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -830,6 +832,53 @@ typedef struct vorta_sampled_fidelity_args {
 
 int vorta_sampled_fidelity(const vorta_sampled_fidelity_args* args, void* hip_stream);
 int vorta_sampled_fidelity_args_size(void);
+
+/*
+ * vorta_gather_sample_rows (ABI 9, a pure addition: a binding asks for the symbol and for vorta_gather_sample_rows_args_size();
+ * vorta_sizeof keeps its 17 indices) -- the glue of a PER-EXPERT fidelity measurement on sampled rows (what every expert would
+ * have written at a sample of n_rows query rows; the reference has no such measurement).  One launch fills up to three compact
+ * (H, n_rows, D) buffers, indexed by the HEAD, for head slot y < n_heads (< *n_heads_dev when given), head h = head_list ?
+ * head_list[y] : y, and sample position p < n_rows:
+ *     dst_q[h][p]    = q[h][rows[p]]                       the row's own query (dense attention, the sliding tile)
+ *     dst_qrep[h][p] = q[h][rep(y, p)]                     the query that stands for the row under the coreset expert:
+ *         rep(y, p) = rows[p], unless win[p] >= 0 and rows[p] is among drop_rows[y][win[p]][0 .. n_dup): then the centre of the
+ *         window, keep_rows[y][win[p]] (vorta_coreset_select's lists: positions < G of a keep list are the centres, a dropped
+ *         margin is written the centre's output).  win[p] = the coreset window of position p, -1 for a token outside the whole
+ *         windows (partial geometry) or a text token; rows, keep_rows and drop_rows all hold PHYSICAL rows of q.
+ *     dst_out[h][p]  = out[h][rows[p]]                     the routed output as launched
+ * A destination with ptr NULL is not written (and its sources need not be given).  Heads the launch does not name, and slots
+ * at or past *n_heads_dev, keep what the destinations held; nothing outside dst[h][0 .. n_rows)[0 .. 128) is written.  head_list
+ * names distinct heads: every destination row has one writer; no atomics; the same bits on every run.  Row addresses are
+ * 64-bit (head * stride_h + row * stride_s); a lane moves 16 bytes.  The row and window VALUES live on the device and are the
+ * caller's contract, as for the attention kernels' tables.
+ * VORTA_EINVAL for a wrong struct_size, negative sizes, more than 65535 head slots, a misaligned table, head list or device
+ * count (4 bytes), a misaligned tensor (16-byte aligned rows), a wanted destination whose source or tables are null while
+ * n_rows > 0; VORTA_EUNSUPPORTED for a dtype other than bf16 / fp16 or head_dim != 128.  Everything is looked at before
+ * anything is launched.  n_heads == 0 and n_rows == 0 are VORTA_OK and launch nothing.
+ */
+typedef struct vorta_gather_sample_rows_args {
+  uint32_t struct_size; /* = sizeof(vorta_gather_sample_rows_args) = vorta_gather_sample_rows_args_size() */
+  int32_t dtype, head_dim;
+  int32_t n_heads;            /* head slots in this launch (upper bound when n_heads_dev is set) */
+  int32_t n_rows;             /* the sample size n */
+  int32_t n_dup;              /* entries of one window's drop list: g - 1 - n_keep */
+  vorta_tensor q;             /* (H, S[+T], D) view, read in place */
+  vorta_tensor out;           /* (H, S[+T], D) view of the routed output, dtype of q; needed for dst_out only */
+  vorta_tensor dst_q;         /* (H, n_rows, D), or ptr NULL */
+  vorta_tensor dst_qrep;      /* (H, n_rows, D), or ptr NULL */
+  vorta_tensor dst_out;       /* (H, n_rows, D), or ptr NULL */
+  const int32_t* rows;        /* [n_rows]: the physical row of q / out for sample position p */
+  const int32_t* win;         /* [n_rows]: the coreset window of position p, or -1; needed for dst_qrep only */
+  const int32_t* keep_rows;   /* [slot][>= G]: vorta_coreset_select's keep list (its centres are read); dst_qrep only */
+  int64_t keep_rows_stride_h;
+  const int32_t* drop_rows;   /* [slot][G][n_dup]: its drop list; dst_qrep only */
+  int64_t drop_rows_stride_h;
+  const int32_t* head_list;   /* [n_heads] or NULL */
+  const int32_t* n_heads_dev; /* optional device count: slots >= *n_heads_dev write nothing */
+} vorta_gather_sample_rows_args;
+
+int vorta_gather_sample_rows(const vorta_gather_sample_rows_args* args, void* hip_stream);
+int vorta_gather_sample_rows_args_size(void);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.

@@ -187,6 +187,15 @@ class SampledFidelityArgs(C.Structure):
     ]
 
 
+class GatherSampleRowsArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("n_heads", _i32), ("n_rows", _i32), ("n_dup", _i32),
+        ("q", Tensor), ("out", Tensor), ("dst_q", Tensor), ("dst_qrep", Tensor), ("dst_out", Tensor),
+        ("rows", _vp), ("win", _vp), ("keep_rows", _vp), ("keep_rows_stride_h", _i64),
+        ("drop_rows", _vp), ("drop_rows_stride_h", _i64), ("head_list", _vp), ("n_heads_dev", _vp),
+    ]
+
+
 MIX_BWD_PARTS = 64  # include/vorta_hip.h VORTA_MIX_BWD_PARTS
 NORM_ROPE_BWD_PARTS = 1024  # include/vorta_hip.h VORTA_NORM_ROPE_BWD_PARTS
 FIDELITY_PARTS, FIDELITY_WS_FLOATS = 64, 12  # include/vorta_hip.h VORTA_FIDELITY_PARTS, VORTA_FIDELITY_WS_FLOATS
@@ -249,6 +258,8 @@ SYMBOLS = {
     "vorta_fidelity_args_size": (C.c_int, []),
     "vorta_sampled_fidelity": (C.c_int, [C.POINTER(SampledFidelityArgs), _vp]),
     "vorta_sampled_fidelity_args_size": (C.c_int, []),
+    "vorta_gather_sample_rows": (C.c_int, [C.POINTER(GatherSampleRowsArgs), _vp]),
+    "vorta_gather_sample_rows_args_size": (C.c_int, []),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "vorta_permute_heads": (C.c_int, [C.POINTER(PermuteArgs), _vp]),
     "vorta_abi_version": (C.c_int, []),
@@ -287,7 +298,7 @@ def lib():
             fn = getattr(h, name)
         except AttributeError:
             # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity, the
-            # partial-geometry entry points and vorta_sampled_fidelity without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # partial-geometry entry points, vorta_sampled_fidelity and vorta_gather_sample_rows without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
@@ -310,6 +321,9 @@ def lib():
     if h.vorta_sampled_fidelity_args_size() != C.sizeof(SampledFidelityArgs):
         raise VortaHipError(f"struct layout mismatch for SampledFidelityArgs: C {h.vorta_sampled_fidelity_args_size()} "
                             f"vs ctypes {C.sizeof(SampledFidelityArgs)}")
+    if h.vorta_gather_sample_rows_args_size() != C.sizeof(GatherSampleRowsArgs):
+        raise VortaHipError(f"struct layout mismatch for GatherSampleRowsArgs: C {h.vorta_gather_sample_rows_args_size()} "
+                            f"vs ctypes {C.sizeof(GatherSampleRowsArgs)}")
     _lib = h
     return h
 

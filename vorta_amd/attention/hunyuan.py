@@ -329,18 +329,25 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                  window_size: Tuple[int, int, int] = (3, 3, 3), tile_size: Tuple[int, int, int] = (6, 8, 8),
                  latent_shape: Tuple[int, int, int] = (30, 48, 80),
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
-                 fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse"):
+                 fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
+                 expert_fidelity: Optional[list] = None):
         """Keyword names as hunyuan.py:521-539.  `head_routing` / `experts_host` are this build's additions: the
         routes of this layer already dispatched by the step's route plan (vorta_amd/patch/_engine.py), on the device /
         on the host; without them the dispatch runs here from `routing_score`.
         fidelity: a list that receives this call's `ops.SampledFidelity` -- the routed output as run against dense attention on
         `fidelity_rows` sampled video rows of the `fidelity_heads` (routed.routed_attention; under sequence parallelism the
-        heads this rank holds, filed under their global ids: attention/_sp.py); None: the launches of today."""
+        heads this rank holds, filed under their global ids: attention/_sp.py); None: the launches of today.
+        expert_fidelity: a list that receives this call's `ops.ExpertFidelity` on the same `fidelity_rows` -- what every expert
+        would have written for every head, and the routed rows (routed.sampled_expert_fidelity); refused by name under sequence
+        parallelism."""
         self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
         q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb)
         assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
         te = self._text_valid(attention_mask, T, flex_attn_mask_func)
         if SP_STATE.enabled:
+            if expert_fidelity is not None:
+                raise NotImplementedError("sampled_expert_fidelity: the per-expert measurement on sampled rows does not run "
+                                          "under sequence parallelism (its gather reads whole heads of one process)")
             from ._sp import sp_attention
             buf = sp_attention(q, k, v, T, routing_score, tau_sparse, model="hunyuan", text_valid=te,
                                lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
@@ -352,12 +359,14 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
             _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
             head_routing = HeadRouting.from_device(lists, counts)
         buf, out = self._new_out(q)
-        if fidelity is not None:  # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
+        if fidelity is not None or expert_fidelity is not None:
+            # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
             from ..routed import routed_attention
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             routed_attention(q, k, v, head_routing, geom, model="hunyuan", text_len=T, text_valid=te, out=out,
-                             fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
+                             fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads,
+                                 expert_fidelity=expert_fidelity)
             return self._output(attn, buf, T)
         torch.ops.vorta.routed_attention(q, k, v, out, **_torch_ops.routing_args(head_routing),
                                          **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),

@@ -215,11 +215,13 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
                  window_size: Tuple[int, int, int] = (3, 3, 3), tile_size: Tuple[int, int, int] = (6, 8, 8),
                  latent_shape: Tuple[int, int, int] = (20, 30, 52), use_original_attn: bool = False,
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
-                 fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse"):
+                 fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
+                 expert_fidelity: Optional[list] = None):
         """Keyword names as wan.py:308-328; `head_routing` / `experts_host`: see the Hunyuan processor.
         fidelity: a list that receives one `ops.SampledFidelity` PER BATCH ITEM of this call, in item order (the routed output
         as run against dense attention on sampled rows, routed.routed_attention); cross attention and the dense teacher file
-        nothing; None: the launches of today."""
+        nothing; None: the launches of today.  expert_fidelity: likewise one `ops.ExpertFidelity` per batch item
+        (routed.sampled_expert_fidelity on the same `fidelity_rows`); refused by name under sequence parallelism."""
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
@@ -230,6 +232,9 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         # take one item per launch, so a batch is a loop over its items with the same routes (the scripts run B = 1:
         # pipeline_wan.py:322-344 does CFG as two forwards)
         if SP_STATE.enabled:
+            if expert_fidelity is not None:
+                raise NotImplementedError("sampled_expert_fidelity: the per-expert measurement on sampled rows does not run "
+                                          "under sequence parallelism (its gather reads whole heads of one process)")
             from ._sp import sp_attention
             bufs = [sp_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], 0, routing_score, tau_sparse, model="wan",
                                  lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
@@ -240,13 +245,15 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
             _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
             head_routing = HeadRouting.from_device(lists, counts)
         buf, out = self._new_out(q)
-        if fidelity is not None:  # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
+        if fidelity is not None or expert_fidelity is not None:
+            # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
             from ..routed import routed_attention
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             for b in range(B):
                 routed_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], head_routing, geom, model="wan", out=out[b:b + 1],
-                                 fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
+                                 fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads,
+                                 expert_fidelity=expert_fidelity)
             return self._output_proj(attn, buf)
         for b in range(B):
             torch.ops.vorta.routed_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], out[b:b + 1],

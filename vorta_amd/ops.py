@@ -1236,6 +1236,60 @@ def sampled_fidelity(ref: torch.Tensor, out: torch.Tensor, rows: torch.Tensor, h
     return into
 
 
+def gather_sample_rows(q: torch.Tensor, rows: torch.Tensor, *, dst_q: Optional[torch.Tensor] = None,
+                       dst_qrep: Optional[torch.Tensor] = None, dst_out: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, win: Optional[torch.Tensor] = None,
+                       keep_rows: Optional[torch.Tensor] = None, drop_rows: Optional[torch.Tensor] = None,
+                       head_list: Optional[torch.Tensor] = None, n_heads: Optional[int] = None,
+                       n_heads_dev: Optional[torch.Tensor] = None) -> None:
+    """vorta_gather_sample_rows: one launch fills up to three compact (H, n, D) buffers for the heads of `head_list` /
+    `n_heads` / `n_heads_dev` (as `attn_fwd` reads them; default: every head) from the (H, N, D) views `q` and `out`:
+    dst_q[h][p] = q[h][rows[p]]; dst_qrep[h][p] = q[h][rep], rep = rows[p] unless that row is among the slot's
+    drop_rows[y][win[p]] -- then keep_rows[y][win[p]], the window's centre (`coreset_select`'s lists; `win`: int32 (n,), the
+    coreset window of position p or -1); dst_out[h][p] = out[h][rows[p]].  `rows`: int32 (n,) physical rows, every value in
+    [0, N): a device contract that no host code checks (it would be a host read).  A destination left None is not written."""
+    q, out, dst_q, dst_qrep, dst_out = (t[0] if t is not None and t.dim() == 4 else t for t in (q, out, dst_q, dst_qrep, dst_out))
+    _require_gpu(q, out, dst_q, dst_qrep, dst_out, rows, win, keep_rows, drop_rows, head_list, n_heads_dev)
+    if q.dim() != 3 or q.dtype not in _DT or rows.dim() != 1:
+        raise ValueError("gather_sample_rows takes q (H,N,D) in bf16 or fp16 and a 1-D int32 row table")
+    H, _, D = q.shape
+    n = rows.numel()
+    for t in (dst_q, dst_qrep, dst_out):
+        if t is not None and (t.dim() != 3 or t.dtype != q.dtype or t.shape[0] != H or t.shape[1] < n or t.shape[2] != D):
+            raise ValueError(f"gather_sample_rows: a destination is ({H}, >= {n}, {D}) of q's dtype, got {tuple(t.shape)} {t.dtype}")
+    if dst_out is not None and (out is None or out.dim() != 3 or out.dtype != q.dtype or out.shape[0] != H or out.shape[2] != D):
+        raise ValueError("gather_sample_rows: dst_out needs `out`, an (H,N,D) view of q's dtype")
+    if n_heads is None:
+        n_heads = head_list.numel() if head_list is not None else H
+    if head_list is not None and head_list.numel() < n_heads:
+        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
+    if head_list is None and n_heads > H:
+        raise ValueError(f"n_heads = {n_heads} head slots for {H} heads")
+    a = _C.GatherSampleRowsArgs()
+    a.struct_size = C.sizeof(_C.GatherSampleRowsArgs)
+    a.dtype, a.head_dim, a.n_heads, a.n_rows = _DT[q.dtype], D, n_heads, n
+    if dst_qrep is not None:
+        if win is None or keep_rows is None or drop_rows is None or win.dim() != 1 or win.numel() != n:
+            raise ValueError("gather_sample_rows: dst_qrep needs win (n,), keep_rows (slots, >= G) and drop_rows (slots, G, n_dup)")
+        if keep_rows.dim() != 2 or drop_rows.dim() != 3 or keep_rows.shape[0] < n_heads or drop_rows.shape[0] < n_heads \
+                or keep_rows.shape[1] < drop_rows.shape[1] or keep_rows.stride(1) != 1 or not drop_rows[0].is_contiguous():
+            raise ValueError(f"gather_sample_rows: keep_rows {tuple(keep_rows.shape)} / drop_rows {tuple(drop_rows.shape)} do "
+                             f"not cover {n_heads} head slots")
+        a.n_dup = drop_rows.shape[2]
+        a.win = _ptr(win)
+        a.keep_rows, a.keep_rows_stride_h = keep_rows.data_ptr(), keep_rows.stride(0)
+        a.drop_rows, a.drop_rows_stride_h = drop_rows.data_ptr(), drop_rows.stride(0)
+        if keep_rows.dtype != torch.int32 or drop_rows.dtype != torch.int32:
+            raise ValueError("index tables must be contiguous torch.int32")
+    a.q = _tensor(q)
+    for name, t in (("out", out if dst_out is not None else None), ("dst_q", dst_q), ("dst_qrep", dst_qrep), ("dst_out", dst_out)):
+        if t is not None and t.numel():
+            setattr(a, name, _tensor(t))
+    a.rows, a.head_list, a.n_heads_dev = _ptr(rows), _ptr(head_list), _ptr(n_heads_dev)
+    if n_heads > 0:  # (n == 0: VORTA_OK, nothing launched)
+        _C.check(_C.lib().vorta_gather_sample_rows(C.byref(a), _stream()), "vorta_gather_sample_rows")
+
+
 def cast_grads(srcs, dsts) -> None:
     """vorta_cast_grads: up to three float32 (H,N,D) buffers -> 16-bit (H,N,D) views in one launch, round to nearest even."""
     _require_gpu(*srcs, *dsts)

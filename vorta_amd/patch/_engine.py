@@ -141,6 +141,13 @@ class ForwardState:
     # this forward read when it started
     routed_fidelity: Optional[Dict[int, Any]] = None
     measure_routed: Optional[Tuple[int, int, str]] = None
+    # layer -> [ops.ExpertFidelity per batch item]; a dict only under `sampled_expert_fidelity(model)`, whose (n_rows, seed)
+    # this forward read when it started
+    sampled_experts: Optional[Dict[int, Any]] = None
+    measure_experts: Optional[Tuple[int, int]] = None
+    # inside `fixed_routes(model, table)`: the (L, H) expert table this forward launches, and its per-layer HeadRouting
+    fixed_routes: Optional[List[List[int]]] = None
+    fixed_routing: Dict[int, HeadRouting] = field(default_factory=dict)
     token_shard: bool = False                    # sequence parallel: this forward got the WHOLE latent and cuts its tokens itself
 
 
@@ -237,6 +244,9 @@ class StepContext:
     fidelity: Optional[Dict[int, Any]] = None  # the statistics of the latest forward that measured (what `fidelity_of` reads)
     measure_routed: Optional[Tuple[int, int, str]] = None  # inside `routed_fidelity(model)`: (n_rows, seed, heads)
     routed_fidelity: Optional[Dict[int, Any]] = None  # the latest measured routed forward's records (`routed_fidelity_of`)
+    measure_experts: Optional[Tuple[int, int]] = None  # inside `sampled_expert_fidelity(model)`: (n_rows, seed)
+    sampled_experts: Optional[Dict[int, Any]] = None  # the latest such forward's records (`sampled_expert_fidelity_of`)
+    fixed_routes: Optional[List[List[int]]] = None  # inside `fixed_routes(model, table)`: the (L, H) expert table
 
     def state_for(self, rotary) -> Optional[ForwardState]:
         """the state of the forward a processor call belongs to: the running forward's (in grad mode filed under `rotary`
@@ -326,20 +336,38 @@ class BoundProcessor:
                 kw["head_routing"] = ctx.plan.routing(self.layer)
             if "experts_host" in self._accepted and SP_STATE.enabled:
                 kw["experts_host"] = ctx.plan.experts_host(self.layer)
-        if "fidelity_rows" in self._accepted:  # a hard-routing (Eval) processor: its sink takes the ROUTED output's statistics
-            if state.routed_fidelity is None:
+        if "fidelity_rows" in self._accepted:  # a hard-routing (Eval) processor: its sinks take the ROUTED call's statistics
+            if state.fixed_routes is not None:
+                # under `fixed_routes(model, table)`: this layer's row of the table, host counts; the plan's routes and
+                # `tau_sparse` are not consulted
+                if self.layer not in state.fixed_routing:
+                    state.fixed_routing[self.layer] = HeadRouting.from_expert_ids(state.fixed_routes[self.layer],
+                                                                                  hidden_states.device)
+                kw["head_routing"] = state.fixed_routing[self.layer]
+                kw.setdefault("tau_sparse", 0.0)
+            if state.routed_fidelity is None and state.sampled_experts is None:
                 return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
-            # under `routed_fidelity(model)`: the sample is fixed per (S, n, seed) -- one cached table, no host work per layer
+            # under `routed_fidelity(model)` / `sampled_expert_fidelity(model)`: the sample is fixed per (S, n, seed) -- one
+            # cached table, no host work per layer; the two share it
             from ..routed import sample_rows
-            n_rows, seed, heads = state.measure_routed
+            n_rows, seed = (state.measure_routed or state.measure_experts)[:2]
             S = 1
             for x in kw.get("latent_shape", self._default_latent):
                 S *= int(x)
-            kw["fidelity"] = sink = []
-            kw["fidelity_rows"], kw["fidelity_heads"] = sample_rows(S, min(n_rows, S), seed, hidden_states.device), heads
+            kw["fidelity_rows"] = sample_rows(S, min(n_rows, S), seed, hidden_states.device)
+            sink = esink = None
+            if state.routed_fidelity is not None:
+                kw["fidelity"] = sink = []
+                kw["fidelity_heads"] = state.measure_routed[2]
+            if state.sampled_experts is not None:
+                if "expert_fidelity" not in self._accepted:
+                    raise ValueError("sampled_expert_fidelity: this model's Eval processor takes no `expert_fidelity` sink")
+                kw["expert_fidelity"] = esink = []
             out = self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
             if sink:  # (a cross-attention call measures nothing)
                 state.routed_fidelity[self.layer] = sink
+            if esink:
+                state.sampled_experts[self.layer] = esink
             return out
         if state.fidelity is None or "fidelity" not in self._accepted:
             return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
@@ -404,6 +432,9 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
                                    fidelity={} if ctx.measure_fidelity and not ctx.teacher else None,
                                    routed_fidelity={} if ctx.measure_routed is not None and not ctx.teacher else None,
                                    measure_routed=ctx.measure_routed,
+                                   sampled_experts={} if ctx.measure_experts is not None and not ctx.teacher else None,
+                                   measure_experts=ctx.measure_experts,
+                                   fixed_routes=None if ctx.teacher else ctx.fixed_routes,
                                    token_shard=token_shard)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
         ctx.forwards += 1
@@ -420,6 +451,8 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
             ctx.fidelity = state.fidelity  # (small per-head tensors: kept until the next measuring forward)
         if state.routed_fidelity:
             ctx.routed_fidelity = state.routed_fidelity  # (likewise)
+        if state.sampled_experts:
+            ctx.sampled_experts = state.sampled_experts  # (likewise)
         if ctx.return_routing_scores and state.scores is not None:
             # one device read for all layers (the reference does `.detach().cpu()` per block, modeling_hunyuan.py:297)
             all_scores = state.scores.detach().cpu()
@@ -456,7 +489,7 @@ def install_timestep_capture(embedder: nn.Module, model: nn.Module, ctx: StepCon
             return None
         tau = state.kwargs.get("tau_sparse")
         if tau is None:
-            if ctx.needs_tau:
+            if ctx.needs_tau and state.fixed_routes is None:
                 raise ValueError("self_attention_kwargs has no `tau_sparse` "
                                  "(prepare_*_self_attn_kwargs(..., tau_sparse=...))")
             tau = 0.0  # soft-mixture processors use the scores only; the dispatch lists go unused

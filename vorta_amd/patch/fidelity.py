@@ -24,6 +24,16 @@ vorta_sampled_fidelity), cheap enough to stay on during a generation:
     rf = routed_fidelity_of(model)                    # ops.SampledFidelity, stacked (L, H) + `expert` (L, H) as launched
     rf.rel_error()                                    # (L, H): NaN for heads that were not measured
     evaluate_routing(rf.expert, rf, geometry)         # a head's error is its measured one
+
+What an inference forward COULD have written -- every expert of every head, on the same sample -- and a way to run by the answer:
+
+    with sampled_expert_fidelity(model, n_rows=2048, seed=0):          # Eval processors: routed.sampled_expert_fidelity per layer
+        model(hidden_states, ..., self_attention_kwargs=kw)
+    fid = sampled_expert_fidelity_of(model)           # ops.ExpertFidelity (L, H, ...): coreset, sliding tile, the routed output
+    table = routes_from_fidelity(fid, 0.05)           # the cheapest expert within the bound, per head
+    with fixed_routes(model, table), routed_fidelity(model, heads="all"):
+        model(hidden_states, ..., self_attention_kwargs=kw)            # launched by the table; routers and tau_sparse unread
+    routed_fidelity_of(model).expert                  # == table
 """
 from __future__ import annotations
 
@@ -100,6 +110,9 @@ def routed_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0, heads: 
         raise ValueError("routed_fidelity: the model was not patched with apply_vorta_transformer")
     if heads not in FIDELITY_HEADS or int(n_rows) < 0:
         raise ValueError(f"routed_fidelity: heads={heads!r} (one of {FIDELITY_HEADS}), n_rows={n_rows}")
+    if ctx.measure_experts is not None and ctx.measure_experts != (int(n_rows), int(seed)):
+        raise ValueError(f"routed_fidelity(n_rows={n_rows}, seed={seed}) inside sampled_expert_fidelity(n_rows="
+                         f"{ctx.measure_experts[0]}, seed={ctx.measure_experts[1]}): the two share one sample")
     previous, ctx.measure_routed = ctx.measure_routed, (int(n_rows), int(seed), heads)
     try:
         yield model
@@ -133,6 +146,73 @@ def routed_fidelity_of(model: nn.Module, item: int = 0) -> SampledFidelity:
         from ..attention._sp import gather_routed_fidelity
         fid = gather_routed_fidelity(fid)
     return fid
+
+
+@contextlib.contextmanager
+def sampled_expert_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0):
+    """While active, every forward of `model` (patched with apply_vorta_transformer, hard-routing Eval processors) measures
+    what EACH expert would have written: after its routed launches, every routed self-attention call runs
+    `routed.sampled_expert_fidelity` on `n_rows` sampled video rows per head (the table `routed.sample_rows(S, n_rows, seed)`,
+    shared with `routed_fidelity(model)` when both are active -- they must then name the same sample) for every head, with
+    `out=` the call's output, and files an `ops.ExpertFidelity` under its layer: column 0 coreset, column 1 sliding tile,
+    column 2 the routed output as launched, all against dense attention in the input dtype.  The flag is read once per forward,
+    when it starts; teacher forwards (`original_attention`) measure nothing.  No host read, graph-capturable; outside the
+    context the forwards launch what they launch today.  Under sequence parallelism the measuring forward raises
+    NotImplementedError by name (the gather reads whole heads of one process)."""
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("sampled_expert_fidelity: the model was not patched with apply_vorta_transformer")
+    if int(n_rows) < 0:
+        raise ValueError(f"sampled_expert_fidelity: n_rows={n_rows}")
+    if ctx.measure_routed is not None and ctx.measure_routed[:2] != (int(n_rows), int(seed)):
+        raise ValueError(f"sampled_expert_fidelity(n_rows={n_rows}, seed={seed}) inside routed_fidelity(n_rows="
+                         f"{ctx.measure_routed[0]}, seed={ctx.measure_routed[1]}): the two share one sample")
+    previous, ctx.measure_experts = ctx.measure_experts, (int(n_rows), int(seed))
+    try:
+        yield model
+    finally:
+        ctx.measure_experts = previous
+
+
+def sampled_expert_fidelity_of(model: nn.Module, item: int = 0) -> ExpertFidelity:
+    """The records of the model's latest forward under `sampled_expert_fidelity(model)`, stacked over the layers in block
+    order like `fidelity_of`'s: sq_ref, max_ref (L, H); sq_err, max_err (L, H, 3) -- `routes_from_fidelity` and
+    `evaluate_routing` take it unchanged.  `item`: the batch item (Wan files one record per item)."""
+    ctx = context_of(model)
+    filed = ctx.sampled_experts
+    if not filed:
+        raise RuntimeError("sampled_expert_fidelity_of: no forward of this model has run under sampled_expert_fidelity(model) "
+                           "with hard-routing (Eval) processors")
+    return stack_fidelity(filed[layer][item] for layer in sorted(filed))
+
+
+@contextlib.contextmanager
+def fixed_routes(model: nn.Module, table):
+    """While active, the hard-routing (Eval) processors of `model` (patched with apply_vorta_transformer) launch the (L, H)
+    expert `table` (0 full attention, 1 coreset, 2 sliding tile; e.g. `routes_from_fidelity`'s): every layer is routed by
+    `HeadRouting.from_expert_ids(table[layer])`, with host counts, so an expert no head has launches nothing.  The routers'
+    routes and `tau_sparse` are not consulted (a forward may leave `tau_sparse` out); `routed_fidelity_of(model).expert`
+    reports the table.  The table is read once per forward, when it starts; teacher forwards stay dense.  Outside the context
+    nothing changes.  ValueError for a table that is not (L, H) or holds another id.  Under sequence parallelism the context
+    refuses by name (NotImplementedError): the head placement there follows `RoutePlan.experts_host`, which knows routers only."""
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("fixed_routes: the model was not patched with apply_vorta_transformer")
+    t = torch.as_tensor(table).detach().cpu()
+    L, H = len(ctx.plan), ctx.plan.heads
+    if t.is_floating_point() or t.dtype == torch.bool or tuple(t.shape) != (L, H):
+        raise ValueError(f"fixed_routes: an integer expert table of shape ({L}, {H}) (layers, heads), got "
+                         f"{tuple(t.shape)} {t.dtype}")
+    if bool(((t < 0) | (t > 2)).any()):
+        raise ValueError("fixed_routes: expert ids are 0 (full), 1 (coreset), 2 (sliding tile)")
+    from ..ulysses import SP_STATE
+    if SP_STATE.enabled:
+        raise NotImplementedError("fixed_routes: routing by a table does not run under sequence parallelism")
+    previous, ctx.fixed_routes = ctx.fixed_routes, [[int(x) for x in row] for row in t.tolist()]
+    try:
+        yield model
+    finally:
+        ctx.fixed_routes = previous
 
 
 Geometry = Union[Mapping[str, Any], Any]

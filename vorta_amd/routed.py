@@ -69,6 +69,66 @@ class HeadRouting:
         return dict(head_list=self.lists[e], n_heads=H, n_heads_dev=self.counts_dev[e:e + 1])
 
 
+class SampleTables(NamedTuple):
+    """`RoutedGeometry.sample_tables`: the device tables of one (geometry, text length, sample table)"""
+    tokens: torch.Tensor   # the sample table itself (kept alive: the cache is keyed on its address)
+    order: torch.Tensor    # int64 (n,): compact row p holds sample position order[p]
+    rows: torch.Tensor     # int32 (n,): the physical row of compact row p
+    win: torch.Tensor      # int32 (n,): its coreset window, -1 outside the whole windows
+    classes: list          # per sliding key-list length class: (start, count, kv_lists, stride, n_kv, block_table, n_lists)
+
+
+def sample_launch_plan(latent, tile, window, group, tokens, t_eff: int = 0, block_rows: int = 256) -> dict:
+    """Host integers of a per-expert measurement on the sampled video `tokens` (ascending ids in [0, S), raster order of the
+    latent grid).  The sliding tile gives every query tile one key list (`_partial.window_geometry`: the first tile of its
+    clamped window per dimension); lists of one LENGTH are one launch, longest first, as `sta_partial_launches` forms them
+    (one class where the tile divides the grid: `sta_launch_tables`), and inside a launch the lists are in ascending order
+    of (first tile) -- the rows of those tables.  Returns
+      order   int64 (n,): the sample positions sorted by (class, list, position) -- compact row p holds tokens[order[p]]
+      win     int32 (n,): in that order, the coreset window ((t // g0) ng1 + h // g1) ng2 + w // g2 of a token inside the ng =
+              latent // group whole windows, else -1
+      classes [dict(index, n_kv, n_lists, start, count, table)]: per length class that holds a sampled position, its index among
+              ALL classes, its key count (video + t_eff), the number of its lists, its range [start, start + count) of compact
+              rows and an int32 (blocks, 3) table of (list, first row, end row) -- rows relative to `start`, at most
+              `block_rows` a block, no block across two lists."""
+    import numpy as np
+    tok = np.asarray(tokens, dtype=np.int64)
+    L = [int(x) for x in latent]
+    t, h, w = tok // (L[1] * L[2]), (tok // L[2]) % L[1], tok % L[2]
+    nt, cnt, first = _partial.window_geometry(latent, tile, window)
+    nf = [n - c + 1 for n, c in zip(nt, cnt)]
+    fa = [np.asarray(first[d], dtype=np.int64) for d in range(3)]
+    lid_of = lambda a, b, c: (fa[0][a] * nf[1] + fa[1][b]) * nf[2] + fa[2][c]  # noqa: E731
+    grid = np.meshgrid(*(np.arange(n) for n in nt), indexing="ij")
+    every = np.unique(lid_of(*grid))  # the lists some tile uses, ascending
+    ext = [[_partial.list_extent(latent, tile, d, f, cnt[d]) for f in range(nf[d])] for d in range(3)]
+    length = {int(l): ext[0][l // (nf[1] * nf[2])] * ext[1][(l // nf[2]) % nf[1]] * ext[2][l % nf[2]] + int(t_eff) for l in every}
+    lengths = sorted(set(length.values()), reverse=True)
+    members = [[l for l in every.tolist() if length[l] == n_kv] for n_kv in lengths]
+    cls_of = {l: (ci, m.index(l)) for ci, m in enumerate(members) for l in m}
+    lid = lid_of(t // int(tile[0]), h // int(tile[1]), w // int(tile[2]))
+    ci = np.array([cls_of[int(l)][0] for l in lid], dtype=np.int64)
+    gi = np.array([cls_of[int(l)][1] for l in lid], dtype=np.int64)
+    order = np.lexsort((np.arange(tok.size), gi, ci)).astype(np.int64)
+    ng = [l // int(g) for l, g in zip(L, group)]
+    inside = (t < ng[0] * group[0]) & (h < ng[1] * group[1]) & (w < ng[2] * group[2])
+    win = np.where(inside, ((t // group[0]) * ng[1] + h // group[1]) * ng[2] + w // group[2], -1).astype(np.int32)
+    classes, start = [], 0
+    for c, n_kv in enumerate(lengths):
+        g_c = gi[order][ci[order] == c]
+        if g_c.size == 0:
+            continue
+        table, p = [], 0
+        for g in np.unique(g_c).tolist():
+            end = p + int((g_c == g).sum())
+            table += [(g, x, min(x + block_rows, end)) for x in range(p, end, block_rows)]
+            p = end
+        classes.append(dict(index=c, n_kv=n_kv, n_lists=len(members[c]), start=start, count=int(g_c.size),
+                            table=np.asarray(table, dtype=np.int32)))
+        start += int(g_c.size)
+    return dict(order=order, win=win[order], classes=classes)
+
+
 @dataclass
 class RoutedGeometry:
     """Everything that depends only on (latent, tile, window, coreset window, rate, text length).
@@ -177,6 +237,31 @@ class RoutedGeometry:
         self.sta_tables(t_eff)
         if STA_MERGE and block_rows in (128, 256):
             self.sta_launch_tables(t_eff, block_rows)
+
+    def sample_tables(self, t_eff: int, tokens: torch.Tensor, block_rows: int = 256) -> "SampleTables":
+        """What `sampled_expert_fidelity` needs beside the sample itself, built ONCE per (text length, sample table) -- host
+        work (`sample_launch_plan`, which reads `tokens` back) -- and cached beside the `_sta` tables: the position order,
+        the physical rows and coreset windows in that order, and per key-list length class of the sliding expert the
+        positions' range, the key lists of `sta_launch_tables` / `sta_partial_launches` and a block table of its own.  The
+        cache holds `tokens`, so its address is not handed to another table."""
+        key = ("sample", t_eff, block_rows, tokens.data_ptr(), tokens.numel(), tokens._version)
+        if key not in self._sta:
+            plan = sample_launch_plan(self.latent, self.tile, self.window, self.group, tokens.cpu().numpy(), t_eff, block_rows)
+            if self.is_partial:
+                full = [(x[1], x[2], x[3], x[5]) for x in self.sta_partial_launches(t_eff, block_rows)]
+            else:
+                _, lists, n_kv, _, n_lists = self.sta_launch_tables(t_eff, block_rows)
+                full = [(lists, n_kv, n_kv, n_lists)]
+            classes = []
+            for c in plan["classes"]:
+                lists, stride, n_kv, n_lists = full[c["index"]]
+                assert (n_kv, n_lists) == (c["n_kv"], c["n_lists"]), "the host plan and the device tables disagree on a class"
+                classes.append((c["start"], c["count"], lists, stride, n_kv, torch.from_numpy(c["table"]).to(self.device), n_lists))
+            order = torch.from_numpy(plan["order"]).to(self.device)
+            toks = tokens.index_select(0, order)
+            rows = toks if self.row_map is None else self.row_map.index_select(0, toks)
+            self._sta[key] = SampleTables(tokens, order, rows.contiguous(), torch.from_numpy(plan["win"]).to(self.device), classes)
+        return self._sta[key]
 
     def sta_launch_tables(self, t_eff: int, block_rows: int = 256):
         """The sliding-tile launch with query tiles of EQUAL key lists merged into one group.  The reference clamps the
@@ -427,6 +512,107 @@ def _measure_routed(fidelity: list, fidelity_rows, fidelity_heads: str, q3, k3, 
     fidelity.append(stats._replace(rows=tokens, expert=_expert_ids(routing, H, q3.device)))
 
 
+SAMPLED_BLOCK_ROWS = 256  # workgroup rows of the sampled coreset and sliding launches: the body the routed launches run
+
+
+def _head_slots(heads, H: int, device) -> dict:
+    """`heads=` of `sampled_expert_fidelity` -> head_list / n_heads / n_heads_dev as the launches read them"""
+    if heads is None:
+        return dict(head_list=None, n_heads=H, n_heads_dev=None)
+    if isinstance(heads, dict):
+        return dict(head_list=heads["head_list"], n_heads=heads["n_heads"], n_heads_dev=heads.get("n_heads_dev"))
+    if isinstance(heads, tuple) and len(heads) == 2 and torch.is_tensor(heads[0]):
+        return dict(head_list=heads[0], n_heads=heads[0].numel(), n_heads_dev=heads[1])
+    if not torch.is_tensor(heads):
+        heads = torch.tensor([int(h) for h in heads], dtype=torch.int32).to(device)
+    return dict(head_list=heads, n_heads=heads.numel(), n_heads_dev=None)
+
+
+def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: RoutedGeometry, *, model: str,
+                            text_len: int = 0, text_valid: int = 0, scale: Optional[float] = None, rows=None, seed: int = 0,
+                            out: Optional[torch.Tensor] = None, heads=None, outputs: Optional[list] = None
+                            ) -> "ops.ExpertFidelity":
+    """What EVERY expert would have written for a head, on a sample of video rows: an `ops.ExpertFidelity` (column 0 coreset,
+    column 1 sliding tile against dense attention on the same rows) without the soft mixture's three full-size forwards.
+    q, k, v: as `routed_attention` takes them, (1,H,S[+T],D) or (H,..); the contractions run in their dtype, whatever
+    VORTA_ATTENTION_PRECISION says (this measures the method, not a precision).
+    rows: a sample size (None: min(DEFAULT_FIDELITY_ROWS, S); `sample_rows` with `seed`) or an int32 table of `sample_rows`.
+    Per call, all on the current stream and without a host read (graph-capturable once `geom.sample_tables` is built):
+    `ops.coreset_select` for the measured heads as the coreset expert calls it; one `ops.gather_sample_rows`; dense attention
+    on the rows' queries as `routed_attention(fidelity=...)` forms it (keys cut by `fidelity_ref_splits`); the coreset expert's
+    value at a row = its REPRESENTATIVE query (the row, or its window's centre where the head's selection dropped it) against
+    the head's keep list; the sliding tile's value = the row's query against its tile's key list, one launch per key-list
+    length with the positions ordered by key list; then `ops.expert_fidelity` on the three compact buffers.  The coreset and
+    sliding launches cut their keys by `fidelity_ref_splits(n_kv)` too -- by the key count alone, so records compare.  The
+    launches go to `ops.attn_fwd_batch`, which fuses those that qualify; every launch writes rows of its own.
+    out: the output of a routed call on the same q, k, v: column 2 of the record is then that output AS LAUNCHED against dense
+    attention (NaN without); `out` is only read.
+    heads: None = every head; else a sequence of head ids, an int32 device list, a (list, device count) pair or the
+    head_list / n_heads / n_heads_dev dictionary of `HeadRouting.slot_args`.  Heads not measured hold NaN.
+    outputs: a list that receives the compact (H, n, D) buffers -- dense, coreset, sliding (and the rows of `out`) -- and last
+    the int64 position order: compact row p is sample position order[p] (rows are ordered by sliding key list)."""
+    hy = model == "hunyuan"
+    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
+    o3 = None if out is None else (out[0] if out.dim() == 4 else out)
+    H, D, S, rm = q3.shape[0], q3.shape[-1], geom.S, geom.row_map
+    T, te = (text_len, text_valid) if hy else (0, 0)
+    if rm is None and q3.shape[1] != S + T:
+        raise ValueError(f"Input sequence length {q3.shape[1] - T} does not match latent shape {geom.latent}.")
+    if rows is None:
+        rows = min(DEFAULT_FIDELITY_ROWS, S)
+    tokens = rows if torch.is_tensor(rows) else sample_rows(S, rows, seed, q3.device)
+    if tokens.dim() != 1 or tokens.dtype != torch.int32 or tokens.numel() > S:
+        raise ValueError("rows: a sample size, or an int32 table of video tokens (routed.sample_rows)")
+    n, dev = tokens.numel(), q3.device
+    sl = _head_slots(heads, H, dev)
+    tabs = geom.sample_tables(te, tokens, SAMPLED_BLOCK_ROWS)
+    # every row of a buffer the statistics pass reads is written only for the measured heads: the others hold zeros
+    new = torch.empty if sl["head_list"] is None else torch.zeros
+    q_own, q_rep, ref, low, sta = (new((H, n, D), dtype=q3.dtype, device=dev) for _ in range(5))
+    mixed = new((H, n, D), dtype=q3.dtype, device=dev) if o3 is not None else None
+    if n and sl["n_heads"]:
+        pk = dict(partial=True) if geom.is_partial else {}
+        gm = CORESET_KV_GROUP_MAJOR
+        if hy:  # K matched on its own, V follows K: `routed_attention`'s expert_lowres
+            keep_q, drop_q = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm,
+                                                **pk, **sl)
+            kk = ops.coreset_select(k3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=te, row_map=rm,
+                                    want_drop=False, want_keep=not gm, want_kv=gm, **pk, **sl)
+            keep_k = kk[2] if gm else kk[0]
+        else:
+            kq = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm, want_kv=gm,
+                                    **pk, **sl)
+            keep_q, drop_q = kq[0], kq[1]
+            keep_k = kq[2] if gm else keep_q
+        ops.gather_sample_rows(q3, tabs.rows, dst_q=q_own, dst_qrep=q_rep, dst_out=mixed, out=o3, win=tabs.win,
+                               keep_rows=keep_q, drop_rows=drop_q, **sl)
+        n_low = geom.S_low + te
+        common = dict(k=k3, v=v3, scale=scale, **sl)
+        calls = [dict(common, q=q_own, out=ref, n_q=n, q_valid=n, n_kv=S + te, kv_rows=None if rm is None else rm[:S + te],
+                      n_splits=fidelity_ref_splits(S + te), tag="fidelity_ref"),
+                 dict(common, q=q_rep, out=low, n_q=n, q_valid=n, n_kv=n_low, kv_rows=keep_k,
+                      n_splits=fidelity_ref_splits(n_low), block_rows=SAMPLED_BLOCK_ROWS, tag="sampled_lowres")]
+        for start, count, lists, stride, n_kv, table, n_lists in tabs.classes:
+            calls.append(dict(common, q=q_own[:, start:start + count], out=sta[:, start:start + count], n_q=count, n_kv=n_kv,
+                              kv_rows=lists, kv_rows_stride_g=stride, q_block_table=table, n_key_lists=n_lists,
+                              n_splits=fidelity_ref_splits(n_kv), block_rows=SAMPLED_BLOCK_ROWS, tag="sampled_sliding"))
+        for i in range(0, len(calls), ops.MAX_FUSED):
+            ops.attn_fwd_batch(calls[i:i + ops.MAX_FUSED])
+    fid = ops.expert_fidelity([ref, low, sta], mixed)
+    if sl["head_list"] is not None:  # NaN for the heads no slot names (slots at or past a device count are not read)
+        slot = torch.arange(sl["n_heads"], device=dev)
+        count = sl["n_heads"] if sl["n_heads_dev"] is None else sl["n_heads_dev"]
+        named = torch.zeros(H + 1, dtype=torch.bool, device=dev)
+        named.index_fill_(0, torch.where(slot < count, sl["head_list"][:sl["n_heads"]].long(), torch.full_like(slot, H)), True)
+        named = named[:H]
+        nan = lambda x: torch.where(named if x.dim() == 1 else named[:, None], x, torch.full_like(x, float("nan")))  # noqa: E731
+        fid = fid._replace(sq_ref=nan(fid.sq_ref), max_ref=nan(fid.max_ref), sq_err=nan(fid.sq_err), max_err=nan(fid.max_err),
+                           range_ref=nan(fid.range_ref))
+    if outputs is not None:
+        outputs.extend([ref, low, sta] + ([mixed] if mixed is not None else []) + [tabs.order])
+    return fid
+
+
 def _side_streams(device: torch.device):
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _SIDE_STREAMS:
@@ -441,7 +627,7 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                      expert_outs: Optional[Sequence[torch.Tensor]] = None, fp8=None, fp8_operands=None,
                      operands: Optional[AttnOperands] = None, kv_splits: int = 1,
                      record: Optional[list] = None, fidelity: Optional[list] = None, fidelity_rows=None,
-                     fidelity_heads: str = "sparse") -> torch.Tensor:
+                     fidelity_heads: str = "sparse", expert_fidelity: Optional[list] = None) -> torch.Tensor:
     """q,k,v: (1,H,S+T,D) [hunyuan: video then text] or (1,H,S,D) [wan].  Returns (1,H,S+T,D).
 
     hunyuan: hunyuan.py:556-605 (TripleEval.__call__ steps 5.1-5.4);  wan: wan.py:351-383.
@@ -470,7 +656,11 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     fidelity_heads: "sparse" = the heads of experts 1 and 2, "all" = expert 0's as well (what 8 bits cost a full head); heads
     split by query range are never measured; unmeasured heads hold NaN.  Every launch is on the current stream, nothing is
     read back (the record's `expert` ids are a device tensor).  None (default): nothing is allocated or launched beyond the
-    routed calls; `out` has the same bits either way.  The reference launches are launches of their own after the routed grid."""
+    routed calls; `out` has the same bits either way.  The reference launches are launches of their own after the routed grid.
+    expert_fidelity: a list that receives one `ops.ExpertFidelity` of this call: `sampled_expert_fidelity` on the same
+    `fidelity_rows`, for every head, after the routed launches and with `out=` this call's output -- what each expert WOULD
+    have written on the sampled rows (columns 0 / 1) beside what the call did write (column 2), all against dense attention
+    in the input dtype.  None (default): nothing is allocated or launched for it."""
     if q.dim() == 4 and q.shape[0] != 1:
         # hunyuan.py:168 asserts batch 1; Wan's CFG runs two batch-1 forwards (pipeline_wan.py:322-344)
         raise AssertionError(f"Batch size {q.shape[0]} is not supported by routed_attention.")
@@ -481,8 +671,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     if rm is None and N != S + T:
         raise ValueError(f"Input sequence length {N - T} does not match latent shape {geom.latent}.")
     te = text_valid if hy else 0
-    if fidelity is not None and expert_outs is not None:
-        raise ValueError("fidelity= measures the routed output `out`: it does not go with expert_outs")
+    if (fidelity is not None or expert_fidelity is not None) and expert_outs is not None:
+        raise ValueError("fidelity= / expert_fidelity= measure the routed output `out`: they do not go with expert_outs")
     if out is None and expert_outs is None:
         out = torch.empty_like(q)
     q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
@@ -609,6 +799,9 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     def measured(result):
         if fidelity is not None:
             _measure_routed(fidelity, fidelity_rows, fidelity_heads, q3, k3, v3, o_e[0], routing, geom, te, scale)
+        if expert_fidelity is not None:
+            expert_fidelity.append(sampled_expert_fidelity(q3, k3, v3, geom, model=model, text_len=T, text_valid=te, scale=scale,
+                                                           rows=fidelity_rows, out=o_e[0]))
         return result
 
     if fused and not concurrent and sliding_block_rows == 0:
