@@ -54,7 +54,10 @@ extern "C" {
                                    and the routed output's fidelity on sampled rows, vorta_sampled_fidelity (a pure addition: a
                                    binding asks for the symbol and for vorta_sampled_fidelity_args_size())
                                    and the sampled rows of a per-expert measurement, vorta_gather_sample_rows (a pure addition:
-                                   a binding asks for the symbol and for vorta_gather_sample_rows_args_size()) */
+                                   a binding asks for the symbol and for vorta_gather_sample_rows_args_size())
+                                   and the fused 16-bit grid in ticket order, vorta_attn_fwd_batch_tickets /
+                                   vorta_attn_ticket_workspace_ints (a pure addition: two more symbols on the existing
+                                   argument block; an older ABI-9 library lacks them, which a binding sees at symbol lookup) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -153,6 +156,21 @@ int vorta_attn_fwd(const vorta_attn_args* args, void* hip_stream);
  * expert instead of idling until a kernel boundary.  Every entry must resolve to the 256-row pipelined kernel
  * (VORTA_EUNSUPPORTED otherwise: launch those separately); split-key entries get their merge kernels after. */
 int vorta_attn_fwd_batch(const vorta_attn_args* args, int32_t n, void* hip_stream);
+/* The same fused grid in TICKET ORDER (ABI 9, a pure addition: a binding asks for the two symbols; 16-bit family only).
+ * vorta_attn_fwd_batch decodes a block index to a fixed logical workgroup: every XCD computes a fixed eighth of every
+ * segment, and the grid ends with its slowest XCD.  Here a workgroup takes a ticket when it starts instead: from its own XCD
+ * class's share of the segments in order (the same workgroups in the same order while that share lasts, so one head's K/V
+ * still streams through one L2), then from the class with the most left.  What a logical workgroup computes and writes is
+ * unchanged, so outputs are bit-identical to vorta_attn_fwd_batch.
+ * The grid is launched with an eighth more blocks than it has logical workgroups (rounded up to a multiple of 8; a profiler
+ * shows that size): the hardware deals blocks to the XCDs round-robin whatever their load, so only spare blocks let an XCD
+ * that is done early take over work.  A block that finds every counter exhausted exits at once.
+ * `tickets`: device memory, vorta_attn_ticket_workspace_ints() int32 (8 per segment + 8), 4-byte aligned, owned by the caller
+ * and used by ONE grid at a time (one workspace per stream).  The call zeroes it with a one-block kernel enqueued on
+ * `hip_stream` in front of the grid -- under stream capture a node of the graph, so a replay starts from zero too; nothing
+ * synchronises with the host.  NULL: exactly vorta_attn_fwd_batch. */
+int vorta_attn_fwd_batch_tickets(const vorta_attn_args* args, int32_t n, int32_t* tickets, void* hip_stream);
+int vorta_attn_ticket_workspace_ints(void);
 /* the launch shape vorta_attn_fwd would use: query rows per workgroup (128 -> kernel attn_fwd_kernel<T,4>,
  * 256 -> attn_fwd_kernel<T,8>) and the number of workgroups; pure host computation */
 int vorta_attn_plan(const vorta_attn_args* args, int32_t* block_rows, int64_t* n_workgroups, int32_t* kernel_id);

@@ -219,6 +219,8 @@ def sampled_fidelity_chain(n_rows: int) -> int:
 SYMBOLS = {
     "vorta_attn_fwd": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "vorta_attn_fwd_batch": (C.c_int, [C.POINTER(AttnArgs), _i32, _vp]),
+    "vorta_attn_fwd_batch_tickets": (C.c_int, [C.POINTER(AttnArgs), _i32, _vp, _vp]),
+    "vorta_attn_ticket_workspace_ints": (C.c_int, []),
     "vorta_attn_plan": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
     "vorta_attn_workspace_bytes": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vorta_fp8_quant_ws_floats": (C.c_int, [_i32, _i32]),
@@ -298,7 +300,7 @@ def lib():
             fn = getattr(h, name)
         except AttributeError:
             # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity, the
-            # partial-geometry entry points, vorta_sampled_fidelity and vorta_gather_sample_rows without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # partial-geometry entry points, vorta_sampled_fidelity, vorta_gather_sample_rows and the ticket-order fused grid without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res

@@ -9,6 +9,7 @@ profiles/) can be re-run, and none is a tuning knob:
     joint_projection=0       separate q / k / v projections + torch.cat (the reference's route) in the Hunyuan processors
     attn_variant=1           the first, register-staged 16-bit kernel
     no_xcd_remap=1           workgroups in launch order (no XCD-aware live order)
+    fused_tickets=0          the 16-bit fused grid in the static order of its block indices (no ticket counters; the same bits)
     sp_staging=torch         index ops instead of vorta_permute_heads in the sequence-parallel staging passes
     sp_group_streams=0       slot groups attend on the current stream instead of alternating streams
     sp_v_wire=0              e4m3 attention under sequence parallelism exchanges v in 16 bits
@@ -17,7 +18,7 @@ The product switches (README "Environment switches") are not here: VORTA_ATTENTI
 VORTA_SP_KV_SPLITS, VORTA_SP_BUFFER_SETS, VORTA_I8_TAIL_MIN_RMS, VORTA_HIP_LIB."""
 import os
 
-KEYS = ("coreset_kv_order", "fused_text_splits", "sta_merge", "fp8_center_k", "joint_projection", "attn_variant", "no_xcd_remap",
+KEYS = ("coreset_kv_order", "fused_text_splits", "sta_merge", "fp8_center_k", "joint_projection", "attn_variant", "no_xcd_remap", "fused_tickets",
         "sp_staging", "sp_group_streams", "sp_v_wire", "sp_emulate_link_gbps")
 
 

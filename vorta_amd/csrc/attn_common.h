@@ -89,12 +89,69 @@ template <class PP> struct MultiOf {
 // the segment's logical ids (same head, neighbouring query blocks -> one L2 serves the K/V stream instead of eight).  Every
 // XCD still gets 1/8 of every segment, which keeps the chip balanced across segments of different cost.
 template <class PP>
-__device__ __forceinline__ const PP& segment_of(const MultiOf<PP>& mp, int b, int& wg) {
+__device__ __forceinline__ int segment_index(const MultiOf<PP>& mp, int b, int& wg) {
   int s = 0;
 #pragma unroll
   for (int i = 1; i < MAX_SEGMENTS; ++i) s += (i < mp.n && b >= mp.start[i]) ? 1 : 0;
   wg = live_order(base_of(mp.seg[s]), b - mp.start[s], mp.start[s + 1] - mp.start[s], true);
-  return mp.seg[s];
+  return s;
+}
+template <class PP>
+__device__ __forceinline__ const PP& segment_of(const MultiOf<PP>& mp, int b, int& wg) {
+  return mp.seg[segment_index(mp, b, wg)];
+}
+
+// Ticket order of a fused grid (the 16-bit family; vorta_attn_fwd_batch_tickets).  cnt[s * 8 + x] counts the tickets drawn
+// from the share of XCD class x (= block index & 7) in segment s: the chunk of the segment's live logical ids that
+// live_order gives that class, drawn in the same order.  A workgroup draws from its own class, segments in order; when
+// its class has nothing left in any segment it draws from the (segment, class) with the most left.  It returns the
+// segment (wg = the logical workgroup there), or -1 when every counter is exhausted -- the grid has at least one block per
+// live or dead logical id (grid_blocks below) and a block exits only when nothing is left, so every live id is drawn.
+// No workgroup waits for another: a draw that loses a race sees that counter exhausted on its next read (counters only
+// grow), so the loop ends after at most one round per counter.  The counters are read and advanced at agent scope: the
+// XCDs' L2s are not coherent with each other.  Called by all 64 lanes of one wave; TICKET_INTS counters, zero at launch.
+constexpr int TICKET_INTS = 8 * MAX_SEGMENTS + 8;  // (the last eight are spare: the size the header promises)
+static_assert(MAX_SEGMENTS <= 8, "draw_ticket keeps one (segment, class) pair per lane");
+template <class PP>
+__device__ __forceinline__ int draw_ticket(const MultiOf<PP>& mp, int32_t* cnt, int b, int& wg) {
+  const int lane = threadIdx.x & 63;
+  const int x_l = lane & 7;
+  int len_l = 0, base_l = 0;  // lane s * 8 + x: the share of class x in segment s
+#pragma unroll
+  for (int i = 0; i < MAX_SEGMENTS; ++i) {
+    if (i < mp.n) {
+      const Params& p = base_of(mp.seg[i]);
+      int n = mp.start[i + 1] - mp.start[i];
+      if (p.n_heads_dev) n = min(n, max(*p.n_heads_dev, 0) * p.wg_per_slot);
+      const int qd = n >> 3, r = n & 7;
+      if ((lane >> 3) == i) {
+        len_l = qd + (x_l < r ? 1 : 0);
+        base_l = x_l < r ? x_l * (qd + 1) : r * (qd + 1) + (x_l - r) * qd;
+      }
+    }
+  }
+  for (;;) {
+    int left = 0;
+    if (len_l > 0) left = max(len_l - __hip_atomic_load(cnt + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0);
+    int pick;
+    const unsigned long long own = __ballot(left > 0 && x_l == (b & 7));
+    if (own) {
+      pick = __ffsll(own) - 1;
+    } else {
+      int most = left;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) most = max(most, __shfl_xor(most, off));
+      if (most == 0) return -1;
+      pick = __ffsll(__ballot(left == most)) - 1;
+    }
+    int t = 0;
+    if (lane == pick) t = __hip_atomic_fetch_add(cnt + lane, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = __shfl(t, pick);
+    if (t < __shfl(len_l, pick)) {
+      wg = __shfl(base_l, pick) + t;
+      return pick >> 3;
+    }
+  }
 }
 
 // Per-channel factor of the merged output: v_descale[head] for the families with e4m3 V, none in 16 bits
@@ -197,9 +254,42 @@ int fwd_single(const F& f, const vorta_attn_args* a, void* hip_stream) {
   return launch_single<_Float16>(F::template kernel<_Float16>(*a, pp, block_rows), block_rows, pp, st);
 }
 
-template <typename T, class PP>
-int launch_fused(void (*kernel)(MultiOf<PP>), const MultiOf<PP>& mp, int total, hipStream_t st) {
-  hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(512), 0, st, mp);
+// What a fused grid needs enqueued in front of it, by the further arguments of the family's fused kernel: nothing, or (the
+// 16-bit family's ticket counters) their reset.  A one-block kernel on the launch stream rather than a reset by the grid's
+// last workgroup: it is a node of a captured graph like the grid itself, so every replay starts from zero as well, it costs
+// the grid no counter of arrivals and no agent-scope release, and a launch that was cut short cannot leave the counters
+// of the next one dirty.  (Not hipMemsetAsync: captured with the layer in a torch.cuda.graph, the counters were zero for
+// the first replay only and the second replay's workgroups found them exhausted -- tests/test_hip_fused_ticket_order.py.)
+template <int N>
+__global__ void ticket_reset_kernel(int32_t* cnt) {
+  if (threadIdx.x < N) cnt[threadIdx.x] = 0;
+}
+inline int before_grid(hipStream_t) { return VORTA_OK; }
+template <class I>  // (a template, so that only the object that passes counters holds the reset kernel)
+int before_grid(hipStream_t st, I* tickets) {
+  if (!tickets) return VORTA_OK;
+  hipLaunchKernelGGL(ticket_reset_kernel<TICKET_INTS>, dim3(1), dim3(64), 0, st, tickets);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+}
+
+// Blocks of a fused grid with `total` logical workgroups.  In ticket order an eighth more (a multiple of 8, so every XCD
+// class gets the same): the hardware deals blocks to the XCDs round-robin whatever their load, so with one block per
+// ticket every XCD runs exactly its eighth of the blocks however early it is done -- a traced Hunyuan layer in ticket
+// order ended with the same 1 179 workgroups on every XCD, up to 5 ms apart (profiles/fused_grid_ticket_order.txt).  The
+// spare blocks are the last of their class to be dispatched: on an XCD that is done early they draw what the late ones
+// have left, on the others they find every counter exhausted and exit.
+inline int grid_blocks(int64_t total) { return (int)total; }
+template <class I>
+int grid_blocks(int64_t total, I* tickets) {
+  if (!tickets) return (int)total;
+  return (int)min((int64_t)0x7fffffff, total + ((total / 8 + 7) & ~(int64_t)7));
+}
+
+// (extra...: further kernel arguments of a family's fused kernel -- the 16-bit one takes its ticket counters)
+template <typename T, class PP, class... X>
+int launch_fused(void (*kernel)(MultiOf<PP>, X...), const MultiOf<PP>& mp, int total, hipStream_t st, X... extra) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(512), 0, st, mp, extra...);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return vorta_set_hip_error(e);
   for (int i = 0; i < mp.n; ++i) {
@@ -211,8 +301,8 @@ int launch_fused(void (*kernel)(MultiOf<PP>), const MultiOf<PP>& mp, int total, 
 
 // vorta_attn_fwd_batch and its siblings: up to MAX_SEGMENTS launches as the segments of ONE grid, in the given order.
 // Empty launches are skipped; the others must resolve to the 256-row pipelined kernel and share one output type.
-template <class F>
-int fwd_batch(const F& f, const vorta_attn_args* args, int32_t n, void* hip_stream) {
+template <class F, class... X>
+int fwd_batch(const F& f, const vorta_attn_args* args, int32_t n, void* hip_stream, X... extra) {
   if (!args || n < 0 || n > MAX_SEGMENTS) return VORTA_EINVAL;
   MultiOf<typename F::PP> mp{};
   int64_t total = 0;
@@ -238,8 +328,11 @@ int fwd_batch(const F& f, const vorta_attn_args* args, int32_t n, void* hip_stre
   for (int i = m; i <= MAX_SEGMENTS; ++i) mp.start[i] = (int)total;
   mp.n = m;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (dtype == VORTA_BF16) return launch_fused<__bf16>(F::template multi<__bf16>, mp, (int)total, st);
-  return launch_fused<_Float16>(F::template multi<_Float16>, mp, (int)total, st);
+  const int rc = before_grid(st, extra...);
+  if (rc != VORTA_OK) return rc;
+  const int blocks = grid_blocks(total, extra...);
+  if (dtype == VORTA_BF16) return launch_fused<__bf16>(F::template multi<__bf16>, mp, blocks, st, extra...);
+  return launch_fused<_Float16>(F::template multi<_Float16>, mp, blocks, st, extra...);
 }
 
 // attn_fwd.hip: argument validation + launch geometry (in_esize = bytes per q/k element, v_esize per v element: 0 = the

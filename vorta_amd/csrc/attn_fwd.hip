@@ -57,11 +57,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const Params p) {
   const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
   const int nblk_total = (n_kv + KVB - 1) / KVB;
   const int blk0 = sp * p.blocks_per_split;
-  const int blk1 = min(blk0 + p.blocks_per_split, nblk_total);
+  // a workgroup whose rows are all past q_valid has no key loop: its rows are zero bits whatever the keys hold
+  const int blk1 = p0 >= q_valid ? blk0 : min(blk0 + p.blocks_per_split, nblk_total);
 
   // ---- query rows ----
   const int wrow0 = p0 + wave * 32;
   const bool wave_active = wrow0 < pend;  // wave-uniform
+  // a wave whose rows are all past q_valid stages tiles and meets the barriers like an inactive one, computes nothing and
+  // goes to the epilogue with zero accumulators (every row of it is `past` there)
+  const bool wave_compute = wave_active && wrow0 < q_valid;
   const int my_p = wrow0 + r32;
   const bool row_ok = my_p < pend;
   const int ld_p = min(my_p, pend - 1);
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const Params p) {
     const int buf = (blk - blk0) & 1;
     const char* sb = smem + buf * BUF_BYTES;
     V8 pb[4];
-    if (wave_active) {
+    if (wave_compute) {
       // ---------------- S^T = K . Q^T ----------------
       f32x16 s0, s1;
 #pragma unroll
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const Params p) {
       if (blk + 2 < blk1) { ISSUE_LOADS(); }
       if (blk + 3 < blk1) { FETCH_ROWS(blk + 3); }
     }
-    if (wave_active) {
+    if (wave_compute) {
       // ---------------- O^T += V^T . P^T ----------------
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
@@ -310,9 +314,14 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   const int qb = rest % n_qb;
   const int y = rest / n_qb;
   if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
+  // (UNI: what this workgroup reads from device memory through a workgroup-uniform address stays in scalar registers.  The
+  // compiler proves that by itself only in a kernel that writes no memory in front of the load; the fused kernel's ticket
+  // draw does, and without this the query block's bounds became vector values that lived across the loops: 2 spilled VGPRs)
+#define UNI(x_) __builtin_amdgcn_readfirstlane(x_)
+  const int head = p.head_list ? UNI(p.head_list[y]) : y;
   int grp, p0, pend;
   q_block_of(p, qb, QB, grp, p0, pend);
+  grp = UNI(grp); p0 = UNI(p0); pend = UNI(pend);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -321,15 +330,20 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   const int hh = lane >> 5;
 
   // ---- key block range of this split (n_kv / q_valid may live on the device: no host sync) ----
-  const int n_kv = p.n_kv_dev ? max(1, min(*p.n_kv_dev, p.n_kv)) : p.n_kv;
-  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
+  const int n_kv = p.n_kv_dev ? max(1, min(UNI(*p.n_kv_dev), p.n_kv)) : p.n_kv;
+  const int q_valid = p.q_valid_dev ? min(UNI(*p.q_valid_dev), p.q_valid) : p.q_valid;
+#undef UNI
   const int nblk_total = (n_kv + KVB - 1) / KVB;
   const int blk0 = sp * p.blocks_per_split;
-  const int blk1 = min(blk0 + p.blocks_per_split, nblk_total);
+  // a workgroup whose rows are all past q_valid has no key loop: its rows are zero bits whatever the keys hold
+  const int blk1 = p0 >= q_valid ? blk0 : min(blk0 + p.blocks_per_split, nblk_total);
 
   // ---- query rows ----
   const int wrow0 = p0 + wave * 32;
   const bool wave_active = wrow0 < pend;  // wave-uniform
+  // a wave whose rows are all past q_valid requests tiles and meets the barriers like an inactive one, issues no MFMA, exp
+  // or fragment read and goes to the epilogue with zero accumulators (every row of it is `past` there)
+  const bool wave_compute = wave_active && wrow0 < q_valid;
   const int my_p = wrow0 + r32;
   const int ld_p = min(my_p, pend - 1);
   const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
@@ -562,7 +576,7 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
   }
 #define STEP_BODY(c0_, c1_, n0_, n1_, kcur_, knext_, j_, tail_)                   \
   {                                                                               \
-    if (wave_active) {                                                            \
+    if (wave_compute) {                                                           \
       V8 kpre_[KPRE > 0 ? KPRE : 1][2];                                                          \
       _Pragma("unroll") for (int ks_ = 0; ks_ < KPRE; ++ks_) {                    \
         kpre_[ks_][0] = *(const V8*)(smem + (knext_) * TILE_BYTES + k_rd[ks_]);   \
@@ -631,7 +645,7 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
       _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) { offK[i_] = (unsigned)K_OFF(i_); offV[i_] = (unsigned)V_OFF(i_); }
     }
     __syncthreads();
-    if (wave_active) {
+    if (wave_compute) {
       QK(sA0, sA1, 0)  // seed 0: plain scores of the first block
       if (blk0 * KVB + KVB > n_kv) {
 #pragma unroll
@@ -692,7 +706,11 @@ __device__ __forceinline__ void attn_pipe_dma_body(const Params& p, char* __rest
 #undef V_OFF
 
   TRACE_FLUSH_()
-  if (!wave_active) return;
+  // (wave_active again from its operands, opaque to the compiler: kept across the loops beside wave_compute, the flag cost
+  // the fused kernel two spilled SGPRs and with them a VGPR)
+  int wrow0_e = wrow0;
+  asm volatile("" : "+v"(wrow0_e));
+  if (__builtin_amdgcn_readfirstlane(wrow0_e) >= pend) return;
   // ---------------- epilogue ----------------
   // The row bookkeeping (e_p = my_p, hh_e = hh, e_row = my_row of the prologue) is derived again from the thread id,
   // opaque to the compiler, so that it is not the prologue's values kept in registers across both loops.  The 0 VGPR
@@ -777,14 +795,37 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_pipe_kernel(const Params 
 // few waves of workgroups per CU-set, fewer still under sequence parallelism) is filled by the next expert's
 // workgroups instead of idling until a kernel boundary.
 
+// `tickets` = the caller's counters of draw_ticket (attn_common.h), zeroed on the launch stream in front of the grid: a
+// workgroup then computes the logical workgroup its ticket names instead of the one its block index decodes to.  Null:
+// the static order of segment_of.
 template <typename T>
-__global__ __launch_bounds__(512, 2) void attn_fwd_multi_kernel(const MultiOf<Params> mp) {
+__global__ __launch_bounds__(512, 2) void attn_fwd_multi_kernel(const MultiOf<Params> mp, int32_t* tickets) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub
   __shared__ __attribute__((aligned(16))) char smem[2 * RING * TILE_BYTES];  // K and V rings
-  int wg;
-  const Params& p = segment_of(mp, blockIdx.x, wg);
+  int wg, s;
+  if (tickets) {
+    // wave 0 draws, the workgroup learns the result through the first words of the K ring, which nothing uses yet; the
+    // second barrier keeps the body's first tile request off them until every wave has read.  (The words are the ring's
+    // own: a variable of their own moved the rings off offset 0 of the LDS allocation, and the whole grid ran 12 % slower,
+    // in static order too -- profiles/fused_grid_ticket_order.txt)
+    int* drawn = (int*)smem;
+    if (threadIdx.x < 64) {
+      int w;
+      const int sg = draw_ticket(mp, tickets, blockIdx.x, w);
+      if (threadIdx.x == 0) { drawn[0] = sg; drawn[1] = w; }
+    }
+    __syncthreads();
+    s = __builtin_amdgcn_readfirstlane(drawn[0]);
+    wg = __builtin_amdgcn_readfirstlane(drawn[1]);
+    __syncthreads();
+    if (s < 0) return;  // every counter exhausted: the grid's other workgroups hold all the work
+  } else {
+    s = segment_index(mp, blockIdx.x, wg);
+  }
+  const Params& p = mp.seg[s];
   if (p.kv_rows) attn_pipe_dma_body<T, 8, true, RING>(p, smem, wg);
   else attn_pipe_dma_body<T, 8, false, RING>(p, smem, wg);
+  TRACE_WG_END_(p, wg)
 #endif
 }
 
@@ -905,7 +946,14 @@ extern "C" int vorta_attn_plan(const vorta_attn_args* a, int32_t* block_rows_out
 }
 
 extern "C" int vorta_attn_fwd_batch(const vorta_attn_args* args, int32_t n, void* hip_stream) {
-  return fwd_batch(Family16{}, args, n, hip_stream);
+  return fwd_batch(Family16{}, args, n, hip_stream, (int32_t*)nullptr);
+}
+
+extern "C" int vorta_attn_ticket_workspace_ints(void) { return TICKET_INTS; }
+
+extern "C" int vorta_attn_fwd_batch_tickets(const vorta_attn_args* args, int32_t n, int32_t* tickets, void* hip_stream) {
+  if ((uintptr_t)tickets & 3) return VORTA_EINVAL;
+  return fwd_batch(Family16{}, args, n, hip_stream, tickets);
 }
 
 extern "C" int vorta_attn_fwd(const vorta_attn_args* a, void* hip_stream) { return fwd_single(Family16{}, a, hip_stream); }

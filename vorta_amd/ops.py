@@ -40,6 +40,23 @@ _timeline: Optional[Timeline] = None
 from ._debug import flag as _debug_flag  # (A/B switches: one gate, VORTA_DEBUG)
 DEFAULT_VARIANT = int(_debug_flag("attn_variant", "0"))
 NO_XCD_REMAP = int(_debug_flag("no_xcd_remap", "0"))
+# the 16-bit fused grid hands its workgroups out by ticket (vorta_attn_fwd_batch_tickets); 0 = the static order of the
+# block index (vorta_attn_fwd_batch) -- the same bits either way
+FUSED_TICKETS = int(_debug_flag("fused_tickets", "1"))
+_ticket_ws: dict = {}  # (device index, stream) -> the int32 counters of that stream's fused grids
+
+
+def _tickets(device: torch.device) -> int:
+    """the ticket counters of fused grids on `device`'s current stream: allocated once, zeroed by every launch itself on its
+    stream, so one grid at a time uses them.  224 bytes per stream that ever ran a fused grid, kept for the life of the
+    process (a stream handle may be reused by a later stream: the counters serve it as well).  First asked for inside a
+    graph capture they come from that graph's pool and their initial zeroing is a node of the graph: harmless, since every
+    launch zeroes them itself, but a warm-up on the capture stream -- which a capture needs anyway -- allocates them outside"""
+    key = (device.index, _stream())
+    ws = _ticket_ws.get(key)
+    if ws is None:
+        ws = _ticket_ws[key] = torch.zeros(_C.lib().vorta_attn_ticket_workspace_ints(), dtype=torch.int32, device=device)
+    return ws.data_ptr()
 
 
 def set_timeline(t: Optional[Timeline]):
@@ -137,6 +154,7 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     a._ext = None
     a._family = _FAMILIES["i8" if i8 else "fp8" if fp8 else "mx" if mixed else "16"]
     a._out_type = "_Float16" if out.dtype == torch.float16 else "__bf16"  # T of the kernel symbols
+    a._device = out.device
     if i8:
         ext = _C.AttnI8Ext()
         ext.struct_size = C.sizeof(_C.AttnI8Ext)
@@ -363,7 +381,12 @@ def attn_fwd_batch_built(built, fuse: bool = True) -> None:
                 raise ValueError(f"fused launch {i} carries other 8-bit operands or options than launch 0 ({', '.join(diff)}): "
                                  "one grid takes one operand set; launch it separately")
     arr = (_C.AttnArgs * len(args))(*args)
-    go = lambda: _C.check(getattr(_C.lib(), fam.batch)(arr, *_ext(args[0]), len(args), _stream()), fam.batch)
+    if fam is _FAMILIES["16"] and FUSED_TICKETS:
+        tickets = _tickets(built[0][0]._device)
+        go = lambda: _C.check(_C.lib().vorta_attn_fwd_batch_tickets(arr, len(args), tickets, _stream()),
+                              "vorta_attn_fwd_batch_tickets")
+    else:
+        go = lambda: _C.check(getattr(_C.lib(), fam.batch)(arr, *_ext(args[0]), len(args), _stream()), fam.batch)
     _timed(go, "+".join(t for _, _, t, _ in built), sum(f for _, _, _, f in built), args, fam.multi.format(t=args[0]._out_type))
 
 
