@@ -22,7 +22,7 @@ from oracle import vorta_oracle as O
 pytestmark = pytest.mark.gpu
 
 from _util import dev, rel_fro, to_dev  # noqa: E402
-from test_hip_fp8 import RELF_PACK, _check, _vmax  # noqa: E402
+from test_hip_fp8 import RELF_PACK, _bits, _check, _vmax  # noqa: E402
 
 
 RELF_DIRECT = 4e-2  # kernel vs exact-P attention on the same operands: e4m3 rounding of P (2.0-2.4e-2) + the linear mantissa
@@ -127,6 +127,9 @@ def test_i8_quantizer_segmented_layout_and_slot_groups_write_the_same_bytes(T):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("block_rows", [128, 256])
 def test_i8_dense_ragged_vs_emulator(dtype, block_rows):
+    """(the rows past q_valid are zero BITS: v is Gaussian, so about half of the accumulators there are negative, and an
+    epilogue that multiplies them by 0 instead of selecting on the position writes -0 in those rows.  q reaches this
+    kernel's accumulators through a clamped integer conversion, so this check, not a NaN in q, is its test of the select)"""
     from vorta_amd import ops
     rng = np.random.default_rng(1)
     H, Sq, Skv = 3, 333, 417
@@ -150,7 +153,7 @@ def test_i8_dense_ragged_vs_emulator(dtype, block_rows):
                           wave_operands=hooks[h])
     _check(out, ref, dtype, amb, _vmax(ve, vde))
     assert rel_fro(out.float().cpu().numpy(), exact) <= RELF_DIRECT
-    assert torch.all(out[:, q_valid:] == 0)
+    assert not _bits(out[:, q_valid:]).any()
     # and against exact attention on the 16-bit inputs: what int8 scores + e4m3 P, V cost together
     full = np.stack([O.dense_attention(qd[h, :Sq].double().cpu().numpy(), kd[h].double().cpu().numpy(),
                                        vdev[h].double().cpu().numpy(), kv_valid=n_kv, q_valid=q_valid) for h in range(H)])
@@ -302,7 +305,7 @@ def test_i8_routed_attention_vs_oracle(model, fused):
     print("i8pv routed vs the fp64 oracle on the 16-bit inputs, rel. Frobenius per head:", [round(x, 4) for x in rfs])
     assert max(rfs) < 0.06, rfs
     if T:
-        assert torch.all(out[0, :, S + te:] == 0)
+        assert not _bits(out[0, :, S + te:]).any()
 
 
 # the targets of VERDICT r03 item 2 (dB over max|x| of the bf16 result), not the measured values
@@ -465,7 +468,7 @@ def test_routed_attention_random_configs_8bit(seed):
         o = out.float()
         assert torch.isfinite(o).all(), (p, desc)
         if T:
-            assert (o[0, :, Sv + te:] == 0).all(), (p, desc)
+            assert not _bits(out[0, :, Sv + te:]).any(), (p, desc)
         for h in range(H):
             rel = float((o[0, h] - ref[0, h]).norm() / ref[0, h].norm().clamp_min(1e-6))
             assert rel <= 0.15, (p, h, rel, desc)

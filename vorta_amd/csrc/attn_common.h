@@ -1,6 +1,12 @@
 // Shared pieces of the gather flash-attention kernel families (attn_fwd.hip: 16 bits; attn_fwd_fp8.hip: all e4m3;
 // attn_fwd_mx.hip: 16-bit scores, e4m3 P V; attn_fwd_i8.hip: int8 scores, e4m3 P V): the launch parameters, the fused-grid
-// block, the split-key merge and the host launch path.  Only the loop bodies are a family's own.
+// block, the split-key merge, the host launch path, and the two ends of a kernel body -- decode_work (logical workgroup ->
+// what it works on) and write_rows (the epilogue).
+// ONLY attn_i8_body calls the two ends so far.  The other four bodies (attn_fwd_kernel, attn_pipe_dma_body, attn8_body,
+// attn_mx_body) still carry their own copies of both, so a change to the decode or the epilogue has to be made in FIVE places:
+// here and in each of them.  All four were built on these functions and put back: attn_fwd_kernel and attn8_body parked more
+// SGPRs in VGPR lanes than before (attn8 also inside its key loop), attn_pipe_dma_body measured 0.4 % slower on the fused
+// layer kernel, attn_mx_body spilled VGPRs (profiles/attn_fwd_shared_pieces_resources.txt, _timing.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +71,43 @@ __device__ __forceinline__ int live_order(const Params& p, int b, int n, bool re
   if (!remap || b >= n) return b;
   const int xcd = b & 7, qd = n >> 3, r = n & 7;
   return (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (b >> 3);
+}
+
+// What logical workgroup wg of a launch works on: split sp of the key blocks [blk0, blk1) of head slot y (tensor head
+// `head`), for the query positions [p0, pend) of group grp (its key list); n_kv and q_valid with their device-resident
+// values applied (no host sync)
+struct Work {
+  int sp, y, head, grp, p0, pend, n_kv, q_valid, blk0, blk1;
+};
+
+// Fills w for a workgroup of QB query rows.  False: a dead head slot (y >= *n_heads_dev, see live_order) -- the body returns.
+template <int QB>
+__device__ __forceinline__ bool decode_work(const Params& p, int wg, Work& w) {
+  w.sp = wg % p.n_splits;
+  const int rest = wg / p.n_splits;
+  const int n_qb = p.n_groups * p.blocks_per_group;
+  w.y = rest / n_qb;
+  if (p.n_heads_dev && w.y >= *p.n_heads_dev) return false;
+  // (UNI: what this workgroup reads from device memory through a workgroup-uniform address stays in scalar registers.  The
+  // compiler proves that by itself only in a kernel that writes no memory in front of the load; the fused kernel's ticket
+  // draw does, and without this the query block's bounds became vector values that lived across the loops: 2 spilled VGPRs)
+#define UNI(x_) __builtin_amdgcn_readfirstlane(x_)
+  w.head = p.head_list ? UNI(p.head_list[w.y]) : w.y;
+  q_block_of(p, rest % n_qb, QB, w.grp, w.p0, w.pend);
+  w.grp = UNI(w.grp); w.p0 = UNI(w.p0); w.pend = UNI(w.pend);
+  w.n_kv = p.n_kv_dev ? max(1, min(UNI(*p.n_kv_dev), p.n_kv)) : p.n_kv;
+  w.q_valid = p.q_valid_dev ? min(UNI(*p.q_valid_dev), p.q_valid) : p.q_valid;
+#undef UNI
+  w.blk0 = w.sp * p.blocks_per_split;
+  w.blk1 = min(w.blk0 + p.blocks_per_split, (w.n_kv + KVB - 1) / KVB);
+  return true;
+}
+
+// Tensor row of query position pos of w (a position past the end of the query block repeats the block's last row)
+__device__ __forceinline__ int64_t q_row_of(const Params& p, const Work& w, int pos) {
+  pos = min(pos, w.pend - 1);
+  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)w.y * p.q_rows_sh : nullptr;
+  return q_rows ? (int64_t)q_rows[pos] : (int64_t)(p.q_row_offset + pos);
 }
 
 #ifndef VORTA_MAX_SEGMENTS
@@ -158,6 +201,13 @@ __device__ __forceinline__ int draw_ticket(const MultiOf<PP>& mp, int32_t* cnt, 
 __device__ __forceinline__ float2 out_descale(const Params&, int, int) { return make_float2(1.f, 1.f); }
 template <class PP> __device__ __forceinline__ float2 out_descale(const PP& pp, int head, int lane) {
   return *(const float2*)(pp.v_descale + (int64_t)head * pp.v_descale_sh + lane * 2);
+}
+// The same for a single-pass epilogue, folded into the row's 1/l: what multiplies the accumulators of the four channels
+// from ch on (16 bits: inv alone -- no load, no multiply by 1)
+__device__ __forceinline__ f32x4 out_descale4(const Params&, int, int, float inv) { return f32x4{inv, inv, inv, inv}; }
+template <class PP> __device__ __forceinline__ f32x4 out_descale4(const PP& pp, int head, int ch, float inv) {
+  const f32x4 s = *(const f32x4*)(pp.v_descale + (int64_t)head * pp.v_descale_sh + ch);
+  return f32x4{inv * s[0], inv * s[1], inv * s[2], inv * s[3]};
 }
 
 // Merge the split-key partials: one wave per (head slot, query position).  The partials are unnormalised (in the e4m3-P
@@ -375,6 +425,79 @@ __device__ __forceinline__ float half_max(float x) {
 __device__ __forceinline__ float half_sum(float x) {
   auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// The end of every forward body, for an active wave (first position wrow0): o = its unnormalised O^T accumulators (channel
+// 32 dt + 8 (i / 4) + 4 hh + (i & 3) of the lane's row in o[dt][i]), m_ref = the row's reference point in the exp2 domain,
+// l_tot = its row sum.  With key splits the partials go to ws_o / ws_ml for attn_combine_kernel; else the rows are
+// normalised, converted to T and stored.
+template <typename T, class PP>
+__device__ __forceinline__ void write_rows(const PP& pp, const Work& w, int wrow0, const f32x16 (&o)[4], float m_ref, float l_tot) {
+  const Params& p = base_of(pp);
+  // The row bookkeeping (hh, pos and row: the body's hh, its lane's position and q_row_of) is derived again from the thread id,
+  // opaque to the compiler, so that it is not the prologue's values kept in registers across both loops.  The 0 VGPR
+  // spills / 0 scratch of vorta_amd.build.kernel_resources depend on it: with the prologue's values used here the
+  // allocator spills them in front of the loops -- attn_fwd_multi_kernel 8 VGPRs (28 B of scratch), attn_fwd_pipe_kernel
+  // <T, 8, true> 5 (24 B), <T, 8, false> 1 (8 B) -- and tests/test_build_resources.py fails.
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int hh = (tid >> 5) & 1;
+  const int pos = wrow0 + (tid & 31);
+  const bool ok = pos < w.pend;
+  const int64_t row = q_row_of(p, w, pos);
+  if (p.n_splits > 1) {
+    // unnormalised partials (in the e4m3-P families both carry the 2^p_bias factor): ws_o[y][sp][pos][d], ws_ml[y][sp][pos][2]
+    if (ok) {
+      const int64_t slot = ((int64_t)w.y * p.n_splits + w.sp) * p.n_q + pos;
+      float* wo = p.ws_o + slot * D;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          f32x4 v = {o[dt][4 * rg], o[dt][4 * rg + 1], o[dt][4 * rg + 2], o[dt][4 * rg + 3]};
+          *(f32x4*)(wo + 32 * dt + 8 * rg + 4 * hh) = v;
+        }
+      if (hh == 0) {
+        p.ws_ml[slot * 2] = m_ref;
+        p.ws_ml[slot * 2 + 1] = l_tot;
+      }
+    }
+    return;
+  }
+  if (!ok) return;
+  // a position past q_valid is written as zero bits whatever its accumulators hold (0 x NaN is NaN, 0 x a negative sum
+  // is -0): a select on the position alone, applied to the converted values.  A position below q_valid keeps its
+  // arithmetic: a NaN row sum still gives a NaN row
+  const bool past = pos >= w.q_valid;
+  const float inv = (!past && l_tot > 0.f) ? 1.f / l_tot : 0.f;
+  uint2 packed[16];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+      const f32x4 s = out_descale4(pp, w.head, 32 * dt + 8 * rg + 4 * hh, inv);
+      typename MF<T>::v4 t;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = (T)(o[dt][4 * rg + j] * s[j]);
+      packed[dt * 4 + rg] = past ? make_uint2(0u, 0u) : *(uint2*)&t;
+    }
+  char* obase = p.o + (int64_t)w.head * p.o_sh + hh * 8;
+  // (a row and its duplicates are stores of the same `packed` values, converted once above.  No barrier as in
+  // attn_combine_kernel pins that here: tried, it changed nothing that a test or the benchmark's outputs could show.
+  // tests/test_hip_attention_fwd_structured.py compares every duplicate row with its source row as bits on each
+  // gather launch, which is what holds the property)
+  auto store_row = [&](int64_t r) {
+    char* op = obase + r * p.o_ss;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) *(uint2*)(op + (32 * dt + 8 * rg) * 2) = packed[dt * 4 + rg];
+  };
+  store_row(row);
+  if (p.dup_rows && pos < p.n_dup_pos) {
+    const int32_t* dr = p.dup_rows + (int64_t)w.y * p.dup_rows_sh + (int64_t)pos * p.n_dup;
+    for (int i = 0; i < p.n_dup; ++i) store_row((int64_t)dr[i]);
+  }
 }
 
 

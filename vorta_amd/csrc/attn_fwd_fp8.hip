@@ -536,7 +536,11 @@ __device__ __forceinline__ void attn8_body(const Params8& pp, char* __restrict__
     return;
   }
   if (!row_ok) return;
-  const float inv = (my_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
+  // (the zero-bits select past q_valid as in write_rows, attn_common.h.  This body keeps its own decode and epilogue: on the
+  // shared pieces its kernels parked 10-23 more SGPRs in VGPR lanes, some read back inside the key loop --
+  // profiles/attn_fwd_shared_pieces_resources.txt)
+  const bool past = my_p >= q_valid;
+  const float inv = (!past && l_tot > 0.f) ? 1.f / l_tot : 0.f;
   const float* vd = pp.v_descale + (int64_t)head * pp.v_descale_sh + 4 * hh;
   uint2 packed[16];
 #pragma unroll
@@ -547,7 +551,7 @@ __device__ __forceinline__ void attn8_body(const Params8& pp, char* __restrict__
       O4 t;
 #pragma unroll
       for (int j = 0; j < 4; ++j) t[j] = (TO)(o[dt][4 * rg + j] * (inv * s[j]));
-      packed[dt * 4 + rg] = *(uint2*)&t;
+      packed[dt * 4 + rg] = past ? make_uint2(0u, 0u) : *(uint2*)&t;
     }
   char* obase = p.o + (int64_t)head * p.o_sh + hh * 8;
   auto store_row = [&](int64_t row) {

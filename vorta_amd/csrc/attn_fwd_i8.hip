@@ -118,18 +118,11 @@ __device__ __forceinline__ void attn_i8_body(const ParamsI8& pp, char* __restric
   constexpr int BBASE = (K_SLOTS_I8 + V_SLOTS_I8) * TILE8;
   constexpr int SEEDBASE = BBASE + B_SLOTS_I8 * SC_BYTES;
   using V8 = typename MF<T>::v8;
-  using V4 = typename MF<T>::v4;
   constexpr int QB = NW * 32;
   constexpr int CH = 8 / NW;  // 1-KiB DMA pieces (8 tile rows of 128 bytes) of one tile per wave
-  const int sp = wg % p.n_splits;
-  const int rest = wg / p.n_splits;
-  const int n_qb = p.n_groups * p.blocks_per_group;
-  const int qb = rest % n_qb;
-  const int y = rest / n_qb;
-  if (p.n_heads_dev && y >= *p.n_heads_dev) return;
-  const int head = p.head_list ? p.head_list[y] : y;
-  int grp, p0, pend;
-  q_block_of(p, qb, QB, grp, p0, pend);
+  Work w;
+  if (!decode_work<QB>(p, wg, w)) return;
+  const int y = w.y, head = w.head, grp = w.grp, n_kv = w.n_kv, blk0 = w.blk0, blk1 = w.blk1;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -137,21 +130,10 @@ __device__ __forceinline__ void attn_i8_body(const ParamsI8& pp, char* __restric
   const int r32 = lane & 31;
   const int hh = lane >> 5;
 
-  // ---- key block range of this split (n_kv / q_valid may live on the device: no host sync) ----
-  const int n_kv = p.n_kv_dev ? max(1, min(*p.n_kv_dev, p.n_kv)) : p.n_kv;
-  const int q_valid = p.q_valid_dev ? min(*p.q_valid_dev, p.q_valid) : p.q_valid;
-  const int nblk_total = (n_kv + KVB - 1) / KVB;
-  const int blk0 = sp * p.blocks_per_split;
-  const int blk1 = min(blk0 + p.blocks_per_split, nblk_total);
-
   // ---- query rows ----
-  const int wrow0 = p0 + wave * 32;
-  const bool wave_active = wrow0 < pend;  // wave-uniform
-  const int my_p = wrow0 + r32;
-  const bool row_ok = my_p < pend;
-  const int ld_p = min(my_p, pend - 1);
-  const int32_t* q_rows = p.q_rows ? p.q_rows + (int64_t)y * p.q_rows_sh : nullptr;
-  const int64_t my_row = q_rows ? (int64_t)q_rows[ld_p] : (int64_t)(p.q_row_offset + ld_p);
+  const int wrow0 = w.p0 + wave * 32;
+  const bool wave_active = wrow0 < w.pend;  // wave-uniform
+  const int64_t my_row = q_row_of(p, w, wrow0 + r32);
 
   // Q -> int8 here: qt = (q - cq) s with the head's q_prep, the abs-max over the WAVE's 32 rows (rows past the end of the
   // group repeat its last row: they change nothing), q8 = rint(qt 127 / amax).  B operand of v_mfma_i32_32x32x32_i8, k-step
@@ -788,54 +770,7 @@ __device__ __forceinline__ void attn_i8_body(const ParamsI8& pp, char* __restric
 #undef DMA_V
 
   if (!wave_active) return;
-  // ---------------- epilogue ----------------
-  const float l_tot = l_run;
-  if (p.n_splits > 1) {
-    // unnormalised partials: ws_o[y][sp][pos][d], ws_ml[y][sp][pos][2]
-    if (row_ok) {
-      const int64_t slot = ((int64_t)y * p.n_splits + sp) * p.n_q + my_p;
-      float* wo = p.ws_o + slot * D;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          f32x4 v = {o[dt][4 * rg], o[dt][4 * rg + 1], o[dt][4 * rg + 2], o[dt][4 * rg + 3]};
-          *(f32x4*)(wo + 32 * dt + 8 * rg + 4 * hh) = v;
-        }
-      if (hh == 0) {
-        p.ws_ml[slot * 2] = 0.125f * m_run8;  // the reference point in the exp2 domain
-        p.ws_ml[slot * 2 + 1] = l_tot;
-      }
-    }
-    return;
-  }
-  if (!row_ok) return;
-  const float inv = (my_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
-  const float* vd = pp.v_descale + (int64_t)head * pp.v_descale_sh + 4 * hh;
-  uint2 packed[16];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const f32x4 s = *(const f32x4*)(vd + 32 * dt + 8 * rg);
-      V4 t;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t[j] = (T)(o[dt][4 * rg + j] * (inv * s[j]));
-      packed[dt * 4 + rg] = *(uint2*)&t;
-    }
-  char* obase = p.o + (int64_t)head * p.o_sh + hh * 8;
-  auto store_row = [&](int64_t row) {
-    char* op = obase + row * p.o_ss;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) *(uint2*)(op + (32 * dt + 8 * rg) * 2) = packed[dt * 4 + rg];
-  };
-  store_row(my_row);
-  if (p.dup_rows && my_p < p.n_dup_pos) {
-    const int32_t* dr = p.dup_rows + (int64_t)y * p.dup_rows_sh + (int64_t)my_p * p.n_dup;
-    for (int i = 0; i < p.n_dup; ++i) store_row((int64_t)dr[i]);
-  }
+  write_rows<T>(pp, w, wrow0, o, 0.125f * m_run8, l_run);  // (the reference point in the exp2 domain)
 }
 
 template <typename T, int NW, bool KVTAB>

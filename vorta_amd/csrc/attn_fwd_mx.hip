@@ -60,7 +60,6 @@ __device__ __forceinline__ void attn_mx_body(const ParamsMx& pp, char* __restric
   constexpr int NT = NW * 64;
   constexpr int QB = NW * 32;
   constexpr int CH = (KVB * 16) / NT;  // 16-byte chunks of one tile per thread (2 or 4)
-  constexpr int ROWSTEP = NT / 16;     // rows between a thread's consecutive chunks
 #ifndef VORTA_MX_KPRE
 #define VORTA_MX_KPRE 1
 #endif
@@ -117,10 +116,6 @@ __device__ __forceinline__ void attn_mx_body(const ParamsMx& pp, char* __restric
   // ---- loader setup ----
   const int32_t* kv_rows =
       p.kv_rows ? p.kv_rows + (int64_t)y * p.kv_rows_sh + (int64_t)grp * p.kv_rows_sg : nullptr;
-  const char* kbase = p.k + (int64_t)head * p.k_sh + (tid & 15) * 16;
-  const char* vbase = p.v + (int64_t)head * p.v_sh + (tid & 15) * 16;
-  const int lrow0 = tid >> 4;
-  const int lcc = tid & 15;
   // K / V tiles go global -> LDS directly (buffer_load ... lds): no staging registers, no ds_write.  One wave
   // instruction fills 1 KiB = 4 tile rows (16 lanes x 16 B per row); the destination is lane-linear, so the
   // bank swizzles of the tile images are applied on the SOURCE side: the lane that lands in chunk c' of row r
@@ -505,7 +500,11 @@ __device__ __forceinline__ void attn_mx_body(const ParamsMx& pp, char* __restric
     return;
   }
   if (!row_ok) return;
-  const float inv = (my_p < q_valid && l_tot > 0.f) ? 1.f / l_tot : 0.f;
+  // (this body keeps its own decode and epilogue, a copy of decode_work and write_rows (attn_common.h): on those its 128-row
+  // kernel with a key table, which runs at the register budget, spilled 2 VGPRs with reloads inside the key loop --
+  // profiles/attn_fwd_shared_pieces_resources.txt.  The zero-bits select past q_valid is the same as there.)
+  const bool past = my_p >= q_valid;
+  const float inv = (!past && l_tot > 0.f) ? 1.f / l_tot : 0.f;
   const float* vd = pp.v_descale + (int64_t)head * pp.v_descale_sh + 4 * hh;
   uint2 packed[16];
 #pragma unroll
@@ -516,7 +515,7 @@ __device__ __forceinline__ void attn_mx_body(const ParamsMx& pp, char* __restric
       V4 t;
 #pragma unroll
       for (int j = 0; j < 4; ++j) t[j] = (T)(o[dt][4 * rg + j] * (inv * s[j]));
-      packed[dt * 4 + rg] = *(uint2*)&t;
+      packed[dt * 4 + rg] = past ? make_uint2(0u, 0u) : *(uint2*)&t;
     }
   char* obase = p.o + (int64_t)head * p.o_sh + hh * 8;
   auto store_row = [&](int64_t row) {
