@@ -57,7 +57,9 @@ extern "C" {
                                    a binding asks for the symbol and for vorta_gather_sample_rows_args_size())
                                    and the fused 16-bit grid in ticket order, vorta_attn_fwd_batch_tickets /
                                    vorta_attn_ticket_workspace_ints (a pure addition: two more symbols on the existing
-                                   argument block; an older ABI-9 library lacks them, which a binding sees at symbol lookup) */
+                                   argument block; an older ABI-9 library lacks them, which a binding sees at symbol lookup)
+                                   and head routing from measured statistics, vorta_route_fidelity (a pure addition: a binding
+                                   asks for the symbol and for vorta_route_fidelity_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -897,6 +899,61 @@ typedef struct vorta_gather_sample_rows_args {
 
 int vorta_gather_sample_rows(const vorta_gather_sample_rows_args* args, void* hip_stream);
 int vorta_gather_sample_rows_args_size(void);
+
+/*
+ * vorta_route_fidelity (ABI 9, a pure addition: a binding asks for the symbol and for vorta_route_fidelity_args_size();
+ * vorta_sizeof keeps its 17 indices) -- head routing from MEASURED statistics, on the device: from the record of a per-expert
+ * measurement (vorta_expert_fidelity's sq_ref / sq_err, e.g. on sampled rows) to the head -> expert table and the per-expert
+ * head lists + counts, in vorta_route_scores' layout, so the expert launches take them without a host read.  The reference
+ * has no counterpart (its routes come from a trained router).  One launch of one workgroup: launch latency.  No atomics; the
+ * same bits on every run.  The rule is the host function's (vorta.patch.routes_from_fidelity), which is the definition.
+ *
+ * Relative error.  It follows ExpertFidelity.rel_error() exactly, in float32:
+ *   - rel = sqrt(sq_err / sq_ref).
+ *   - The division and the square root are correctly rounded.
+ *   - sq_ref == 0 gives 0 where sq_err == 0, and +inf otherwise.
+ *   - NaN stays NaN.
+ *
+ * Mode 0 (error bound).
+ *   - Of the sparse experts whose rel <= (float)max_rel_error, take the one with the smaller work.
+ *   - On equal work, take expert 2.
+ *   - Where no sparse expert qualifies, take expert 0.
+ *   - NaN meets no bound.
+ *   - The host function compares a float32 tensor with a Python scalar.  That compares in float32, so the bound is a float.
+ *
+ * Mode 1 (FLOP budget).
+ *   - A head's candidate is the sparse expert with the smaller rel.  Only experts with work[e] < work[0] and a finite rel
+ *     count.  On equal rel, take the smaller work, then expert 2.
+ *   - A head with no such expert has no candidate.
+ *   - Heads are ranked by (rel of candidate, head id) ascending.
+ *   - Start with every head on expert 0.
+ *   - Walk the ranking.  While cost > max_flops_share * (heads * work[0]), move the next head to its candidate.
+ *   - cost = n0*work[0] + n1*work[1] + n2*work[2], evaluated in double from the integer counts, left to right (every product
+ *     and sum rounded on its own: no fused multiply-add).  The order of moves then cannot change its bits.
+ *   - Stop when the cost is within the budget or the candidates run out.
+ *   - max_flops_share >= 1 moves nothing.
+ *
+ * VORTA_EINVAL for a wrong struct_size; a null sq_ref, sq_err, expert_of_head, head_lists or head_counts; heads outside
+ * 1..1024; a mode other than 0 or 1; in mode 0 a NaN or negative bound, in mode 1 a NaN or non-positive share; a work entry
+ * that is not positive and finite.  Everything is looked at before anything is launched.
+ */
+typedef struct vorta_route_fidelity_args {
+  uint32_t struct_size;      /* = sizeof(vorta_route_fidelity_args) = vorta_route_fidelity_args_size() */
+  int32_t heads;             /* 1..1024 */
+  const float* sq_ref;       /* [heads] */
+  const float* sq_err;       /* [heads][3]; column 0 coreset, column 1 sliding tile (ExpertFidelity's layout); column 2 is not read */
+  int32_t mode;              /* 0 = error bound, 1 = FLOP budget */
+  float max_rel_error;       /* mode 0: >= 0 */
+  double work[3];            /* FLOPs of one head under expert 0 / 1 / 2 (patch.fidelity.expert_work); all > 0 */
+  double max_flops_share;    /* mode 1: > 0 */
+  int32_t* expert_of_head;   /* [heads] */
+  int32_t* head_lists;       /* [3][heads], ascending head ids; entries at or past the count are not written */
+  int32_t* head_counts;      /* [3] */
+  float* flops_share;        /* optional, 1 float: (n0 w0 + n1 w1 + n2 w2) / (heads w0), in double, rounded once */
+} vorta_route_fidelity_args;
+
+int vorta_route_fidelity(const vorta_route_fidelity_args* args, void* hip_stream);
+int vorta_route_fidelity_args_size(void);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.

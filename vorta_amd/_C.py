@@ -196,6 +196,14 @@ class GatherSampleRowsArgs(C.Structure):
     ]
 
 
+class RouteFidelityArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("heads", _i32), ("sq_ref", _vp), ("sq_err", _vp), ("mode", _i32), ("max_rel_error", C.c_float),
+        ("work", C.c_double * 3), ("max_flops_share", C.c_double), ("expert_of_head", _vp), ("head_lists", _vp),
+        ("head_counts", _vp), ("flops_share", _vp),
+    ]
+
+
 MIX_BWD_PARTS = 64  # include/vorta_hip.h VORTA_MIX_BWD_PARTS
 NORM_ROPE_BWD_PARTS = 1024  # include/vorta_hip.h VORTA_NORM_ROPE_BWD_PARTS
 FIDELITY_PARTS, FIDELITY_WS_FLOATS = 64, 12  # include/vorta_hip.h VORTA_FIDELITY_PARTS, VORTA_FIDELITY_WS_FLOATS
@@ -262,6 +270,8 @@ SYMBOLS = {
     "vorta_sampled_fidelity_args_size": (C.c_int, []),
     "vorta_gather_sample_rows": (C.c_int, [C.POINTER(GatherSampleRowsArgs), _vp]),
     "vorta_gather_sample_rows_args_size": (C.c_int, []),
+    "vorta_route_fidelity": (C.c_int, [C.POINTER(RouteFidelityArgs), _vp]),
+    "vorta_route_fidelity_args_size": (C.c_int, []),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "vorta_permute_heads": (C.c_int, [C.POINTER(PermuteArgs), _vp]),
     "vorta_abi_version": (C.c_int, []),
@@ -300,7 +310,7 @@ def lib():
             fn = getattr(h, name)
         except AttributeError:
             # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity, the
-            # partial-geometry entry points, vorta_sampled_fidelity, vorta_gather_sample_rows and the ticket-order fused grid without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # partial-geometry entry points, vorta_sampled_fidelity, vorta_gather_sample_rows, the ticket-order fused grid and vorta_route_fidelity without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
@@ -326,6 +336,9 @@ def lib():
     if h.vorta_gather_sample_rows_args_size() != C.sizeof(GatherSampleRowsArgs):
         raise VortaHipError(f"struct layout mismatch for GatherSampleRowsArgs: C {h.vorta_gather_sample_rows_args_size()} "
                             f"vs ctypes {C.sizeof(GatherSampleRowsArgs)}")
+    if h.vorta_route_fidelity_args_size() != C.sizeof(RouteFidelityArgs):
+        raise VortaHipError(f"struct layout mismatch for RouteFidelityArgs: C {h.vorta_route_fidelity_args_size()} "
+                            f"vs ctypes {C.sizeof(RouteFidelityArgs)}")
     _lib = h
     return h
 

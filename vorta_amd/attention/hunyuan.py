@@ -330,7 +330,7 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                  latent_shape: Tuple[int, int, int] = (30, 48, 80),
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
                  fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
-                 expert_fidelity: Optional[list] = None):
+                 expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None):
         """Keyword names as hunyuan.py:521-539.  `head_routing` / `experts_host` are this build's additions: the
         routes of this layer already dispatched by the step's route plan (vorta_amd/patch/_engine.py), on the device /
         on the host; without them the dispatch runs here from `routing_score`.
@@ -339,7 +339,11 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
         heads this rank holds, filed under their global ids: attention/_sp.py); None: the launches of today.
         expert_fidelity: a list that receives this call's `ops.ExpertFidelity` on the same `fidelity_rows` -- what every expert
         would have written for every head, and the routed rows (routed.sampled_expert_fidelity); refused by name under sequence
-        parallelism."""
+        parallelism.
+        route_rule: a `routed.RouteRule`: the call is routed by its OWN measurement (routed.route_by_fidelity on the projected
+        q, k, v: a stated error bound or FLOP budget, on the device, no host read); `routing_score`, `tau_sparse` and
+        `head_routing` are then not consulted, and `route_sink` (a list) receives (expert_ids, lists, counts, fid).  Refused
+        by name under sequence parallelism."""
         self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
         q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb)
         assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
@@ -348,6 +352,9 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
             if expert_fidelity is not None:
                 raise NotImplementedError("sampled_expert_fidelity: the per-expert measurement on sampled rows does not run "
                                           "under sequence parallelism (its gather reads whole heads of one process)")
+            if route_rule is not None:
+                raise NotImplementedError("route_rule: routing by a measured error bound or FLOP budget does not run under "
+                                          "sequence parallelism (its gather reads whole heads of one process)")
             from ._sp import sp_attention
             buf = sp_attention(q, k, v, T, routing_score, tau_sparse, model="hunyuan", text_valid=te,
                                lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
@@ -355,7 +362,13 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                                fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
             return self._output(attn, buf, T)
         # top-1 / tau dispatch on the device: no torch.nonzero host sync (hunyuan.py:612-640)
-        if head_routing is None:
+        if route_rule is not None:
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            head_routing, ids, fid = route_rule.route(q, k, v, geom, model="hunyuan", text_len=T, text_valid=te)
+            if route_sink is not None:
+                route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
+        elif head_routing is None:
             _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
             head_routing = HeadRouting.from_device(lists, counts)
         buf, out = self._new_out(q)

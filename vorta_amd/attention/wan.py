@@ -216,12 +216,14 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
                  latent_shape: Tuple[int, int, int] = (20, 30, 52), use_original_attn: bool = False,
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
                  fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
-                 expert_fidelity: Optional[list] = None):
+                 expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None):
         """Keyword names as wan.py:308-328; `head_routing` / `experts_host`: see the Hunyuan processor.
         fidelity: a list that receives one `ops.SampledFidelity` PER BATCH ITEM of this call, in item order (the routed output
         as run against dense attention on sampled rows, routed.routed_attention); cross attention and the dense teacher file
         nothing; None: the launches of today.  expert_fidelity: likewise one `ops.ExpertFidelity` per batch item
-        (routed.sampled_expert_fidelity on the same `fidelity_rows`); refused by name under sequence parallelism."""
+        (routed.sampled_expert_fidelity on the same `fidelity_rows`); refused by name under sequence parallelism.
+        route_rule / route_sink: see the Hunyuan processor; a batch is routed, every item, by ITEM 0's measurement (the
+        reference's convention for scores, quoted below), so the sink receives one entry per call."""
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
@@ -235,13 +237,22 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
             if expert_fidelity is not None:
                 raise NotImplementedError("sampled_expert_fidelity: the per-expert measurement on sampled rows does not run "
                                           "under sequence parallelism (its gather reads whole heads of one process)")
+            if route_rule is not None:
+                raise NotImplementedError("route_rule: routing by a measured error bound or FLOP budget does not run under "
+                                          "sequence parallelism (its gather reads whole heads of one process)")
             from ._sp import sp_attention
             bufs = [sp_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], 0, routing_score, tau_sparse, model="wan",
                                  lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
                                  latent_shape=latent_shape, experts_host=experts_host, fidelity=fidelity,
                                  fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads) for b in range(B)]
             return self._output_proj(attn, bufs[0] if B == 1 else torch.cat(bufs, dim=0))
-        if head_routing is None:
+        if route_rule is not None:
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            head_routing, ids, fid = route_rule.route(q[:1], k[:1], v[:1], geom, model="wan")
+            if route_sink is not None:
+                route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
+        elif head_routing is None:
             _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
             head_routing = HeadRouting.from_device(lists, counts)
         buf, out = self._new_out(q)

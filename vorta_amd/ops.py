@@ -1173,6 +1173,47 @@ def expert_fidelity(bufs, mixed: Optional[torch.Tensor] = None) -> ExpertFidelit
     return ExpertFidelity(sq_ref, max_ref, sq_err, max_err, range_ref, N * D)
 
 
+DEFAULT_ROUTE_WORK = (3.0, 2.0, 1.0)  # routes_from_fidelity's order without a geometry: sliding tile cheapest, then coreset
+
+
+def route_fidelity(fid: ExpertFidelity, *, max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
+                   work=None, flops_share: bool = False):
+    """vorta_route_fidelity: the head -> expert table of one layer from its measured statistics `fid` (sq_ref (H,), sq_err
+    (H,3) float32 on the device), by `vorta.patch.routes_from_fidelity`'s rule, without a host read: `max_rel_error` = per head
+    the cheapest sparse expert within the bound, `max_flops_share` = heads moved to their better sparse expert, smallest
+    error first, until the layer costs at most that share of the all-dense layer (exactly one of the two).
+    work: FLOPs of one head under expert 0 / 1 / 2 (`patch.fidelity.expert_work`); None = (3, 2, 1).
+    Returns (expert_of_head (H,), head_lists (3,H), head_counts (3,)) int32 on the device -- `HeadRouting.from_device(lists,
+    counts)` takes them -- and with `flops_share=True` a fourth, one float32: the routed layer's FLOPs over the dense one's."""
+    if (max_rel_error is None) == (max_flops_share is None):
+        raise ValueError("route_fidelity: exactly one of max_rel_error and max_flops_share")
+    sq_ref, sq_err = fid.sq_ref, fid.sq_err
+    _require_gpu(sq_ref, sq_err)
+    if sq_ref.dim() != 1 or tuple(sq_err.shape) != (sq_ref.shape[0], 3) or sq_ref.dtype != torch.float32 \
+            or sq_err.dtype != torch.float32:
+        raise ValueError("route_fidelity: the statistics of ONE layer, sq_ref (H,) and sq_err (H, 3) in float32")
+    sq_ref, sq_err = sq_ref.contiguous(), sq_err.contiguous()
+    H, dev = sq_ref.shape[0], sq_ref.device
+    expert = torch.empty(H, dtype=torch.int32, device=dev)
+    lists = torch.empty((3, H), dtype=torch.int32, device=dev)  # (entries at or past a count are not written, and not read)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    share = torch.empty(1, dtype=torch.float32, device=dev) if flops_share else None
+    a = _C.RouteFidelityArgs()
+    a.struct_size = C.sizeof(_C.RouteFidelityArgs)
+    a.heads = H
+    a.sq_ref, a.sq_err = sq_ref.data_ptr(), sq_err.data_ptr()
+    a.mode = 0 if max_flops_share is None else 1
+    a.max_rel_error = 0.0 if max_rel_error is None else float(max_rel_error)
+    a.max_flops_share = 0.0 if max_flops_share is None else float(max_flops_share)
+    for e, w in enumerate(DEFAULT_ROUTE_WORK if work is None else work):
+        a.work[e] = float(w)
+    a.expert_of_head, a.head_lists, a.head_counts = expert.data_ptr(), lists.data_ptr(), counts.data_ptr()
+    if share is not None:
+        a.flops_share = share.data_ptr()
+    _C.check(_C.lib().vorta_route_fidelity(C.byref(a), _stream()), "vorta_route_fidelity")
+    return (expert, lists, counts) + ((share,) if flops_share else ())
+
+
 class SampledFidelity(NamedTuple):
     """vorta_sampled_fidelity's statistics: per head how far the rows a ROUTED call wrote are from dense attention in the input
     dtype, on a sample of `rows.numel()` query rows.  Float32 tensors with any leading dimensions (a layer axis,

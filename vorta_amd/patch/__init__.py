@@ -14,10 +14,13 @@ gradients, summed).  For judging a router or a `tau_sparse`:
 full attention) and the host helpers `routes_from_fidelity` / `evaluate_routing` (patch/fidelity.py); at inference,
 `routed_fidelity(model)` / `routed_fidelity_of(model)`: the routed output as run against dense attention on sampled rows;
 `sampled_expert_fidelity(model)` / `sampled_expert_fidelity_of(model)`: what EVERY expert would have written on those rows (an
-`ExpertFidelity` without the soft mixture's forward), and `fixed_routes(model, table)`: run the model by an expert table."""
+`ExpertFidelity` without the soft mixture's forward), and `fixed_routes(model, table)`: run the model by an expert table;
+`measured_routes(model, max_rel_error=... | max_flops_share=...)` / `measured_routes_of(model)`: route every layer of every
+forward by its own measurement on the device -- a stated error bound or FLOP budget, no router checkpoint, no host read."""
 from ._engine import all_reduce_router_grads, original_attention, routing_scores_of, token_sharded
-from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, routed_fidelity,
-                       routed_fidelity_of, routes_from_fidelity, sampled_expert_fidelity, sampled_expert_fidelity_of)
+from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, measured_routes,
+                       measured_routes_of, routed_fidelity, routed_fidelity_of, routes_from_fidelity, sampled_expert_fidelity,
+                       sampled_expert_fidelity_of)
 from .router import Router, load_router_checkpoint
 from .utils import (Pixel2TokenFactory, hunyuan_pixel2token, prepare_hunyuan_self_attn_kwargs,
                     prepare_wan_self_attn_kwargs, wan_pixel2token)

@@ -148,6 +148,10 @@ class ForwardState:
     # inside `fixed_routes(model, table)`: the (L, H) expert table this forward launches, and its per-layer HeadRouting
     fixed_routes: Optional[List[List[int]]] = None
     fixed_routing: Dict[int, HeadRouting] = field(default_factory=dict)
+    # inside `measured_routes(model, ...)`: the context's state (patch/fidelity.py MeasuredRoutes) and whether THIS forward
+    # measures (forwards 0, k, 2k, ... of the context) or launches the lists the latest measuring forward stored
+    measured_routes: Any = None
+    measures_routes: bool = False
     token_shard: bool = False                    # sequence parallel: this forward got the WHOLE latent and cuts its tokens itself
 
 
@@ -247,6 +251,8 @@ class StepContext:
     measure_experts: Optional[Tuple[int, int]] = None  # inside `sampled_expert_fidelity(model)`: (n_rows, seed)
     sampled_experts: Optional[Dict[int, Any]] = None  # the latest such forward's records (`sampled_expert_fidelity_of`)
     fixed_routes: Optional[List[List[int]]] = None  # inside `fixed_routes(model, table)`: the (L, H) expert table
+    measured_routes: Any = None  # inside `measured_routes(model, ...)`: its MeasuredRoutes (rule, forward count, stored lists)
+    latest_measured_routes: Any = None  # that of the latest context left (what `measured_routes_of` reads outside one)
 
     def state_for(self, rotary) -> Optional[ForwardState]:
         """the state of the forward a processor call belongs to: the running forward's (in grad mode filed under `rotary`
@@ -345,8 +351,24 @@ class BoundProcessor:
                                                                                   hidden_states.device)
                 kw["head_routing"] = state.fixed_routing[self.layer]
                 kw.setdefault("tau_sparse", 0.0)
+            rsink = None
+            if state.measured_routes is not None:
+                # under `measured_routes(model, ...)`: a measuring forward routes this layer by its own measurement and
+                # stores the device lists; the forwards between two measurements launch the stored lists, nothing more.  The
+                # plan's routes and `tau_sparse` are not consulted
+                if "route_rule" not in self._accepted:
+                    raise ValueError("measured_routes: this model's Eval processor takes no `route_rule`")
+                kw.setdefault("tau_sparse", 0.0)
+                if state.measures_routes:
+                    rsink = []
+                    kw["route_rule"], kw["route_sink"] = state.measured_routes.rule, rsink
+                else:
+                    kw["head_routing"] = state.measured_routes.stored_routing(self.layer)  # (raises where there is none)
             if state.routed_fidelity is None and state.sampled_experts is None:
-                return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+                out = self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
+                if rsink:  # (a cross-attention call measures nothing)
+                    state.measured_routes.file(self.layer, rsink)
+                return out
             # under `routed_fidelity(model)` / `sampled_expert_fidelity(model)`: the sample is fixed per (S, n, seed) -- one
             # cached table, no host work per layer; the two share it
             from ..routed import sample_rows
@@ -368,6 +390,8 @@ class BoundProcessor:
                 state.routed_fidelity[self.layer] = sink
             if esink:
                 state.sampled_experts[self.layer] = esink
+            if rsink:
+                state.measured_routes.file(self.layer, rsink)
             return out
         if state.fidelity is None or "fidelity" not in self._accepted:
             return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
@@ -428,7 +452,9 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
                              f"latent frame count, which is {int(sak['latent_shape'][0])} (latent_shape "
                              f"{tuple(sak['latent_shape'])}): hand every rank the whole latent inside "
                              "`token_sharded(model)`, or run the pipeline call, which shards tokens")
-        ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher,
+        measured = None if ctx.teacher else ctx.measured_routes
+        measures = measured is not None and measured.begin_forward()  # (the context counts its non-teacher forwards)
+        ctx.current = ForwardState(kwargs=sak, teacher=ctx.teacher, measured_routes=measured, measures_routes=measures,
                                    fidelity={} if ctx.measure_fidelity and not ctx.teacher else None,
                                    routed_fidelity={} if ctx.measure_routed is not None and not ctx.teacher else None,
                                    measure_routed=ctx.measure_routed,
@@ -489,7 +515,7 @@ def install_timestep_capture(embedder: nn.Module, model: nn.Module, ctx: StepCon
             return None
         tau = state.kwargs.get("tau_sparse")
         if tau is None:
-            if ctx.needs_tau and state.fixed_routes is None:
+            if ctx.needs_tau and state.fixed_routes is None and state.measured_routes is None:
                 raise ValueError("self_attention_kwargs has no `tau_sparse` "
                                  "(prepare_*_self_attn_kwargs(..., tau_sparse=...))")
             tau = 0.0  # soft-mixture processors use the scores only; the dispatch lists go unused

@@ -34,10 +34,18 @@ What an inference forward COULD have written -- every expert of every head, on t
     with fixed_routes(model, table), routed_fidelity(model, heads="all"):
         model(hidden_states, ..., self_attention_kwargs=kw)            # launched by the table; routers and tau_sparse unread
     routed_fidelity_of(model).expert                  # == table
+
+The same loop closed on the device -- every layer of every forward routed by its own measurement, by a stated rule:
+
+    with measured_routes(model, max_rel_error=0.05, n_rows=512):       # or max_flops_share=0.4; no router, no tau_sparse, no host read
+        model(hidden_states, ..., self_attention_kwargs=kw)            # routed.route_by_fidelity per layer (vorta_route_fidelity)
+    experts, fid = measured_routes_of(model)          # (L, H) device table and the ExpertFidelity it came from
 """
 from __future__ import annotations
 
 import contextlib
+import math
+from dataclasses import dataclass, field
 from typing import Any, Dict, Mapping, Optional, Tuple, Union
 
 import torch
@@ -113,6 +121,10 @@ def routed_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0, heads: 
     if ctx.measure_experts is not None and ctx.measure_experts != (int(n_rows), int(seed)):
         raise ValueError(f"routed_fidelity(n_rows={n_rows}, seed={seed}) inside sampled_expert_fidelity(n_rows="
                          f"{ctx.measure_experts[0]}, seed={ctx.measure_experts[1]}): the two share one sample")
+    rule = None if ctx.measured_routes is None else ctx.measured_routes.rule
+    if rule is not None and (rule.n_rows, rule.seed) != (int(n_rows), int(seed)):
+        raise ValueError(f"routed_fidelity(n_rows={n_rows}, seed={seed}) inside measured_routes(n_rows={rule.n_rows}, "
+                         f"seed={rule.seed}): the two share one sample")
     previous, ctx.measure_routed = ctx.measure_routed, (int(n_rows), int(seed), heads)
     try:
         yield model
@@ -167,6 +179,9 @@ def sampled_expert_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0)
     if ctx.measure_routed is not None and ctx.measure_routed[:2] != (int(n_rows), int(seed)):
         raise ValueError(f"sampled_expert_fidelity(n_rows={n_rows}, seed={seed}) inside routed_fidelity(n_rows="
                          f"{ctx.measure_routed[0]}, seed={ctx.measure_routed[1]}): the two share one sample")
+    if ctx.measured_routes is not None:
+        raise ValueError("sampled_expert_fidelity inside measured_routes: measured_routes runs that measurement itself "
+                         "(measured_routes_of(model) returns its records)")
     previous, ctx.measure_experts = ctx.measure_experts, (int(n_rows), int(seed))
     try:
         yield model
@@ -205,6 +220,8 @@ def fixed_routes(model: nn.Module, table):
                          f"{tuple(t.shape)} {t.dtype}")
     if bool(((t < 0) | (t > 2)).any()):
         raise ValueError("fixed_routes: expert ids are 0 (full), 1 (coreset), 2 (sliding tile)")
+    if ctx.measured_routes is not None:
+        raise ValueError("fixed_routes inside measured_routes: a forward is routed by the table or by the measurement, not both")
     from ..ulysses import SP_STATE
     if SP_STATE.enabled:
         raise NotImplementedError("fixed_routes: routing by a table does not run under sequence parallelism")
@@ -213,6 +230,105 @@ def fixed_routes(model: nn.Module, table):
         yield model
     finally:
         ctx.fixed_routes = previous
+
+
+@dataclass(eq=False)
+class MeasuredRoutes:
+    """The state of one `measured_routes(model, ...)` context: its rule, its count of the model's non-teacher forwards, and
+    per layer what the latest measuring forward filed -- the processors' sink entries (expert_ids, lists, counts, fid)"""
+    rule: Any                       # routed.RouteRule
+    refresh_every: int = 1
+    forwards: int = 0
+    filed: Dict[int, list] = field(default_factory=dict)
+
+    def begin_forward(self) -> bool:
+        """counts a forward; True where it measures: forwards 0, k, 2k, ... of the context"""
+        measures = self.forwards % self.refresh_every == 0
+        self.forwards += 1
+        return measures
+
+    def file(self, layer: int, entries: list) -> None:
+        self.filed[layer] = entries
+
+    def stored_routing(self, layer: int):
+        """the device lists and counts the latest measuring forward stored for `layer`, as a HeadRouting: nothing is launched"""
+        from ..routed import HeadRouting
+        entries = self.filed.get(layer)
+        if not entries:  # (never with the patch's own forwards: every routed layer of a measuring forward files its lists)
+            raise RuntimeError(f"measured_routes: layer {layer} has no measured routes on record for a forward between two "
+                               "measurements (the latest measuring forward did not run this layer's self-attention)")
+        return HeadRouting.from_device(entries[0][1], entries[0][2])
+
+
+@contextlib.contextmanager
+def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
+                    n_rows: int = 512, seed: int = 0, refresh_every: int = 1):
+    """While active, every non-teacher forward of `model` (patched with apply_vorta_transformer, hard-routing Eval processors)
+    routes each layer by a MEASUREMENT of that layer on its own q, k, v, held per prompt, per layer and per step, without a
+    router checkpoint and without a host read (`routed.route_by_fidelity`: `n_rows` sampled video rows per head,
+    `routed.sample_rows(S, n_rows, seed)`; then vorta_route_fidelity).  Exactly one rule:
+    `max_rel_error=b`: no sparse head is further than b from dense attention on the sampled rows -- per head the cheapest
+    expert within the bound, full attention where none is; `max_flops_share=s`: per layer at most the share s of the all-dense
+    FLOPs, spent where it hurts least (`routes_from_fidelity` defines both).  The bound covers the sampled rows and the METHOD:
+    the measurement runs in the dtype of q, k, v, whatever 8-bit precision the routed launches use.
+    `refresh_every=k`: the context counts the model's non-teacher forwards on the host and measures on forwards 0, k, 2k, ...
+    of the context; between them every layer launches the device lists and counts it stored (`HeadRouting.from_device`),
+    with nothing measured or launched beyond the routed call.  A pipeline that runs two forwards per step (Wan's
+    classifier-free guidance) counts two: with k = 2 the conditional forward measures and the unconditional one launches its
+    routes.  The routers' routes, `tau_sparse` (a forward may leave it out) and `head_routing` are not consulted; teacher
+    forwards stay dense.  Inside `routed_fidelity(model)` with the same (n_rows, seed) -- the two share one sample -- that
+    record's `expert` reports the measured routes.  Outside the context nothing changes.
+    Refused by name: a model that was not patched; both rules or neither; nesting with `fixed_routes`, `sampled_expert_fidelity`
+    or another `measured_routes`, either way round; sequence parallelism (NotImplementedError, as `fixed_routes`)."""
+    from ..routed import ROUTE_RULE_MODES, RouteRule
+    ctx = context_of(model)
+    if ctx.plan is None:
+        raise ValueError("measured_routes: the model was not patched with apply_vorta_transformer")
+    if (max_rel_error is None) == (max_flops_share is None):
+        raise ValueError("measured_routes: exactly one of max_rel_error and max_flops_share")
+    mode = ROUTE_RULE_MODES[0] if max_flops_share is None else ROUTE_RULE_MODES[1]
+    value = float(max_rel_error if max_flops_share is None else max_flops_share)
+    if not (value >= 0 if max_flops_share is None else value > 0):
+        raise ValueError(f"measured_routes: {mode}={value} (a bound >= 0; a share > 0)")
+    if not ctx.needs_tau:
+        raise ValueError("measured_routes: the model was patched with soft-mixture (Train) processors, which run every "
+                         "expert of every head: only the hard-routing (Eval) processors are routed")
+    if int(n_rows) < 1 or int(refresh_every) < 1:
+        raise ValueError(f"measured_routes: n_rows={n_rows}, refresh_every={refresh_every} (both at least 1: without a "
+                         "sampled row every error reads 0 and every head would meet any bound)")
+    if ctx.fixed_routes is not None:
+        raise ValueError("measured_routes inside fixed_routes: a forward is routed by the table or by the measurement, not both")
+    if ctx.measure_experts is not None:
+        raise ValueError("measured_routes inside sampled_expert_fidelity: measured_routes runs that measurement itself "
+                         "(measured_routes_of(model) returns its records)")
+    if ctx.measured_routes is not None:
+        raise ValueError("measured_routes inside measured_routes: one rule routes a forward")
+    if ctx.measure_routed is not None and ctx.measure_routed[:2] != (int(n_rows), int(seed)):
+        raise ValueError(f"measured_routes(n_rows={n_rows}, seed={seed}) inside routed_fidelity(n_rows="
+                         f"{ctx.measure_routed[0]}, seed={ctx.measure_routed[1]}): the two share one sample")
+    from ..ulysses import SP_STATE
+    if SP_STATE.enabled:
+        raise NotImplementedError("measured_routes: routing by a measurement does not run under sequence parallelism")
+    ctx.measured_routes = MeasuredRoutes(RouteRule(mode, value, int(n_rows), int(seed)), int(refresh_every))
+    try:
+        yield model
+    finally:
+        ctx.measured_routes, ctx.latest_measured_routes = None, ctx.measured_routes
+
+
+def measured_routes_of(model: nn.Module, item: int = 0) -> Tuple[torch.Tensor, ExpertFidelity]:
+    """(experts, fid) of the model's latest MEASURING forward under `measured_routes(model, ...)`, stacked over the layers in
+    block order: `experts` the (L, H) int32 head -> expert table on the device (read only when asked: `fixed_routes(model,
+    experts)` reads it), `fid` the `ops.ExpertFidelity` (L, H, ...) the routes came from (column 2 NaN) -- `evaluate_routing`
+    and `routes_from_fidelity` take it unchanged.  `item`: the batch item that was measured; a call measures item 0 alone
+    (Wan routes a batch by it), so 0."""
+    ctx = context_of(model)
+    measured = ctx.measured_routes if ctx.measured_routes is not None else ctx.latest_measured_routes
+    if measured is None or not measured.filed:
+        raise RuntimeError("measured_routes_of: no forward of this model has measured under measured_routes(model, ...) with "
+                           "hard-routing (Eval) processors")
+    entries = [measured.filed[layer][item] for layer in sorted(measured.filed)]
+    return torch.stack([e[0] for e in entries]), stack_fidelity(e[3] for e in entries)
 
 
 Geometry = Union[Mapping[str, Any], Any]
@@ -252,20 +368,72 @@ def _geometry_numbers(geometry: Geometry) -> Tuple[int, int, int, float]:
 
 def expert_work(geometry: Geometry, text_valid: int = 0, head_dim: int = 128) -> Tuple[float, float, float]:
     """FLOPs of one head under expert 0 / 1 / 2 by the work formulas of BASELINE.md section 2:
-    F_full = 4 (S + T_eff)^2 D, F_low = 4 (S_low + T_eff)^2 D, F_sl = 4 D [S (n_kv tok + T_eff) + T_eff (S + T_eff)]"""
+    F_full = 4 (S + T_eff)^2 D, F_low = 4 (S_low + T_eff)^2 D, F_sl = 4 D [S (n_kv tok + T_eff) + T_eff (S + T_eff)].
+    A mapping with `work` names the three figures itself (measured costs, say): they are returned as they are."""
+    if isinstance(geometry, Mapping) and geometry.get("work") is not None:
+        work = tuple(float(x) for x in geometry["work"])
+        if len(work) != 3 or not all(x > 0 and math.isfinite(x) for x in work):
+            raise ValueError("geometry['work']: three positive finite figures (expert 0 / 1 / 2)")
+        return work
     S, s_low, _, keys = _geometry_numbers(geometry)
     te, D = int(text_valid), int(head_dim)
     return (4.0 * (S + te) ** 2 * D, 4.0 * (s_low + te) ** 2 * D, 4.0 * D * (S * (keys + te) + te * (S + te)))
 
 
-def routes_from_fidelity(fid: ExpertFidelity, max_rel_error: float, geometry: Optional[Geometry] = None,
-                         text_valid: int = 0) -> torch.Tensor:
-    """(..., H) int64 expert table (on the CPU): per head the CHEAPEST expert whose `rel_error` is within `max_rel_error`
+def _routes_within_budget(rel: torch.Tensor, work: Tuple[float, float, float], max_flops_share: float) -> torch.Tensor:
+    """`routes_from_fidelity(max_flops_share=...)` on a CPU float32 rel (..., H, 3): plain Python per layer, in doubles"""
+    w0, w1, w2 = (float(x) for x in work)
+    H = rel.shape[-2]
+    flat = rel.reshape(-1, H, rel.shape[-1])
+    table = torch.zeros(flat.shape[:2], dtype=torch.int64)
+    budget = float(max_flops_share) * (H * w0)
+    for layer, rows in enumerate(flat.tolist()):
+        ranking = []  # (rel of the candidate, head, candidate)
+        for h, row in enumerate(rows):
+            # (rel, work, -expert): the smaller rel, then the smaller work, then expert 2
+            cands = [(row[_COLUMN_OF_EXPERT[e]], work[e], -e) for e in (1, 2)
+                     if work[e] < w0 and math.isfinite(row[_COLUMN_OF_EXPERT[e]])]
+            if cands:
+                r, _, neg_e = min(cands)
+                ranking.append((r, h, -neg_e))
+        ranking.sort(key=lambda x: x[:2])
+        n = [H, 0, 0]
+        for _, h, e in ranking:
+            # from the integer counts, left to right: the order of the moves cannot change the bits
+            if not (n[0] * w0 + n[1] * w1 + n[2] * w2 > budget):
+                break
+            n[0] -= 1
+            n[e] += 1
+            table[layer, h] = e
+    return table.reshape(rel.shape[:-1])
+
+
+def routes_from_fidelity(fid: ExpertFidelity, max_rel_error: Optional[float] = None, geometry: Optional[Geometry] = None,
+                         text_valid: int = 0, *, max_flops_share: Optional[float] = None) -> torch.Tensor:
+    """(..., H) int64 expert table (on the CPU) by ONE of two rules (both or neither: ValueError).
+    `max_rel_error`: per head the CHEAPEST expert whose `rel_error` is within `max_rel_error`
     (<=), full attention (0) where no sparse expert meets it.  Cost order: sliding tile, coreset, full -- the order the work
     formulas of BASELINE.md give at every published geometry; with `geometry` the order is computed from them (`expert_work`).
     A tie takes the cheaper expert.  A NaN error meets no bound.  No backward pass, no router: a table to compare a router's
-    routes against, or to route by."""
+    routes against, or to route by.
+    `max_flops_share` (needs `geometry`): spend at most that share of the all-dense layer's FLOPs where it hurts least, per
+    layer.  A head's candidate is the sparse expert with the smaller rel.  Only experts with work[e] < work[0] and a finite rel
+    count.  On equal rel, take the smaller work, then expert 2.  A head with no such expert has no candidate.  Heads are
+    ranked by (rel of candidate, head id) ascending.  Start with every head on expert 0.  Walk the ranking.  While
+    cost > max_flops_share * (heads * work[0]), move the next head to its candidate.  cost = n0*work[0] + n1*work[1] +
+    n2*work[2], evaluated in double from the integer counts, left to right.  Stop when the cost is within the budget or the
+    candidates run out; max_flops_share >= 1 moves nothing.
+    This function is the definition of both rules: `ops.route_fidelity` (vorta_route_fidelity) applies them on the device."""
+    if (max_rel_error is None) == (max_flops_share is None):
+        raise ValueError("routes_from_fidelity: exactly one of max_rel_error and max_flops_share")
     rel = fid.rel_error().detach().cpu()
+    if max_flops_share is not None:
+        if geometry is None:
+            raise ValueError("routes_from_fidelity: max_flops_share needs `geometry` (the work of the experts: expert_work)")
+        share = float(max_flops_share)
+        if not share > 0:
+            raise ValueError(f"routes_from_fidelity: max_flops_share={max_flops_share} (a positive share)")
+        return _routes_within_budget(rel.float(), expert_work(geometry, text_valid), share)
     order = (2, 1)  # sparse experts, cheapest first
     if geometry is not None:
         work = expert_work(geometry, text_valid)

@@ -613,6 +613,55 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     return fid
 
 
+ROUTE_RULE_MODES = ("max_rel_error", "max_flops_share")
+
+
+@dataclass(frozen=True)
+class RouteRule:
+    """How the Eval processors route a call by its own measurement (`route_rule=`): `mode` one of ROUTE_RULE_MODES with its
+    `value`, on `n_rows` sampled video rows per head (`sample_rows` with `seed`; every row where the clip has fewer)"""
+    mode: str
+    value: float
+    n_rows: int = 512
+    seed: int = 0
+
+    def __post_init__(self):
+        if self.mode not in ROUTE_RULE_MODES or int(self.n_rows) < 1:
+            raise ValueError(f"RouteRule: mode={self.mode!r} (one of {ROUTE_RULE_MODES}), n_rows={self.n_rows} (at least 1)")
+
+    def route(self, q, k, v, geom: "RoutedGeometry", **kw):
+        """`route_by_fidelity` by this rule on (1,H,N,D) q, k, v"""
+        rows = sample_rows(geom.S, min(int(self.n_rows), geom.S), int(self.seed), q.device)
+        return route_by_fidelity(q, k, v, geom, rows=rows, **{self.mode: float(self.value)}, **kw)
+
+
+def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: RoutedGeometry, *, model: str,
+                      text_len: int = 0, text_valid: int = 0, scale: Optional[float] = None, rows=None, seed: int = 0,
+                      max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None
+                      ) -> Tuple["HeadRouting", torch.Tensor, "ops.ExpertFidelity"]:
+    """Routes of one layer MEASURED on its own q, k, v, by a stated rule and without a router: `max_rel_error` = no sparse head
+    may be further than that from dense attention on the sampled rows (per head the cheapest expert within the bound), or
+    `max_flops_share` = spend at most that share of the dense layer's FLOPs where it hurts least (exactly one of the two;
+    `vorta.patch.routes_from_fidelity` defines both).  Returns (HeadRouting, expert_ids, ops.ExpertFidelity): device head
+    lists with device counts (`HeadRouting.from_device`), the int32 (H,) head -> expert table and the record they came from.
+    Per call: `sampled_expert_fidelity` for every head with `out=None` (column 2 of the record stays NaN), then
+    `ops.route_fidelity` with `work = expert_work(geom, text_valid, D)`.  Everything runs on the current stream, nothing is
+    read back, graph-capturable once `geom.sample_tables` is built -- as the measurement is.
+    The measurement runs in the dtype of q, k, v whatever VORTA_ATTENTION_PRECISION says: the bound is on the METHOD (which
+    keys a head sees) on the sampled rows, not on what an 8-bit precision adds to the routed launches."""
+    if (max_rel_error is None) == (max_flops_share is None):
+        raise ValueError("route_by_fidelity: exactly one of max_rel_error and max_flops_share")
+    if rows is not None and (rows.numel() if torch.is_tensor(rows) else int(rows)) < 1:
+        raise ValueError("route_by_fidelity: rows: at least one sampled row (without one every error reads 0 and every head "
+                         "would meet any bound)")
+    from .patch.fidelity import expert_work
+    fid = sampled_expert_fidelity(q, k, v, geom, model=model, text_len=text_len, text_valid=text_valid, scale=scale, rows=rows,
+                                  seed=seed)
+    work = expert_work(geom, text_valid if model == "hunyuan" else 0, q.shape[-1])
+    expert, lists, counts = ops.route_fidelity(fid, max_rel_error=max_rel_error, max_flops_share=max_flops_share, work=work)
+    return HeadRouting.from_device(lists, counts), expert, fid
+
+
 def _side_streams(device: torch.device):
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _SIDE_STREAMS:

@@ -14,6 +14,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::coreset_select(x, latent, group, n_keep, ...) -> (keep_rows, drop_rows)  vorta_coreset_select
     vorta::sta_build_tables(like, latent, tile, window, t_eff, row_map) -> (q_rows, kv_rows)
     vorta::route_scores(scores, tau)                  -> (expert_of_head, head_lists, head_counts)
+    vorta::route_fidelity(sq_ref, sq_err, max_rel_error, max_flops_share, work)
+                                                      -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
     vorta::router_route(temb, weight, bias, heads, tau) -> (scores, expert_of_head, head_lists, head_counts)
     vorta::qk_norm_rope(x, weight, eps, cos, sin, rope_tokens, across_heads) -> () mutates x
     vorta::mix_experts(x0,x1,x2, scores, out)         -> ()    mutates out
@@ -108,6 +110,24 @@ def _(scores, tau):
     _, H, E = scores.shape
     i32 = dict(dtype=torch.int32)
     return scores.new_empty((H,), **i32), scores.new_empty((E, H), **i32), scores.new_empty((E,), **i32)
+
+
+@torch.library.custom_op("vorta::route_fidelity", mutates_args=(), device_types="cuda")
+def route_fidelity(sq_ref: torch.Tensor, sq_err: torch.Tensor, max_rel_error: Optional[float] = None,
+                   max_flops_share: Optional[float] = None, work: Optional[List[float]] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.route_fidelity on the statistics of one layer, sq_ref (H,) and sq_err (H,3): int32 (H,), (3,H), (3,) and the
+    routed layer's share of the dense FLOPs, float32 (1,); exactly one of `max_rel_error` and `max_flops_share`"""
+    return ops.route_fidelity(ops.ExpertFidelity(sq_ref, sq_ref, sq_err, sq_err), max_rel_error=max_rel_error,
+                              max_flops_share=max_flops_share, work=work, flops_share=True)
+
+
+@route_fidelity.register_fake
+def _(sq_ref, sq_err, max_rel_error=None, max_flops_share=None, work=None):
+    H = sq_ref.shape[0]
+    i32 = dict(dtype=torch.int32)
+    return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((3, H), **i32), sq_ref.new_empty((3,), **i32),
+            sq_ref.new_empty((1,), dtype=torch.float32))
 
 
 @torch.library.custom_op("vorta::router_route", mutates_args=(), device_types="cuda")
