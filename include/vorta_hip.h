@@ -59,7 +59,9 @@ extern "C" {
                                    vorta_attn_ticket_workspace_ints (a pure addition: two more symbols on the existing
                                    argument block; an older ABI-9 library lacks them, which a binding sees at symbol lookup)
                                    and head routing from measured statistics, vorta_route_fidelity (a pure addition: a binding
-                                   asks for the symbol and for vorta_route_fidelity_args_size()) */
+                                   asks for the symbol and for vorta_route_fidelity_args_size())
+                                   and the same over (precision tier, expert) pairs, vorta_route_fidelity_tiers (a pure
+                                   addition: the symbol and vorta_route_fidelity_tiers_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -954,6 +956,56 @@ typedef struct vorta_route_fidelity_args {
 
 int vorta_route_fidelity(const vorta_route_fidelity_args* args, void* hip_stream);
 int vorta_route_fidelity_args_size(void);
+
+/*
+ * vorta_route_fidelity_tiers (ABI 9, a pure addition: a binding asks for the symbol and for
+ * vorta_route_fidelity_tiers_args_size(); vorta_sizeof keeps its 17 indices) -- vorta_route_fidelity's error-bound rule over
+ * (precision tier, expert) PAIRS: the record holds, per tier the call may launch in, what each expert of each head writes IN
+ * THAT TIER'S PRECISION against the one dense reference in the input dtype, so the bound covers the precision of what is
+ * launched.  One launch of one workgroup; no atomics; the same bits on every run.  The rule is the host function's
+ * (vorta.patch.routes_from_fidelity_tiers), which is the definition.
+ *
+ * Tiers are the CALLER'S, cheapest first, 1..3 of them; the kernel knows them by index only.
+ *
+ * Candidates.  A candidate is a pair (t, e): tier index t, expert e.
+ *   - Its rel is vorta_route_fidelity's, in float32 from sq_err[t][h][c] and sq_ref[h]: c = 0 for expert 1 (coreset), c = 1
+ *     for expert 2 (sliding tile), c = 2 for expert 0 (full attention in tier t).  Same zero rules; NaN meets no bound.
+ *   - exact_tier names the tier whose full attention IS the reference: its column 2 is not read and counts as 0.  -1: none.
+ *   - Its cost is work[e] * tier_cost[t] in double, one rounded product (no fused multiply-add).
+ *
+ * Rule.
+ *   - Per head, take the cheapest candidate with rel <= (float)max_rel_error.
+ *   - On equal cost, take the lower tier index, then the larger expert id.
+ *   - Where no candidate qualifies, take full attention (expert 0) in the LAST tier.
+ *
+ * The FLOP-budget rule has no tier form: mode 1 is VORTA_EINVAL.
+ *
+ * VORTA_EINVAL for whatever vorta_route_fidelity refuses (a wrong struct_size; a null sq_ref, sq_err, expert_of_head,
+ * head_lists or head_counts; heads outside 1..1024; a NaN or negative bound; a work entry that is not positive and finite),
+ * and for a null tier_of_head, a mode other than 0, n_tiers outside 1..3, exact_tier outside -1..n_tiers-1 and a tier_cost
+ * entry (of the first n_tiers) that is not positive and finite.  Everything is looked at before anything is launched.
+ */
+typedef struct vorta_route_fidelity_tiers_args {
+  uint32_t struct_size;      /* = sizeof(vorta_route_fidelity_tiers_args) = vorta_route_fidelity_tiers_args_size() */
+  int32_t heads;             /* 1..1024 */
+  int32_t n_tiers;           /* 1..3 */
+  int32_t exact_tier;        /* -1..n_tiers-1 */
+  const float* sq_ref;       /* [heads] */
+  const float* sq_err;       /* [n_tiers][heads][3]; column 0 coreset, column 1 sliding tile, column 2 full attention, in that tier */
+  int32_t mode;              /* 0 = error bound; anything else: VORTA_EINVAL */
+  float max_rel_error;       /* >= 0 */
+  double work[3];            /* FLOPs of one head under expert 0 / 1 / 2 (patch.fidelity.expert_work); all > 0 */
+  double tier_cost[3];       /* cost of a FLOP in tier t relative to any common unit; the first n_tiers > 0 */
+  int32_t* expert_of_head;   /* [heads] */
+  int32_t* tier_of_head;     /* [heads], the caller's tier index */
+  int32_t* head_lists;       /* [n_tiers][3][heads], ascending head ids; entries at or past the count are not written */
+  int32_t* head_counts;      /* [n_tiers][3] */
+  float* cost_share;         /* optional, 1 float: sum over (t, e), t-major, of n[t][e] (work[e] tier_cost[t]), over
+                                heads (work[0] tier_cost[n_tiers-1]), in double from the integer counts, rounded once */
+} vorta_route_fidelity_tiers_args;
+
+int vorta_route_fidelity_tiers(const vorta_route_fidelity_tiers_args* args, void* hip_stream);
+int vorta_route_fidelity_tiers_args_size(void);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.

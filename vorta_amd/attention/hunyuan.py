@@ -12,7 +12,8 @@ import torch
 from .. import ops
 from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import HeadRouting, dense_attention_autograd, geometry_for, qk_norm_rope_autograd, soft_mixture_attention_autograd
+from ..routed import (HeadRouting, TierRoutes, dense_attention_autograd, geometry_for, qk_norm_rope_autograd, routed_attention_tiers,
+                      soft_mixture_attention_autograd, tier_sink_entry)
 from ..ulysses import SP_STATE, shrink_dim
 from .coreset_select import LowresGroupInfo
 from .sliding_tile import SlidingTileDescriptor
@@ -330,7 +331,8 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                  latent_shape: Tuple[int, int, int] = (30, 48, 80),
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
                  fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
-                 expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None):
+                 expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None,
+                 tier_routing: Optional[dict] = None):
         """Keyword names as hunyuan.py:521-539.  `head_routing` / `experts_host` are this build's additions: the
         routes of this layer already dispatched by the step's route plan (vorta_amd/patch/_engine.py), on the device /
         on the host; without them the dispatch runs here from `routing_score`.
@@ -343,7 +345,13 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
         route_rule: a `routed.RouteRule`: the call is routed by its OWN measurement (routed.route_by_fidelity on the projected
         q, k, v: a stated error bound or FLOP budget, on the device, no host read); `routing_score`, `tau_sparse` and
         `head_routing` are then not consulted, and `route_sink` (a list) receives (expert_ids, lists, counts, fid).  Refused
-        by name under sequence parallelism."""
+        by name under sequence parallelism.  With `route_rule.covers_precision` under an 8-bit process precision the call is
+        routed AND launched over (precision tier, expert) pairs (routed.route_by_fidelity(tiers=...), then
+        routed.routed_attention_tiers on the operands the measurement prepared); the sink then receives a 5-tuple: expert_ids,
+        the (n_tiers,3,H) lists, the (n_tiers,3) counts, the `native` tier's record, and a dictionary with `tiers` (names, in
+        launch order), `tier_ids` (int32 (H,), global ids) and `fids` (tier -> record).
+        tier_routing: tier -> HeadRouting (a stored `TierRoutes.routings`): the call launches it with
+        routed.routed_attention_tiers; nothing else is consulted.  Refused by name under sequence parallelism."""
         self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
         q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb)
         assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
@@ -355,6 +363,8 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
             if route_rule is not None:
                 raise NotImplementedError("route_rule: routing by a measured error bound or FLOP budget does not run under "
                                           "sequence parallelism (its gather reads whole heads of one process)")
+            if tier_routing is not None:
+                raise NotImplementedError("tier_routing: launching by precision tiers does not run under sequence parallelism")
             from ._sp import sp_attention
             buf = sp_attention(q, k, v, T, routing_score, tau_sparse, model="hunyuan", text_valid=te,
                                lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
@@ -365,13 +375,30 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
         if route_rule is not None:
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
-            head_routing, ids, fid = route_rule.route(q, k, v, geom, model="hunyuan", text_len=T, text_valid=te)
-            if route_sink is not None:
-                route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
+            routes = route_rule.route(q, k, v, geom, model="hunyuan", text_len=T, text_valid=te)
+            if isinstance(routes, TierRoutes):
+                tier_routing, tier_operands = routes.routings, routes.operands
+                if route_sink is not None:
+                    route_sink.append(tier_sink_entry(routes))
+            else:
+                head_routing, ids, fid = routes
+                if route_sink is not None:
+                    route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
+        elif tier_routing is not None:
+            tier_operands = None
         elif head_routing is None:
             _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
             head_routing = HeadRouting.from_device(lists, counts)
         buf, out = self._new_out(q)
+        if tier_routing is not None:
+            if expert_fidelity is not None:
+                raise ValueError("expert_fidelity: the per-expert sink does not go with a launch by precision tiers")
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            fkw = {} if fidelity is None else dict(fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
+            routed_attention_tiers(q, k, v, tier_routing, geom, model="hunyuan", text_len=T, text_valid=te, out=out,
+                                   operands=tier_operands, **fkw)
+            return self._output(attn, buf, T)
         if fidelity is not None or expert_fidelity is not None:
             # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
             from ..routed import routed_attention

@@ -10,7 +10,8 @@ import torch
 from .. import ops
 from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import (HeadRouting, dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
+from ..routed import (HeadRouting, TierRoutes, routed_attention_tiers, tier_sink_entry,
+                      dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
                       soft_mixture_attention_autograd)
 from ..ulysses import SP_STATE, shrink_dim
 from .coreset_select import LowresGroupInfo
@@ -216,14 +217,17 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
                  latent_shape: Tuple[int, int, int] = (20, 30, 52), use_original_attn: bool = False,
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
                  fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
-                 expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None):
+                 expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None,
+                 tier_routing: Optional[dict] = None):
         """Keyword names as wan.py:308-328; `head_routing` / `experts_host`: see the Hunyuan processor.
         fidelity: a list that receives one `ops.SampledFidelity` PER BATCH ITEM of this call, in item order (the routed output
         as run against dense attention on sampled rows, routed.routed_attention); cross attention and the dense teacher file
         nothing; None: the launches of today.  expert_fidelity: likewise one `ops.ExpertFidelity` per batch item
         (routed.sampled_expert_fidelity on the same `fidelity_rows`); refused by name under sequence parallelism.
         route_rule / route_sink: see the Hunyuan processor; a batch is routed, every item, by ITEM 0's measurement (the
-        reference's convention for scores, quoted below), so the sink receives one entry per call."""
+        reference's convention for scores, quoted below), so the sink receives one entry per call.  `covers_precision` and
+        `tier_routing`: see the Hunyuan processor; the operands the measurement prepared serve item 0's launches, every other
+        item converts its own."""
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
@@ -240,6 +244,8 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
             if route_rule is not None:
                 raise NotImplementedError("route_rule: routing by a measured error bound or FLOP budget does not run under "
                                           "sequence parallelism (its gather reads whole heads of one process)")
+            if tier_routing is not None:
+                raise NotImplementedError("tier_routing: launching by precision tiers does not run under sequence parallelism")
             from ._sp import sp_attention
             bufs = [sp_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], 0, routing_score, tau_sparse, model="wan",
                                  lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
@@ -249,13 +255,31 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         if route_rule is not None:
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
-            head_routing, ids, fid = route_rule.route(q[:1], k[:1], v[:1], geom, model="wan")
-            if route_sink is not None:
-                route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
+            routes = route_rule.route(q[:1], k[:1], v[:1], geom, model="wan")
+            if isinstance(routes, TierRoutes):
+                tier_routing, tier_operands = routes.routings, routes.operands
+                if route_sink is not None:
+                    route_sink.append(tier_sink_entry(routes))
+            else:
+                head_routing, ids, fid = routes
+                if route_sink is not None:
+                    route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
+        elif tier_routing is not None:
+            tier_operands = None
         elif head_routing is None:
             _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
             head_routing = HeadRouting.from_device(lists, counts)
         buf, out = self._new_out(q)
+        if tier_routing is not None:
+            if expert_fidelity is not None:
+                raise ValueError("expert_fidelity: the per-expert sink does not go with a launch by precision tiers")
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            fkw = {} if fidelity is None else dict(fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
+            for b in range(B):
+                routed_attention_tiers(q[b:b + 1], k[b:b + 1], v[b:b + 1], tier_routing, geom, model="wan", out=out[b:b + 1],
+                                       operands=tier_operands if b == 0 else None, **fkw)
+            return self._output_proj(attn, buf)
         if fidelity is not None or expert_fidelity is not None:
             # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
             from ..routed import routed_attention

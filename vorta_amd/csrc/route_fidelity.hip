@@ -18,6 +18,7 @@
 
 #include "vorta_hip.h"
 #include "common.h"
+#include "route_rel_error.h"
 
 #pragma clang fp contract(off)
 
@@ -34,14 +35,7 @@ struct FParams {
   int32_t* expert; int32_t* lists; int32_t* counts; float* flops_share;
 };
 
-// ExpertFidelity.rel_error() of one (head, column)
-__device__ __forceinline__ float rel_error(float err, float ref) {
-  if (ref == 0.f) {
-    if (err == 0.f) return 0.f;
-    if (err > 0.f) return INFINITY;
-  }
-  return sqrtf(err / ref);
-}
+using vorta_route::rel_error;  // ExpertFidelity.rel_error() of one (head, column); route_fidelity_tiers.hip forms the same
 
 __device__ __forceinline__ double cost_of(int n0, int n1, int n2, const FParams& p) {
   return ((double)n0 * p.w0 + (double)n1 * p.w1) + (double)n2 * p.w2;

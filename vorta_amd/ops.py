@@ -1214,6 +1214,93 @@ def route_fidelity(fid: ExpertFidelity, *, max_rel_error: Optional[float] = None
     return (expert, lists, counts) + ((share,) if flops_share else ())
 
 
+TIER_NAMES = ("native", "fp8pv", "i8pv")  # the global precision tier ids 0 / 1 / 2: the input dtype and the two 8-bit precisions
+# what a FLOP costs in a tier, relative to the 16-bit kernel.  Source: README.md, Wan-14B-81f on an MI355X -- the e4m3-PV
+# kernel runs 1.25 x and the int8-score kernel 1.66 - 1.70 x the bf16 kernel (1 / 1.25 = 0.80, 1 / 1.70 = 0.59)
+DEFAULT_TIER_COST = {"native": 1.0, "fp8pv": 0.80, "i8pv": 0.59}
+
+
+def tier_id(tier) -> int:
+    """the global tier id (0 native, 1 fp8pv, 2 i8pv) of a tier given by name or by id; ValueError for anything else"""
+    if isinstance(tier, str):
+        if tier not in TIER_NAMES:
+            raise ValueError(f"precision tier {tier!r}: one of {TIER_NAMES}")
+        return TIER_NAMES.index(tier)
+    if isinstance(tier, bool) or int(tier) != tier or not 0 <= int(tier) < len(TIER_NAMES):
+        raise ValueError(f"precision tier id {tier!r}: 0 (native), 1 (fp8pv), 2 (i8pv)")
+    return int(tier)
+
+
+def tier_plan(fids, tier_cost=None):
+    """(global tier ids, costs, exact tier index) of `fids`, a mapping tier -> ExpertFidelity in the caller's order (cheapest
+    first; the LAST is where a head without a candidate goes): 1..3 distinct tiers by name or id; `tier_cost` a mapping by
+    name or id whose entries replace DEFAULT_TIER_COST's (None: none), every entry positive and finite; the exact tier is
+    `native`'s index, whose full attention is the reference itself, or -1"""
+    import math
+    if not hasattr(fids, "keys"):
+        raise ValueError("precision tiers: a mapping tier -> ExpertFidelity, in the caller's order")
+    ids = [tier_id(t) for t in fids.keys()]
+    if not 1 <= len(ids) <= len(TIER_NAMES) or len(set(ids)) != len(ids):
+        raise ValueError(f"precision tiers: one to three distinct tiers of {TIER_NAMES}, got {list(fids.keys())}")
+    by_id = {tier_id(t): c for t, c in DEFAULT_TIER_COST.items()}
+    for t, c in ({} if tier_cost is None else tier_cost).items():
+        if c is None or isinstance(c, (bool, str)) or not (float(c) > 0 and math.isfinite(float(c))):
+            raise ValueError(f"tier_cost[{t!r}] = {c!r}: a positive finite cost")
+        by_id[tier_id(t)] = float(c)
+    return ids, [float(by_id[t]) for t in ids], (ids.index(0) if 0 in ids else -1)
+
+
+def route_fidelity_tiers(fids, *, max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None, work=None,
+                         tier_cost=None, cost_share: bool = False):
+    """vorta_route_fidelity_tiers: the head -> (tier, expert) tables of one layer from its measured statistics per precision
+    tier, by `vorta.patch.routes_from_fidelity_tiers`'s rule, without a host read.  `fids`: a mapping tier (name or global id)
+    -> ExpertFidelity in the caller's order, cheapest first (see `tier_plan`); each record's sq_err (H,3) float32 on the device
+    holds what the coreset (column 0), the sliding tile (column 1) and full attention (column 2) write IN THAT TIER against
+    the one dense reference; sq_ref (H,) is the first record's.  `native`'s column 2 is not read: it is the reference.
+    work: FLOPs of one head under expert 0 / 1 / 2; None = (3, 2, 1).  tier_cost: None = DEFAULT_TIER_COST.
+    `max_flops_share` is refused by name: the budget rule has no tier form.
+    Returns (expert_of_head (H,), tier_of_head (H,) = the INDEX into the caller's tiers, head_lists (n_tiers,3,H),
+    head_counts (n_tiers,3)) int32 on the device -- `HeadRouting.from_device(lists[t], counts[t])` takes a tier's -- and with
+    `cost_share=True` a fifth, one float32: the routed layer's cost over all heads on full attention in the last tier."""
+    if max_flops_share is not None:
+        raise ValueError("route_fidelity_tiers: max_flops_share has no form over precision tiers (a FLOP budget routes "
+                         "experts alone: route_fidelity); give max_rel_error")
+    if max_rel_error is None:
+        raise ValueError("route_fidelity_tiers: max_rel_error is the rule")
+    ids, costs, exact = tier_plan(fids, tier_cost)
+    records = list(fids.values())
+    sq_ref = records[0].sq_ref
+    _require_gpu(sq_ref, *(f.sq_err for f in records))
+    for f in records:
+        if sq_ref.dim() != 1 or tuple(f.sq_err.shape) != (sq_ref.shape[0], 3) or sq_ref.dtype != torch.float32 \
+                or f.sq_err.dtype != torch.float32:
+            raise ValueError("route_fidelity_tiers: the statistics of ONE layer, sq_ref (H,) and per tier sq_err (H, 3) in float32")
+    T = len(records)
+    sq_ref = sq_ref.contiguous()
+    sq_err = records[0].sq_err.contiguous() if T == 1 else torch.stack([f.sq_err for f in records])
+    H, dev = sq_ref.shape[0], sq_ref.device
+    expert = torch.empty(H, dtype=torch.int32, device=dev)
+    tier = torch.empty(H, dtype=torch.int32, device=dev)
+    lists = torch.empty((T, 3, H), dtype=torch.int32, device=dev)  # (entries at or past a count are not written, and not read)
+    counts = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    share = torch.empty(1, dtype=torch.float32, device=dev) if cost_share else None
+    a = _C.RouteFidelityTiersArgs()
+    a.struct_size = C.sizeof(_C.RouteFidelityTiersArgs)
+    a.heads, a.n_tiers, a.exact_tier, a.mode = H, T, exact, 0
+    a.sq_ref, a.sq_err = sq_ref.data_ptr(), sq_err.data_ptr()
+    a.max_rel_error = float(max_rel_error)
+    for e, w in enumerate(DEFAULT_ROUTE_WORK if work is None else work):
+        a.work[e] = float(w)
+    for t, c in enumerate(costs):
+        a.tier_cost[t] = c
+    a.expert_of_head, a.tier_of_head = expert.data_ptr(), tier.data_ptr()
+    a.head_lists, a.head_counts = lists.data_ptr(), counts.data_ptr()
+    if share is not None:
+        a.cost_share = share.data_ptr()
+    _C.check(_C.lib().vorta_route_fidelity_tiers(C.byref(a), _stream()), "vorta_route_fidelity_tiers")
+    return (expert, tier, lists, counts) + ((share,) if cost_share else ())
+
+
 class SampledFidelity(NamedTuple):
     """vorta_sampled_fidelity's statistics: per head how far the rows a ROUTED call wrote are from dense attention in the input
     dtype, on a sample of `rows.numel()` query rows.  Float32 tensors with any leading dimensions (a layer axis,

@@ -16,11 +16,13 @@ full attention) and the host helpers `routes_from_fidelity` / `evaluate_routing`
 `sampled_expert_fidelity(model)` / `sampled_expert_fidelity_of(model)`: what EVERY expert would have written on those rows (an
 `ExpertFidelity` without the soft mixture's forward), and `fixed_routes(model, table)`: run the model by an expert table;
 `measured_routes(model, max_rel_error=... | max_flops_share=...)` / `measured_routes_of(model)`: route every layer of every
-forward by its own measurement on the device -- a stated error bound or FLOP budget, no router checkpoint, no host read."""
+forward by its own measurement on the device -- a stated error bound or FLOP budget, no router checkpoint, no host read;
+`routes_from_fidelity_tiers`: the error-bound rule over (precision tier, expert) pairs, from one record per tier -- the
+definition `ops.route_fidelity_tiers` (vorta_route_fidelity_tiers) equals on the device."""
 from ._engine import all_reduce_router_grads, original_attention, routing_scores_of, token_sharded
-from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, measured_routes,
-                       measured_routes_of, routed_fidelity, routed_fidelity_of, routes_from_fidelity, sampled_expert_fidelity,
-                       sampled_expert_fidelity_of)
+from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, measured_precisions_of,
+                       measured_routes, measured_routes_of, routed_fidelity, routed_fidelity_of, routes_from_fidelity, routes_from_fidelity_tiers,
+                       sampled_expert_fidelity, sampled_expert_fidelity_of)
 from .router import Router, load_router_checkpoint
 from .utils import (Pixel2TokenFactory, hunyuan_pixel2token, prepare_hunyuan_self_attn_kwargs,
                     prepare_wan_self_attn_kwargs, wan_pixel2token)

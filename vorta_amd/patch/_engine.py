@@ -148,6 +148,9 @@ class ForwardState:
     # inside `fixed_routes(model, table)`: the (L, H) expert table this forward launches, and its per-layer HeadRouting
     fixed_routes: Optional[List[List[int]]] = None
     fixed_routing: Dict[int, HeadRouting] = field(default_factory=dict)
+    # `fixed_routes(model, table, precisions=...)`: the (L, H) table of global tier ids, and per layer tier -> HeadRouting
+    fixed_precisions: Optional[List[List[int]]] = None
+    fixed_tier_routing: Dict[int, Dict[str, HeadRouting]] = field(default_factory=dict)
     # inside `measured_routes(model, ...)`: the context's state (patch/fidelity.py MeasuredRoutes) and whether THIS forward
     # measures (forwards 0, k, 2k, ... of the context) or launches the lists the latest measuring forward stored
     measured_routes: Any = None
@@ -251,6 +254,7 @@ class StepContext:
     measure_experts: Optional[Tuple[int, int]] = None  # inside `sampled_expert_fidelity(model)`: (n_rows, seed)
     sampled_experts: Optional[Dict[int, Any]] = None  # the latest such forward's records (`sampled_expert_fidelity_of`)
     fixed_routes: Optional[List[List[int]]] = None  # inside `fixed_routes(model, table)`: the (L, H) expert table
+    fixed_precisions: Optional[List[List[int]]] = None  # ... and with `precisions=`: the (L, H) table of global tier ids
     measured_routes: Any = None  # inside `measured_routes(model, ...)`: its MeasuredRoutes (rule, forward count, stored lists)
     latest_measured_routes: Any = None  # that of the latest context left (what `measured_routes_of` reads outside one)
 
@@ -351,6 +355,18 @@ class BoundProcessor:
                                                                                   hidden_states.device)
                 kw["head_routing"] = state.fixed_routing[self.layer]
                 kw.setdefault("tau_sparse", 0.0)
+                if state.fixed_precisions is not None:
+                    # ... and this layer's row of the tier table: per tier the heads that run in it, host counts
+                    if "tier_routing" not in self._accepted:
+                        raise ValueError("fixed_routes(precisions=...): this model's Eval processor takes no `tier_routing`")
+                    if self.layer not in state.fixed_tier_routing:
+                        from ..ops import TIER_NAMES
+                        experts, tiers = state.fixed_routes[self.layer], state.fixed_precisions[self.layer]
+                        state.fixed_tier_routing[self.layer] = {
+                            TIER_NAMES[t]: HeadRouting.from_expert_ids([e if p == t else -1 for e, p in zip(experts, tiers)],
+                                                                       hidden_states.device)
+                            for t in sorted(set(tiers), reverse=True)}
+                    kw["tier_routing"] = state.fixed_tier_routing[self.layer]
             rsink = None
             if state.measured_routes is not None:
                 # under `measured_routes(model, ...)`: a measuring forward routes this layer by its own measurement and
@@ -362,6 +378,10 @@ class BoundProcessor:
                 if state.measures_routes:
                     rsink = []
                     kw["route_rule"], kw["route_sink"] = state.measured_routes.rule, rsink
+                elif state.measured_routes.stores_tiers(self.layer):
+                    if "tier_routing" not in self._accepted:
+                        raise ValueError("measured_routes(covers_precision=True): this model's Eval processor takes no `tier_routing`")
+                    kw["tier_routing"] = state.measured_routes.stored_tier_routing(self.layer)
                 else:
                     kw["head_routing"] = state.measured_routes.stored_routing(self.layer)  # (raises where there is none)
             if state.routed_fidelity is None and state.sampled_experts is None:
@@ -461,6 +481,7 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
                                    sampled_experts={} if ctx.measure_experts is not None and not ctx.teacher else None,
                                    measure_experts=ctx.measure_experts,
                                    fixed_routes=None if ctx.teacher else ctx.fixed_routes,
+                                   fixed_precisions=None if ctx.teacher else ctx.fixed_precisions,
                                    token_shard=token_shard)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
         ctx.forwards += 1

@@ -40,6 +40,14 @@ The same loop closed on the device -- every layer of every forward routed by its
     with measured_routes(model, max_rel_error=0.05, n_rows=512):       # or max_flops_share=0.4; no router, no tau_sparse, no host read
         model(hidden_states, ..., self_attention_kwargs=kw)            # routed.route_by_fidelity per layer (vorta_route_fidelity)
     experts, fid = measured_routes_of(model)          # (L, H) device table and the ExpertFidelity it came from
+
+And with the bound over the 8-bit PRECISION of what is launched (process precision "i8pv", "fp8pv" or "auto8"):
+
+    with measured_routes(model, max_rel_error=0.05, covers_precision=True):   # one measurement per precision tier, in its arithmetic
+        model(hidden_states, ..., self_attention_kwargs=kw)            # routed.route_by_fidelity(tiers=...) (vorta_route_fidelity_tiers)
+    tiers = measured_precisions_of(model)             # (L, H) global tier ids: 0 native, 1 fp8pv, 2 i8pv
+    with fixed_routes(model, measured_routes_of(model)[0], precisions=tiers):   # the same launches, nothing measured
+        model(hidden_states, ..., self_attention_kwargs=kw)
 """
 from __future__ import annotations
 
@@ -202,17 +210,37 @@ def sampled_expert_fidelity_of(model: nn.Module, item: int = 0) -> ExpertFidelit
 
 
 @contextlib.contextmanager
-def fixed_routes(model: nn.Module, table):
+def fixed_routes(model: nn.Module, table, precisions=None):
     """While active, the hard-routing (Eval) processors of `model` (patched with apply_vorta_transformer) launch the (L, H)
     expert `table` (0 full attention, 1 coreset, 2 sliding tile; e.g. `routes_from_fidelity`'s): every layer is routed by
     `HeadRouting.from_expert_ids(table[layer])`, with host counts, so an expert no head has launches nothing.  The routers'
     routes and `tau_sparse` are not consulted (a forward may leave `tau_sparse` out); `routed_fidelity_of(model).expert`
     reports the table.  The table is read once per forward, when it starts; teacher forwards stay dense.  Outside the context
     nothing changes.  ValueError for a table that is not (L, H) or holds another id.  Under sequence parallelism the context
-    refuses by name (NotImplementedError): the head placement there follows `RoutePlan.experts_host`, which knows routers only."""
+    refuses by name (NotImplementedError): the head placement there follows `RoutePlan.experts_host`, which knows routers only.
+    precisions: an (L, H) table of GLOBAL precision tier ids (0 native, 1 fp8pv, 2 i8pv; `measured_precisions_of(model)`'s):
+    every head runs its expert in that tier (`routed.routed_attention_tiers`), whatever the process precision would have
+    chosen for it.  ValueError for an id outside 0..2 and for a tier the process precision does not offer
+    (`routed.TIERS_OF_PRECISION`, read when the context is entered).  None: every head in the process precision, as ever."""
     ctx = context_of(model)
     if ctx.plan is None:
         raise ValueError("fixed_routes: the model was not patched with apply_vorta_transformer")
+    tier_table = None
+    if precisions is not None:
+        from ..routed import tiers_of
+        from ..ops import TIER_NAMES
+        p = torch.as_tensor(precisions).detach().cpu()
+        if p.is_floating_point() or p.dtype == torch.bool or tuple(p.shape) != (len(ctx.plan), ctx.plan.heads):
+            raise ValueError(f"fixed_routes: precisions: an integer tier table of shape ({len(ctx.plan)}, {ctx.plan.heads}) "
+                             f"(layers, heads), got {tuple(p.shape)} {p.dtype}")
+        if bool(((p < 0) | (p > 2)).any()):
+            raise ValueError("fixed_routes: precision tier ids are 0 (native), 1 (fp8pv), 2 (i8pv)")
+        offered = tiers_of(None)
+        missing = sorted({TIER_NAMES[int(x)] for x in p.flatten().tolist()} - set(offered))
+        if missing:
+            raise ValueError(f"fixed_routes: precisions name {missing}, which the process precision does not offer (its tiers: "
+                             f"{offered}; set_attention_precision)")
+        tier_table = [[int(x) for x in row] for row in p.tolist()]
     t = torch.as_tensor(table).detach().cpu()
     L, H = len(ctx.plan), ctx.plan.heads
     if t.is_floating_point() or t.dtype == torch.bool or tuple(t.shape) != (L, H):
@@ -226,10 +254,11 @@ def fixed_routes(model: nn.Module, table):
     if SP_STATE.enabled:
         raise NotImplementedError("fixed_routes: routing by a table does not run under sequence parallelism")
     previous, ctx.fixed_routes = ctx.fixed_routes, [[int(x) for x in row] for row in t.tolist()]
+    previous_tiers, ctx.fixed_precisions = ctx.fixed_precisions, tier_table
     try:
         yield model
     finally:
-        ctx.fixed_routes = previous
+        ctx.fixed_routes, ctx.fixed_precisions = previous, previous_tiers
 
 
 @dataclass(eq=False)
@@ -257,12 +286,27 @@ class MeasuredRoutes:
         if not entries:  # (never with the patch's own forwards: every routed layer of a measuring forward files its lists)
             raise RuntimeError(f"measured_routes: layer {layer} has no measured routes on record for a forward between two "
                                "measurements (the latest measuring forward did not run this layer's self-attention)")
+        if len(entries[0]) > 4:
+            raise RuntimeError(f"measured_routes: layer {layer} stored routes over precision tiers (stored_tier_routing)")
         return HeadRouting.from_device(entries[0][1], entries[0][2])
+
+    def stores_tiers(self, layer: int) -> bool:
+        """whether the latest measuring forward routed `layer` over precision tiers (a 5-tuple in the sink)"""
+        entries = self.filed.get(layer)
+        return bool(entries) and len(entries[0]) > 4
+
+    def stored_tier_routing(self, layer: int):
+        """tier -> HeadRouting of the device lists and counts the latest measuring forward stored for `layer`, in its launch
+        order: nothing is launched"""
+        from ..routed import HeadRouting
+        _, lists, counts, _, data = self.filed[layer][0]
+        return {name: HeadRouting.from_device(lists[i], counts[i]) for i, name in enumerate(data["tiers"])}
 
 
 @contextlib.contextmanager
 def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
-                    n_rows: int = 512, seed: int = 0, refresh_every: int = 1):
+                    n_rows: int = 512, seed: int = 0, refresh_every: int = 1, covers_precision: bool = False,
+                    tier_cost: Optional[Mapping] = None):
     """While active, every non-teacher forward of `model` (patched with apply_vorta_transformer, hard-routing Eval processors)
     routes each layer by a MEASUREMENT of that layer on its own q, k, v, held per prompt, per layer and per step, without a
     router checkpoint and without a host read (`routed.route_by_fidelity`: `n_rows` sampled video rows per head,
@@ -270,7 +314,15 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     `max_rel_error=b`: no sparse head is further than b from dense attention on the sampled rows -- per head the cheapest
     expert within the bound, full attention where none is; `max_flops_share=s`: per layer at most the share s of the all-dense
     FLOPs, spent where it hurts least (`routes_from_fidelity` defines both).  The bound covers the sampled rows and the METHOD:
-    the measurement runs in the dtype of q, k, v, whatever 8-bit precision the routed launches use.
+    the measurement runs in the dtype of q, k, v, whatever 8-bit precision the routed launches use -- unless
+    `covers_precision=True` (with `max_rel_error`; with `max_flops_share` a ValueError by name): every layer is then measured
+    once per precision tier of the process precision (`routed.TIERS_OF_PRECISION`: "i8pv" -> i8pv, native; "fp8pv" -> fp8pv,
+    native; "auto8" -> i8pv, fp8pv, native) IN that tier's precision, routed over (tier, expert) pairs -- per head the
+    cheapest within the bound, cost = work[expert] * tier_cost[tier] (`routes_from_fidelity_tiers` is the rule; `tier_cost`
+    None: `ops.DEFAULT_TIER_COST`), full attention in the input dtype where none is -- and launched tier by tier
+    (`routed.routed_attention_tiers`).  The bound then holds for the candidate launches on the sampled rows, precision
+    included; a full-size launch is the same arithmetic with another key cut and, under "i8pv", another grouping of rows into
+    waves.  Under "native" the flag changes nothing.  `measured_precisions_of(model)` reads the tiers back.
     `refresh_every=k`: the context counts the model's non-teacher forwards on the host and measures on forwards 0, k, 2k, ...
     of the context; between them every layer launches the device lists and counts it stored (`HeadRouting.from_device`),
     with nothing measured or launched beyond the routed call.  A pipeline that runs two forwards per step (Wan's
@@ -284,8 +336,17 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     ctx = context_of(model)
     if ctx.plan is None:
         raise ValueError("measured_routes: the model was not patched with apply_vorta_transformer")
+    if covers_precision and max_flops_share is not None:
+        raise ValueError("measured_routes: covers_precision with max_flops_share: a FLOP budget has no form over precision "
+                         "tiers; give max_rel_error")
+    if tier_cost is not None and not covers_precision:
+        raise ValueError("measured_routes: tier_cost goes with covers_precision=True")
     if (max_rel_error is None) == (max_flops_share is None):
         raise ValueError("measured_routes: exactly one of max_rel_error and max_flops_share")
+    if covers_precision:
+        from ..ops import tier_plan
+        tier_plan({"native": None}, tier_cost)  # (ValueError for a tier that is none of the three, a cost not positive and finite)
+        tier_cost = None if tier_cost is None else dict(tier_cost)
     mode = ROUTE_RULE_MODES[0] if max_flops_share is None else ROUTE_RULE_MODES[1]
     value = float(max_rel_error if max_flops_share is None else max_flops_share)
     if not (value >= 0 if max_flops_share is None else value > 0):
@@ -309,7 +370,8 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     from ..ulysses import SP_STATE
     if SP_STATE.enabled:
         raise NotImplementedError("measured_routes: routing by a measurement does not run under sequence parallelism")
-    ctx.measured_routes = MeasuredRoutes(RouteRule(mode, value, int(n_rows), int(seed)), int(refresh_every))
+    ctx.measured_routes = MeasuredRoutes(RouteRule(mode, value, int(n_rows), int(seed), bool(covers_precision), tier_cost),
+                                         int(refresh_every))
     try:
         yield model
     finally:
@@ -329,6 +391,21 @@ def measured_routes_of(model: nn.Module, item: int = 0) -> Tuple[torch.Tensor, E
                            "hard-routing (Eval) processors")
     entries = [measured.filed[layer][item] for layer in sorted(measured.filed)]
     return torch.stack([e[0] for e in entries]), stack_fidelity(e[3] for e in entries)
+
+
+def measured_precisions_of(model: nn.Module, item: int = 0) -> torch.Tensor:
+    """The (L, H) int32 table of GLOBAL precision tier ids (0 native, 1 fp8pv, 2 i8pv) of the model's latest MEASURING forward
+    under `measured_routes(model, ..., covers_precision=True)`, on the device, layers in block order: the tier every head was
+    launched in, beside `measured_routes_of(model)[0]`, its expert -- `fixed_routes(model, experts, precisions=...)` replays
+    the pair.  A layer that was routed over experts alone (without the flag, or under the "native" process precision) reads 0
+    throughout: every head in the process precision."""
+    ctx = context_of(model)
+    measured = ctx.measured_routes if ctx.measured_routes is not None else ctx.latest_measured_routes
+    if measured is None or not measured.filed:
+        raise RuntimeError("measured_precisions_of: no forward of this model has measured under measured_routes(model, ...) "
+                           "with hard-routing (Eval) processors")
+    entries = [measured.filed[layer][item] for layer in sorted(measured.filed)]
+    return torch.stack([e[4]["tier_ids"] if len(e) > 4 else torch.zeros_like(e[0]) for e in entries])
 
 
 Geometry = Union[Mapping[str, Any], Any]
@@ -442,6 +519,57 @@ def routes_from_fidelity(fid: ExpertFidelity, max_rel_error: Optional[float] = N
     for e in reversed(order):  # the cheapest is written last: it wins a tie
         table = torch.where(rel[..., _COLUMN_OF_EXPERT[e]] <= float(max_rel_error), torch.full_like(table, e), table)
     return table
+
+
+def routes_from_fidelity_tiers(fids, max_rel_error: Optional[float] = None, geometry: Optional[Geometry] = None,
+                               text_valid: int = 0, *, tier_cost: Optional[Mapping] = None,
+                               max_flops_share: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(experts, tiers), two (..., H) int64 tables (on the CPU): per head the expert AND the precision tier to launch it in,
+    from one record per tier.  `fids`: a mapping tier -> ExpertFidelity in the caller's order, cheapest first; a tier is
+    named `native` / `fp8pv` / `i8pv` or by its global id 0 / 1 / 2 (`ops.TIER_NAMES`), and `tiers` holds the global ids.  Tier
+    t's record holds what the coreset (column 0), the sliding tile (column 1) and FULL ATTENTION (column 2) write in that
+    tier's precision against dense attention in the input dtype (`routed.sampled_expert_fidelity(precision=...)`); sq_ref is
+    the first record's.  `native`'s full attention is that reference: its column 2 is not read and counts as 0.
+    The rule.  A candidate is a pair (tier index t, expert e) with rel = `rel_error` of its column, in float32, and
+    cost = work[e] * tier_cost[tier], one product in double; work = `expert_work(geometry, text_valid)`, (3, 2, 1) without a
+    geometry; `tier_cost` a mapping tier -> cost (None: `ops.DEFAULT_TIER_COST`).  Per head take the cheapest candidate with
+    rel <= max_rel_error (compared in float32; NaN meets no bound); on equal cost the lower tier index, then the larger
+    expert id; where no candidate qualifies, full attention in the LAST tier.
+    ValueError for `max_flops_share` (by name: a FLOP budget has no tier form), for a tier that is none of the three or named
+    twice, and for a `tier_cost` that is not positive and finite for a tier in use.
+    This function is the definition: `ops.route_fidelity_tiers` (vorta_route_fidelity_tiers) applies it on the device."""
+    from ..ops import DEFAULT_ROUTE_WORK, tier_plan
+    if max_flops_share is not None:
+        raise ValueError("routes_from_fidelity_tiers: max_flops_share has no form over precision tiers (a FLOP budget routes "
+                         "experts alone: routes_from_fidelity); give max_rel_error")
+    if max_rel_error is None or not float(max_rel_error) >= 0:
+        raise ValueError(f"routes_from_fidelity_tiers: max_rel_error={max_rel_error} (a bound >= 0)")
+    ids, costs, exact = tier_plan(fids, tier_cost)
+    work = DEFAULT_ROUTE_WORK if geometry is None else expert_work(geometry, text_valid)
+    bound = float(torch.tensor(float(max_rel_error), dtype=torch.float32))  # the comparison is float32's
+    records = list(fids.values())
+    sq_ref = records[0].sq_ref.detach().cpu().float()
+    rels = []  # per tier (N, H, 3) float32 as Python doubles
+    for f in records:
+        sq_err = f.sq_err.detach().cpu().float()
+        rel = ExpertFidelity(sq_ref, sq_ref, sq_err, sq_err).rel_error()
+        rels.append(rel.reshape(-1, rel.shape[-2], 3).tolist())
+    shape = tuple(records[0].sq_err.shape[:-1])
+    N, H, T = len(rels[0]), shape[-1], len(ids)
+    experts = torch.zeros((N, H), dtype=torch.int64)
+    tiers = torch.zeros((N, H), dtype=torch.int64)
+    for layer in range(N):
+        for h in range(H):
+            best = None  # (cost, tier index, -expert): the smallest wins
+            for t in range(T):
+                for e in (0, 1, 2):
+                    rel = 0.0 if (e == 0 and t == exact) else rels[t][layer][h][2 if e == 0 else _COLUMN_OF_EXPERT[e]]
+                    if rel <= bound:
+                        key = (float(work[e]) * costs[t], t, -e)
+                        best = key if best is None or key < best else best
+            t, e = (T - 1, 0) if best is None else (best[1], -best[2])
+            experts[layer, h], tiers[layer, h] = e, ids[t]
+    return experts.reshape(shape), tiers.reshape(shape)
 
 
 def evaluate_routing(experts_or_scores: torch.Tensor, fid: Union[ExpertFidelity, SampledFidelity], geometry: Geometry,

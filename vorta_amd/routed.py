@@ -530,7 +530,8 @@ def _head_slots(heads, H: int, device) -> dict:
 
 def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: RoutedGeometry, *, model: str,
                             text_len: int = 0, text_valid: int = 0, scale: Optional[float] = None, rows=None, seed: int = 0,
-                            out: Optional[torch.Tensor] = None, heads=None, outputs: Optional[list] = None
+                            out: Optional[torch.Tensor] = None, heads=None, outputs: Optional[list] = None,
+                            precision: Optional[str] = None, operands: Optional[AttnOperands] = None
                             ) -> "ops.ExpertFidelity":
     """What EVERY expert would have written for a head, on a sample of video rows: an `ops.ExpertFidelity` (column 0 coreset,
     column 1 sliding tile against dense attention on the same rows) without the soft mixture's three full-size forwards.
@@ -550,8 +551,26 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     heads: None = every head; else a sequence of head ids, an int32 device list, a (list, device count) pair or the
     head_list / n_heads / n_heads_dev dictionary of `HeadRouting.slot_args`.  Heads not measured hold NaN.
     outputs: a list that receives the compact (H, n, D) buffers -- dense, coreset, sliding (and the rows of `out`) -- and last
-    the int64 position order: compact row p is sample position order[p] (rows are ordered by sliding key list)."""
+    the int64 position order: compact row p is sample position order[p] (rows are ordered by sliding key list).
+    precision: None (above), or "fp8pv" / "i8pv" = the measurement IN THAT TIER'S PRECISION: the dense reference rows stay in
+    the input dtype; the coreset and the sliding launches read that precision's operands (K, V converted once per call by
+    `prepare_operands`, or `operands=` the AttnOperands the caller prepared for this precision -- "auto8" operands serve both
+    tiers -- and goes on to launch with); and a third compact launch runs FULL attention on the rows' own queries in that
+    precision, whose error is column 2 (the `mixed` slot of `ops.expert_fidelity`), and whose buffer `outputs` receives in the
+    place of the rows of `out`.  `precision` together with `out=` is a ValueError (column 2 holds one of the two).  The
+    coreset ranking still reads the 16-bit q, k, as the routed launches' does.  No host read; graph-capturable.  What the
+    record of a tier bounds: these launches on these rows.  A full-size launch of the same tier is the same arithmetic with
+    another key cut (`fidelity_ref_splits` against the routed call's own) and, under "i8pv", another grouping of rows into
+    waves (the int8 query scale is a wave's, over its 32 rows: DESIGN.md 6.8)."""
     hy = model == "hunyuan"
+    if precision is not None:
+        if precision not in ("fp8pv", "i8pv"):
+            raise ValueError(f"sampled_expert_fidelity: precision={precision!r} (None, 'fp8pv' or 'i8pv')")
+        if out is not None:
+            raise ValueError("sampled_expert_fidelity: precision= together with out=: column 2 holds full attention in that "
+                             "precision or the routed output, not both")
+    elif operands is not None:
+        raise ValueError("sampled_expert_fidelity: operands= goes with precision=")
     q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
     o3 = None if out is None else (out[0] if out.dim() == 4 else out)
     H, D, S, rm = q3.shape[0], q3.shape[-1], geom.S, geom.row_map
@@ -569,7 +588,7 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     # every row of a buffer the statistics pass reads is written only for the measured heads: the others hold zeros
     new = torch.empty if sl["head_list"] is None else torch.zeros
     q_own, q_rep, ref, low, sta = (new((H, n, D), dtype=q3.dtype, device=dev) for _ in range(5))
-    mixed = new((H, n, D), dtype=q3.dtype, device=dev) if o3 is not None else None
+    mixed = new((H, n, D), dtype=q3.dtype, device=dev) if o3 is not None or precision is not None else None
     if n and sl["n_heads"]:
         pk = dict(partial=True) if geom.is_partial else {}
         gm = CORESET_KV_GROUP_MAJOR
@@ -584,14 +603,20 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
                                     **pk, **sl)
             keep_q, drop_q = kq[0], kq[1]
             keep_k = kq[2] if gm else keep_q
-        ops.gather_sample_rows(q3, tabs.rows, dst_q=q_own, dst_qrep=q_rep, dst_out=mixed, out=o3, win=tabs.win,
+        ops.gather_sample_rows(q3, tabs.rows, dst_q=q_own, dst_qrep=q_rep, dst_out=mixed if o3 is not None else None, out=o3, win=tabs.win,
                                keep_rows=keep_q, drop_rows=drop_q, **sl)
         n_low = geom.S_low + te
-        common = dict(k=k3, v=v3, scale=scale, **sl)
-        calls = [dict(common, q=q_own, out=ref, n_q=n, q_valid=n, n_kv=S + te, kv_rows=None if rm is None else rm[:S + te],
-                      n_splits=fidelity_ref_splits(S + te), tag="fidelity_ref"),
+        dense = dict(k=k3, v=v3, scale=scale, **sl)  # the reference: the input dtype, whatever `precision`
+        common = dense if precision is None else dict(_tier_key_side(precision, operands, q3, k3, v3, scale), scale=scale, **sl)
+        full = dict(q=q_own, n_q=n, q_valid=n, n_kv=S + te, kv_rows=None if rm is None else rm[:S + te],
+                    n_splits=fidelity_ref_splits(S + te))
+        calls = [dict(dense, out=ref, tag="fidelity_ref", **full),
                  dict(common, q=q_rep, out=low, n_q=n, q_valid=n, n_kv=n_low, kv_rows=keep_k,
                       n_splits=fidelity_ref_splits(n_low), block_rows=SAMPLED_BLOCK_ROWS, tag="sampled_lowres")]
+        if precision is not None:
+            # (a fused grid is of one kernel family: the 16-bit reference goes alone, the tier's launches follow it)
+            ops.attn_fwd_batch(calls[:1])
+            calls = calls[1:] + [dict(common, out=mixed, tag="sampled_full", **full)]
         for start, count, lists, stride, n_kv, table, n_lists in tabs.classes:
             calls.append(dict(common, q=q_own[:, start:start + count], out=sta[:, start:start + count], n_q=count, n_kv=n_kv,
                               kv_rows=lists, kv_rows_stride_g=stride, q_block_table=table, n_key_lists=n_lists,
@@ -613,7 +638,32 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     return fid
 
 
+def _tier_key_side(precision: str, operands: Optional[AttnOperands], q3, k3, v3, scale) -> dict:
+    """k, v and what goes with them of an 8-bit tier's launches, from `operands` of that precision or of "auto8" (whose int8
+    launch is "i8pv"'s and whose 16-bit-score launch is "fp8pv"'s), prepared here where none is given"""
+    if operands is None:
+        operands = prepare_operands(precision, q3, k3, v3, scale)
+    if operands.precision not in (precision, "auto8"):
+        raise ValueError(f"sampled_expert_fidelity(precision={precision!r}): operands of {operands.precision!r}")
+    kw = operands.tail_kwargs(scale) if (precision == "fp8pv" and operands.precision == "auto8") else operands.kwargs(scale)
+    return {key: val for key, val in kw.items() if key not in ("q", "scale") and val is not None}
+
+
 ROUTE_RULE_MODES = ("max_rel_error", "max_flops_share")
+# the precision tiers a call may launch in, cheapest first, by the process precision (`set_attention_precision`); the last is
+# where a head goes that no candidate serves.  Tier names and global ids: ops.TIER_NAMES (0 native, 1 fp8pv, 2 i8pv)
+TIERS_OF_PRECISION = {"i8pv": ("i8pv", "native"), "fp8pv": ("fp8pv", "native"), "auto8": ("i8pv", "fp8pv", "native"),
+                      "native": ("native",)}
+DEFAULT_TIER_COST = ops.DEFAULT_TIER_COST  # (README.md: Wan-14B-81f, 1.25 x and 1.66 - 1.70 x the bf16 kernel)
+
+
+def tiers_of(fp8=None) -> Tuple[str, ...]:
+    """the tiers of an `fp8=` value (None: the process precision); "fp8" (both contractions in e4m3) is no product precision and
+    has no tiers"""
+    name = precision_of(fp8)
+    if name not in TIERS_OF_PRECISION:
+        raise ValueError(f"precision {name!r} has no tiers to route over: one of {tuple(TIERS_OF_PRECISION)}")
+    return TIERS_OF_PRECISION[name]
 
 
 @dataclass(frozen=True)
@@ -624,21 +674,51 @@ class RouteRule:
     value: float
     n_rows: int = 512
     seed: int = 0
+    covers_precision: bool = False       # route over (precision tier, expert) pairs of the process precision: `tiers()`
+    tier_cost: Optional[dict] = None     # tier -> cost of a FLOP there; None: DEFAULT_TIER_COST
 
     def __post_init__(self):
         if self.mode not in ROUTE_RULE_MODES or int(self.n_rows) < 1:
             raise ValueError(f"RouteRule: mode={self.mode!r} (one of {ROUTE_RULE_MODES}), n_rows={self.n_rows} (at least 1)")
+        if self.covers_precision and self.mode != ROUTE_RULE_MODES[0]:
+            raise ValueError("RouteRule: covers_precision goes with max_rel_error: max_flops_share has no form over precision "
+                             "tiers")
+
+    def tiers(self) -> Optional[Tuple[str, ...]]:
+        """the tiers this rule routes over NOW, by the process precision; None where it routes experts alone -- without
+        `covers_precision`, and under "native", whose one tier is the routes of today"""
+        if not self.covers_precision:
+            return None
+        tiers = tiers_of(None)
+        return None if tiers == ("native",) else tiers
 
     def route(self, q, k, v, geom: "RoutedGeometry", **kw):
-        """`route_by_fidelity` by this rule on (1,H,N,D) q, k, v"""
+        """`route_by_fidelity` by this rule on (1,H,N,D) q, k, v: its 3-tuple, or its `TierRoutes` where `tiers()` names some"""
         rows = sample_rows(geom.S, min(int(self.n_rows), geom.S), int(self.seed), q.device)
+        tiers = self.tiers()
+        if tiers is not None:
+            kw = dict(kw, tiers=tiers, tier_cost=self.tier_cost)
         return route_by_fidelity(q, k, v, geom, rows=rows, **{self.mode: float(self.value)}, **kw)
+
+
+class TierRoutes(NamedTuple):
+    """`route_by_fidelity(tiers=...)`: per tier, in the caller's order, the HeadRouting of its device lists; the int32 (H,)
+    head -> expert and head -> GLOBAL tier id tables; per tier the record it was measured by; per 8-bit tier the operands
+    that were prepared for the measurement (`routed_attention_tiers(operands=...)` launches with them); and the kernel's
+    (n_tiers,3,H) lists and (n_tiers,3) counts the routings are views of"""
+    routings: Dict[str, "HeadRouting"]
+    expert_ids: torch.Tensor
+    tier_ids: torch.Tensor
+    fids: Dict[str, "ops.ExpertFidelity"]
+    operands: Dict[str, AttnOperands]
+    lists: torch.Tensor
+    counts: torch.Tensor
 
 
 def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: RoutedGeometry, *, model: str,
                       text_len: int = 0, text_valid: int = 0, scale: Optional[float] = None, rows=None, seed: int = 0,
-                      max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None
-                      ) -> Tuple["HeadRouting", torch.Tensor, "ops.ExpertFidelity"]:
+                      max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
+                      tiers: Optional[Sequence] = None, tier_cost: Optional[dict] = None):
     """Routes of one layer MEASURED on its own q, k, v, by a stated rule and without a router: `max_rel_error` = no sparse head
     may be further than that from dense attention on the sampled rows (per head the cheapest expert within the bound), or
     `max_flops_share` = spend at most that share of the dense layer's FLOPs where it hurts least (exactly one of the two;
@@ -647,8 +727,19 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
     Per call: `sampled_expert_fidelity` for every head with `out=None` (column 2 of the record stays NaN), then
     `ops.route_fidelity` with `work = expert_work(geom, text_valid, D)`.  Everything runs on the current stream, nothing is
     read back, graph-capturable once `geom.sample_tables` is built -- as the measurement is.
-    The measurement runs in the dtype of q, k, v whatever VORTA_ATTENTION_PRECISION says: the bound is on the METHOD (which
-    keys a head sees) on the sampled rows, not on what an 8-bit precision adds to the routed launches."""
+    Without `tiers` the measurement runs in the dtype of q, k, v whatever VORTA_ATTENTION_PRECISION says: the bound is on
+    the METHOD (which keys a head sees) on the sampled rows, not on what an 8-bit precision adds to the routed launches.
+    tiers: the precision tiers the call may launch in, cheapest first (names or global ids of ops.TIER_NAMES; `tiers_of()`
+    gives the process precision's): the bound then covers the PRECISION too.  One measurement per tier -- `native`'s as
+    above, an 8-bit tier's by `sampled_expert_fidelity(precision=tier)` on operands prepared once and handed on -- then
+    `ops.route_fidelity_tiers` (`vorta.patch.routes_from_fidelity_tiers` is the rule: per head the cheapest (tier, expert)
+    pair within the bound, cost = work[expert] * tier_cost[tier]; full attention in the last tier where none is).  Returns a
+    `TierRoutes`; `routed_attention_tiers` launches it.  tier_cost: None = DEFAULT_TIER_COST.  `max_flops_share` with `tiers`
+    is a ValueError by name.  What the bound covers: the candidate launches on the sampled rows, in each tier's own
+    arithmetic; a full-size launch is that arithmetic with another key cut and, under "i8pv", another grouping of rows
+    into waves."""
+    if tiers is not None and max_flops_share is not None:
+        raise ValueError("route_by_fidelity: max_flops_share has no form over precision tiers; give max_rel_error")
     if (max_rel_error is None) == (max_flops_share is None):
         raise ValueError("route_by_fidelity: exactly one of max_rel_error and max_flops_share")
     if rows is not None and (rows.numel() if torch.is_tensor(rows) else int(rows)) < 1:
@@ -658,8 +749,79 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
     fid = sampled_expert_fidelity(q, k, v, geom, model=model, text_len=text_len, text_valid=text_valid, scale=scale, rows=rows,
                                   seed=seed)
     work = expert_work(geom, text_valid if model == "hunyuan" else 0, q.shape[-1])
+    if tiers is not None:
+        return _route_tiers(q, k, v, geom, fid, work, tiers, tier_cost, float(max_rel_error),
+                            dict(model=model, text_len=text_len, text_valid=text_valid, scale=scale, rows=rows, seed=seed))
     expert, lists, counts = ops.route_fidelity(fid, max_rel_error=max_rel_error, max_flops_share=max_flops_share, work=work)
     return HeadRouting.from_device(lists, counts), expert, fid
+
+
+def _route_tiers(q, k, v, geom, native_fid, work, tiers, tier_cost, bound: float, measure_kw: dict) -> TierRoutes:
+    """`route_by_fidelity(tiers=...)` after the native measurement"""
+    names = [ops.TIER_NAMES[ops.tier_id(t)] for t in tiers]
+    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
+    operands: Dict[str, AttnOperands] = {}
+    if "i8pv" in names:
+        operands["i8pv"] = prepare_operands("i8pv", q3, k3, v3, measure_kw["scale"])
+    if "fp8pv" in names:  # (the e4m3 V of "i8pv" is "fp8pv"'s: one conversion serves both)
+        i8 = operands.get("i8pv")
+        operands["fp8pv"] = (prepare_operands("fp8pv", q3, k3, v3, measure_kw["scale"]) if i8 is None
+                             else AttnOperands("fp8pv", q3, k3, i8.v, i8.v_descale))
+    fids = {name: native_fid if name == "native" else
+            sampled_expert_fidelity(q, k, v, geom, precision=name, operands=operands[name], **measure_kw) for name in names}
+    expert, tier, lists, counts = ops.route_fidelity_tiers(fids, max_rel_error=bound, work=work, tier_cost=tier_cost)
+    tier_ids = torch.zeros_like(tier)
+    for i, name in enumerate(names):  # the caller's index -> the global id, on the device
+        tier_ids = torch.where(tier == i, ops.TIER_NAMES.index(name), tier_ids)
+    routings = {name: HeadRouting.from_device(lists[i], counts[i]) for i, name in enumerate(names)}
+    return TierRoutes(routings, expert, tier_ids, fids, operands, lists, counts)
+
+
+def tier_sink_entry(routes: TierRoutes) -> tuple:
+    """what a processor's `route_sink` receives for a call routed over tiers: the four entries of a call routed over experts
+    -- expert_ids, lists (n_tiers,3,H), counts (n_tiers,3), a record (`native`'s, the method's error, where that tier is one of
+    them; else the first tier's) -- and the tier data"""
+    fid = routes.fids.get("native", next(iter(routes.fids.values())))
+    return (routes.expert_ids, routes.lists, routes.counts, fid,
+            dict(tiers=tuple(routes.routings), tier_ids=routes.tier_ids, fids=routes.fids))
+
+
+def _merge_sampled(records) -> "ops.SampledFidelity":
+    """the per-tier records of one `routed_attention_tiers` call as one: every head from the record that measured it"""
+    first = records[0]
+    for other in records[1:]:
+        pick = lambda a, b: None if a is None or b is None else torch.where(torch.isnan(a), b, a)  # noqa: E731
+        expert = None if first.expert is None or other.expert is None else torch.where(first.expert < 0, other.expert, first.expert)
+        first = first._replace(sq_ref=pick(first.sq_ref, other.sq_ref), max_ref=pick(first.max_ref, other.max_ref),
+                               sq_err=pick(first.sq_err, other.sq_err), max_err=pick(first.max_err, other.max_err),
+                               range_ref=pick(first.range_ref, other.range_ref),
+                               row_sq_err=pick(first.row_sq_err, other.row_sq_err), expert=expert)
+    return first
+
+
+def routed_attention_tiers(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routings, geom: RoutedGeometry, *,
+                           out: Optional[torch.Tensor] = None, operands: Optional[Dict[str, AttnOperands]] = None,
+                           fidelity: Optional[list] = None, **kw) -> torch.Tensor:
+    """One `routed_attention` call per precision tier: `routings` maps a tier (a name or global id of ops.TIER_NAMES) to the
+    HeadRouting of the heads that run in it (`TierRoutes.routings`; a head is in one list of one tier), each with `fp8=` that
+    tier, all writing disjoint heads of one `out`.  A tier whose device lists are empty launches workgroups that exit at once,
+    as "auto8"'s second part does.  operands: tier -> AttnOperands prepared already (`TierRoutes.operands`); a tier without
+    an entry converts its own.  fidelity: receives ONE `ops.SampledFidelity`, every head from the call that launched it.
+    Other keywords go to every `routed_attention` call (`fp8`, `fp8_operands`, `expert_outs` do not apply)."""
+    for bad in ("fp8", "fp8_operands", "expert_outs", "expert_fidelity"):
+        if bad in kw:
+            raise ValueError(f"routed_attention_tiers: {bad}= does not apply: a tier names its precision, one `out` takes the heads")
+    if out is None:
+        out = torch.empty_like(q)
+    records: list = []
+    for tier, routing in routings.items():
+        name = ops.TIER_NAMES[ops.tier_id(tier)]
+        routed_attention(q, k, v, routing, geom, out=out, fp8=False if name == "native" else name,
+                         operands=None if operands is None else operands.get(name),
+                         fidelity=None if fidelity is None else records, **kw)
+    if fidelity is not None:
+        fidelity.append(_merge_sampled(records))
+    return out
 
 
 def _side_streams(device: torch.device):

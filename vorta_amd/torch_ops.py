@@ -16,6 +16,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::route_scores(scores, tau)                  -> (expert_of_head, head_lists, head_counts)
     vorta::route_fidelity(sq_ref, sq_err, max_rel_error, max_flops_share, work)
                                                       -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
+    vorta::route_fidelity_tiers(sq_ref, sq_err, tiers, max_rel_error, work, tier_cost)
+                                                      -> (expert_of_head, tier_of_head, head_lists, head_counts, cost_share)   vorta_route_fidelity_tiers
     vorta::router_route(temb, weight, bias, heads, tau) -> (scores, expert_of_head, head_lists, head_counts)
     vorta::qk_norm_rope(x, weight, eps, cos, sin, rope_tokens, across_heads) -> () mutates x
     vorta::mix_experts(x0,x1,x2, scores, out)         -> ()    mutates out
@@ -128,6 +130,30 @@ def _(sq_ref, sq_err, max_rel_error=None, max_flops_share=None, work=None):
     i32 = dict(dtype=torch.int32)
     return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((3, H), **i32), sq_ref.new_empty((3,), **i32),
             sq_ref.new_empty((1,), dtype=torch.float32))
+
+
+@torch.library.custom_op("vorta::route_fidelity_tiers", mutates_args=(), device_types="cuda")
+def route_fidelity_tiers(sq_ref: torch.Tensor, sq_err: torch.Tensor, tiers: List[int], max_rel_error: float,
+                         work: Optional[List[float]] = None, tier_cost: Optional[List[float]] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.route_fidelity_tiers on the statistics of one layer: sq_ref (H,), sq_err (n_tiers,H,3), `tiers` the global tier ids
+    of sq_err's leading axis in the caller's order, `tier_cost` their costs in that order (None: ops.DEFAULT_TIER_COST):
+    int32 (H,), (H,), (n_tiers,3,H), (n_tiers,3) and the routed layer's cost share, float32 (1,)"""
+    if sq_err.dim() != 3 or sq_err.shape[0] != len(tiers) or (tier_cost is not None and len(tier_cost) != len(tiers)):
+        raise ValueError("route_fidelity_tiers: sq_err (n_tiers, H, 3) with one tier id, and one cost where given, per tier")
+    fids = {t: ops.ExpertFidelity(sq_ref, sq_ref, sq_err[i], sq_err[i]) for i, t in enumerate(tiers)}
+    if len(fids) != len(tiers):
+        raise ValueError(f"route_fidelity_tiers: distinct tiers, got {list(tiers)}")
+    cost = None if tier_cost is None else dict(zip(tiers, tier_cost))
+    return ops.route_fidelity_tiers(fids, max_rel_error=max_rel_error, work=work, tier_cost=cost, cost_share=True)
+
+
+@route_fidelity_tiers.register_fake
+def _(sq_ref, sq_err, tiers, max_rel_error, work=None, tier_cost=None):
+    H, T = sq_ref.shape[0], len(tiers)
+    i32 = dict(dtype=torch.int32)
+    return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((H,), **i32), sq_ref.new_empty((T, 3, H), **i32),
+            sq_ref.new_empty((T, 3), **i32), sq_ref.new_empty((1,), dtype=torch.float32))
 
 
 @torch.library.custom_op("vorta::router_route", mutates_args=(), device_types="cuda")
