@@ -61,7 +61,9 @@ extern "C" {
                                    and head routing from measured statistics, vorta_route_fidelity (a pure addition: a binding
                                    asks for the symbol and for vorta_route_fidelity_args_size())
                                    and the same over (precision tier, expert) pairs, vorta_route_fidelity_tiers (a pure
-                                   addition: the symbol and vorta_route_fidelity_tiers_args_size()) */
+                                   addition: the symbol and vorta_route_fidelity_tiers_args_size())
+                                   and the verification and repair of launched routes, vorta_route_repair (a pure addition:
+                                   the symbol and vorta_route_repair_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -1006,6 +1008,50 @@ typedef struct vorta_route_fidelity_tiers_args {
 
 int vorta_route_fidelity_tiers(const vorta_route_fidelity_tiers_args* args, void* hip_stream);
 int vorta_route_fidelity_tiers_args_size(void);
+
+/*
+ * vorta_route_repair (ABI 9, a pure addition: a binding asks for the symbol and for vorta_route_repair_args_size();
+ * vorta_sizeof keeps its 17 indices) -- verify what a forward LAUNCHED against a stated error and repair the routes.  The
+ * record is vorta_sampled_fidelity's (sq_ref, sq_err per head: the rows the routed launches wrote against dense attention in
+ * the input dtype).  One launch of one workgroup; no atomics; the same bits on every run.  The rule is the host function's
+ * (vorta.patch.repair_routes), which is the definition.
+ *
+ * Rule, per head h with e = expert_of_head[h] and t = tier_of_head[h] (0 where tier_of_head is NULL):
+ *   - e == -1 (no list names the head), or (e, t) == (0, exact_tier) (its launch IS the reference): not checked, kept.
+ *   - Otherwise rel = vorta_route_fidelity's, in float32 from sq_err[h] and sq_ref[h] (same zero rules).  rel <= repair_above:
+ *     kept.  Else (NaN included: NaN meets no bound) repaired: the head becomes (expert 0, exact_tier).
+ *
+ * expert_of_head, tier_of_head, head_lists and head_counts are updated IN PLACE: they are the buffers the next launches read.
+ * The lists are rebuilt from the head tables (the old lists are not read), ascending; entries at or past a count are not
+ * written.  repair_list receives the heads repaired by THIS launch, ascending, repair_count their number: the head list and
+ * device count of the dense launch that overwrites them.  The rule is idempotent: a second launch on the same record repairs
+ * nothing.
+ *
+ * VORTA_EINVAL for a wrong struct_size; a null sq_ref, sq_err, expert_of_head, head_lists, head_counts, repair_list or
+ * repair_count; a null tier_of_head with n_tiers > 1; heads outside 1..1024; n_tiers outside 1..3; exact_tier outside
+ * 0..n_tiers-1; a NaN or negative bound.  Everything is looked at before anything is launched.
+ */
+typedef struct vorta_route_repair_args {
+  uint32_t struct_size;      /* = sizeof(vorta_route_repair_args) = vorta_route_repair_args_size() */
+  int32_t heads;             /* 1..1024 */
+  int32_t n_tiers;           /* 1..3 */
+  int32_t exact_tier;        /* 0..n_tiers-1: the tier whose full attention is the reference */
+  float repair_above;        /* >= 0 */
+  int32_t reserved;          /* 0 */
+  const float* sq_ref;       /* [heads] */
+  const float* sq_err;       /* [heads] */
+  int32_t* expert_of_head;   /* [heads], in place: -1, 0, 1, 2 */
+  int32_t* tier_of_head;     /* [heads], in place, the caller's tier index; may be NULL when n_tiers == 1 */
+  int32_t* head_lists;       /* [n_tiers][3][heads], rewritten: ascending head ids; entries at or past the count are not written */
+  int32_t* head_counts;      /* [n_tiers][3], rewritten */
+  int32_t* repair_list;      /* [heads]: the heads repaired by this launch, ascending; entries at or past the count are not written */
+  int32_t* repair_count;     /* [1] */
+  int32_t* state_of_head;    /* optional, [heads]: 0 not checked, 1 kept, 2 repaired */
+  float* rel;                /* optional, [heads]: the error as checked; NaN for a head that was not checked */
+} vorta_route_repair_args;
+
+int vorta_route_repair(const vorta_route_repair_args* args, void* hip_stream);
+int vorta_route_repair_args_size(void);
 
 /*
  * vorta_seq_row_map -- physical row of every token for the zero-copy Ulysses layout.

@@ -12,8 +12,8 @@ import torch
 from .. import ops
 from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import (HeadRouting, TierRoutes, dense_attention_autograd, geometry_for, qk_norm_rope_autograd, routed_attention_tiers,
-                      soft_mixture_attention_autograd, tier_sink_entry)
+from ..routed import (HeadRouting, RepairableRoutes, TierRoutes, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
+                      routed_attention_repaired, routed_attention_tiers, soft_mixture_attention_autograd, tier_sink_entry)
 from ..ulysses import SP_STATE, shrink_dim
 from .coreset_select import LowresGroupInfo
 from .sliding_tile import SlidingTileDescriptor
@@ -332,7 +332,8 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
                  fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
                  expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None,
-                 tier_routing: Optional[dict] = None):
+                 tier_routing: Optional[dict] = None, repair_above: Optional[float] = None,
+                 repair_sink: Optional[list] = None):
         """Keyword names as hunyuan.py:521-539.  `head_routing` / `experts_host` are this build's additions: the
         routes of this layer already dispatched by the step's route plan (vorta_amd/patch/_engine.py), on the device /
         on the host; without them the dispatch runs here from `routing_score`.
@@ -351,7 +352,15 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
         the (n_tiers,3,H) lists, the (n_tiers,3) counts, the `native` tier's record, and a dictionary with `tiers` (names, in
         launch order), `tier_ids` (int32 (H,), global ids) and `fids` (tier -> record).
         tier_routing: tier -> HeadRouting (a stored `TierRoutes.routings`): the call launches it with
-        routed.routed_attention_tiers; nothing else is consulted.  Refused by name under sequence parallelism."""
+        routed.routed_attention_tiers; nothing else is consulted.  Refused by name under sequence parallelism.
+        repair_above / repair_sink: the call VERIFIES what it launched on the `fidelity_rows` and re-runs every head further
+        than `repair_above` from dense attention, dense in the input dtype, in this forward (routed.routed_attention_repaired):
+        whether the routes come from `route_rule`, from a device `head_routing` (its `expert_ids`; derived from its lists where
+        it has none) or from `tier_routing` -- then a routed.RepairableRoutes or TierRoutes, whose joint tables are rewritten in
+        place, as a `head_routing`'s lists and counts are: a later call with the same tables launches the repaired heads dense.
+        `repair_sink` (a list) receives the call's routed.RepairRecord; a `fidelity` sink receives that record's
+        SampledFidelity: the rows as they were BEFORE the repair.  None: the launches of today.  Refused by name under sequence
+        parallelism."""
         self._check_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
         q, k, v, T = self._project(attn, hidden_states, encoder_hidden_states, image_rotary_emb)
         assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
@@ -365,6 +374,9 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                                           "sequence parallelism (its gather reads whole heads of one process)")
             if tier_routing is not None:
                 raise NotImplementedError("tier_routing: launching by precision tiers does not run under sequence parallelism")
+            if repair_above is not None:
+                raise NotImplementedError("repair_above: verifying and repairing launched routes does not run under sequence "
+                                          "parallelism (its dense repair launch reads whole heads of one process)")
             from ._sp import sp_attention
             buf = sp_attention(q, k, v, T, routing_score, tau_sparse, model="hunyuan", text_valid=te,
                                lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
@@ -372,24 +384,43 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
                                fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
             return self._output(attn, buf, T)
         # top-1 / tau dispatch on the device: no torch.nonzero host sync (hunyuan.py:612-640)
+        tier_operands = None
         if route_rule is not None:
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             routes = route_rule.route(q, k, v, geom, model="hunyuan", text_len=T, text_valid=te)
             if isinstance(routes, TierRoutes):
-                tier_routing, tier_operands = routes.routings, routes.operands
+                tier_routing, tier_operands, repairable = routes.routings, routes.operands, routes
                 if route_sink is not None:
                     route_sink.append(tier_sink_entry(routes))
             else:
                 head_routing, ids, fid = routes
+                repairable = (head_routing, ids)
                 if route_sink is not None:
                     route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
         elif tier_routing is not None:
-            tier_operands = None
+            tier_operands, repairable = None, tier_routing
+            if isinstance(tier_routing, RepairableRoutes):  # (the joint tables of the tiers: launched by their views)
+                tier_routing = tier_routing.routings
         elif head_routing is None:
-            _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
-            head_routing = HeadRouting.from_device(lists, counts)
+            ids, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
+            head_routing = HeadRouting.from_device(lists, counts, ids)
+            repairable = head_routing
+        else:
+            repairable = head_routing
         buf, out = self._new_out(q)
+        if repair_above is not None:
+            if expert_fidelity is not None:
+                raise ValueError("expert_fidelity: the per-expert sink does not go with repair_above")
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            _, repaired = routed_attention_repaired(q, k, v, repairable, geom, repair_above=repair_above, rows=fidelity_rows,
+                                                    operands=tier_operands, model="hunyuan", text_len=T, text_valid=te, out=out)
+            if repair_sink is not None:
+                repair_sink.append(repaired)
+            if fidelity is not None:  # (the rows as they were BEFORE the repair: the record the repair was decided by)
+                fidelity.append(repaired.fidelity)
+            return self._output(attn, buf, T)
         if tier_routing is not None:
             if expert_fidelity is not None:
                 raise ValueError("expert_fidelity: the per-expert sink does not go with a launch by precision tiers")

@@ -10,7 +10,7 @@ import torch
 from .. import ops
 from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import (HeadRouting, TierRoutes, routed_attention_tiers, tier_sink_entry,
+from ..routed import (HeadRouting, RepairableRoutes, TierRoutes, routed_attention_repaired, routed_attention_tiers, tier_sink_entry,
                       dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
                       soft_mixture_attention_autograd)
 from ..ulysses import SP_STATE, shrink_dim
@@ -218,7 +218,8 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
                  head_routing: Optional[HeadRouting] = None, experts_host: Optional[List[int]] = None,
                  fidelity: Optional[list] = None, fidelity_rows=None, fidelity_heads: str = "sparse",
                  expert_fidelity: Optional[list] = None, route_rule=None, route_sink: Optional[list] = None,
-                 tier_routing: Optional[dict] = None):
+                 tier_routing: Optional[dict] = None, repair_above: Optional[float] = None,
+                 repair_sink: Optional[list] = None):
         """Keyword names as wan.py:308-328; `head_routing` / `experts_host`: see the Hunyuan processor.
         fidelity: a list that receives one `ops.SampledFidelity` PER BATCH ITEM of this call, in item order (the routed output
         as run against dense attention on sampled rows, routed.routed_attention); cross attention and the dense teacher file
@@ -227,7 +228,10 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         route_rule / route_sink: see the Hunyuan processor; a batch is routed, every item, by ITEM 0's measurement (the
         reference's convention for scores, quoted below), so the sink receives one entry per call.  `covers_precision` and
         `tier_routing`: see the Hunyuan processor; the operands the measurement prepared serve item 0's launches, every other
-        item converts its own."""
+        item converts its own.
+        repair_above / repair_sink: see the Hunyuan processor; ITEM 0 is verified and repaired, and every other item launches
+        the repaired tables -- item 0's repaired heads dense -- without a verification of its own; the sink receives one
+        record per call."""
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
@@ -246,30 +250,58 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
                                           "sequence parallelism (its gather reads whole heads of one process)")
             if tier_routing is not None:
                 raise NotImplementedError("tier_routing: launching by precision tiers does not run under sequence parallelism")
+            if repair_above is not None:
+                raise NotImplementedError("repair_above: verifying and repairing launched routes does not run under sequence "
+                                          "parallelism (its dense repair launch reads whole heads of one process)")
             from ._sp import sp_attention
             bufs = [sp_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], 0, routing_score, tau_sparse, model="wan",
                                  lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
                                  latent_shape=latent_shape, experts_host=experts_host, fidelity=fidelity,
                                  fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads) for b in range(B)]
             return self._output_proj(attn, bufs[0] if B == 1 else torch.cat(bufs, dim=0))
+        tier_operands = None
         if route_rule is not None:
             geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
                                 device=q.device)
             routes = route_rule.route(q[:1], k[:1], v[:1], geom, model="wan")
             if isinstance(routes, TierRoutes):
-                tier_routing, tier_operands = routes.routings, routes.operands
+                tier_routing, tier_operands, repairable = routes.routings, routes.operands, routes
                 if route_sink is not None:
                     route_sink.append(tier_sink_entry(routes))
             else:
                 head_routing, ids, fid = routes
+                repairable = (head_routing, ids)
                 if route_sink is not None:
                     route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
         elif tier_routing is not None:
-            tier_operands = None
+            tier_operands, repairable = None, tier_routing
+            if isinstance(tier_routing, RepairableRoutes):  # (the joint tables of the tiers: launched by their views)
+                tier_routing = tier_routing.routings
         elif head_routing is None:
-            _, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
-            head_routing = HeadRouting.from_device(lists, counts)
+            ids, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
+            head_routing = HeadRouting.from_device(lists, counts, ids)
+            repairable = head_routing
+        else:
+            repairable = head_routing
         buf, out = self._new_out(q)
+        if repair_above is not None:
+            if expert_fidelity is not None:
+                raise ValueError("expert_fidelity: the per-expert sink does not go with repair_above")
+            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
+                                device=q.device)
+            # item 0 is verified and repaired; the tables are repaired in place, so every other item launches item 0's
+            # repaired heads dense (the convention for routes: a batch follows item 0)
+            _, repaired = routed_attention_repaired(q[:1], k[:1], v[:1], repairable, geom, repair_above=repair_above,
+                                                    rows=fidelity_rows, operands=tier_operands, model="wan", out=out[:1])
+            if repair_sink is not None:
+                repair_sink.append(repaired)
+            if fidelity is not None:  # (the rows as they were BEFORE the repair: the record the repair was decided by)
+                fidelity.append(repaired.fidelity)
+            fkw = {} if fidelity is None else dict(fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
+            for b in range(1, B):
+                routed_attention_repaired(q[b:b + 1], k[b:b + 1], v[b:b + 1], repaired.routes, geom, repair_above=None,
+                                          model="wan", out=out[b:b + 1], **fkw)
+            return self._output_proj(attn, buf)
         if tier_routing is not None:
             if expert_fidelity is not None:
                 raise ValueError("expert_fidelity: the per-expert sink does not go with a launch by precision tiers")

@@ -1301,6 +1301,55 @@ def route_fidelity_tiers(fids, *, max_rel_error: Optional[float] = None, max_flo
     return (expert, tier, lists, counts) + ((share,) if cost_share else ())
 
 
+def route_repair(sq_ref: torch.Tensor, sq_err: torch.Tensor, expert_of_head: torch.Tensor,
+                 tier_of_head: Optional[torch.Tensor], head_lists: torch.Tensor, head_counts: torch.Tensor, *,
+                 exact_tier: int, repair_above: float, out=None):
+    """vorta_route_repair: verify the routes of one layer AS LAUNCHED against the bound `repair_above` and repair them, by
+    `vorta.patch.repair_routes`'s rule, without a host read.  sq_ref, sq_err: float32 (H,) on the device, the fields of the
+    `SampledFidelity` the launches were verified by.  The route tables are int32 on the device, contiguous, and are updated IN
+    PLACE: expert_of_head (H,), tier_of_head (H,) = the caller's tier index (None with one tier), head_lists (n_tiers,3,H) or
+    (3,H), head_counts (n_tiers,3) or (3,).  A checked head whose rel is over the bound (or NaN) becomes (expert 0,
+    `exact_tier`), and the lists and counts are rebuilt.
+    Returns (repair_list (H,) int32: the heads repaired by this call, ascending, entries past the count unwritten;
+    repair_count (1,) int32; state_of_head (H,) int32: 0 not checked, 1 kept, 2 repaired; rel (H,) float32, NaN for a head
+    that was not checked), fresh device tensors, or the four of `out=` (a caller's buffers at fixed addresses)."""
+    _require_gpu(sq_ref, sq_err, expert_of_head, tier_of_head, head_lists, head_counts)
+    if sq_ref.dim() != 1 or sq_err.shape != sq_ref.shape or sq_ref.dtype != torch.float32 or sq_err.dtype != torch.float32:
+        raise ValueError("route_repair: the record of ONE layer, sq_ref (H,) and sq_err (H,) in float32")
+    H = sq_ref.shape[0]
+    T = head_lists.shape[0] if head_lists.dim() == 3 else 1
+    tables = [expert_of_head, head_lists, head_counts] + ([] if tier_of_head is None else [tier_of_head])
+    if any(t.dtype != torch.int32 or not t.is_contiguous() for t in tables):
+        raise ValueError("route_repair: the route tables are contiguous int32 tensors (they are updated in place)")
+    if tuple(expert_of_head.shape) != (H,) or (tier_of_head is not None and tuple(tier_of_head.shape) != (H,)) \
+            or tuple(head_lists.shape) not in ((T, 3, H), (3, H)) or head_counts.numel() != T * 3:
+        raise ValueError(f"route_repair: expert_of_head and tier_of_head ({H},), head_lists (n_tiers, 3, {H}), head_counts "
+                         "(n_tiers, 3)")
+    sq_ref, sq_err = sq_ref.contiguous(), sq_err.contiguous()
+    dev = sq_ref.device
+    if out is None:
+        out = (torch.empty(H, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+               torch.empty(H, dtype=torch.int32, device=dev), torch.empty(H, dtype=torch.float32, device=dev))
+    repair_list, repair_count, state, rel = out
+    _require_gpu(*out)
+    if (repair_list.dtype, repair_count.dtype, state.dtype, rel.dtype) != (torch.int32,) * 3 + (torch.float32,) \
+            or repair_list.numel() < H or repair_count.numel() < 1 or state.numel() < H or rel.numel() < H \
+            or not all(t.is_contiguous() for t in out):
+        raise ValueError(f"route_repair: out = (repair_list int32 ({H},), repair_count int32 (1,), state int32 ({H},), rel "
+                         f"float32 ({H},)), contiguous")
+    a = _C.RouteRepairArgs()
+    a.struct_size = C.sizeof(_C.RouteRepairArgs)
+    a.heads, a.n_tiers, a.exact_tier = H, T, int(exact_tier)
+    a.repair_above = float(repair_above)
+    a.sq_ref, a.sq_err = sq_ref.data_ptr(), sq_err.data_ptr()
+    a.expert_of_head, a.tier_of_head = expert_of_head.data_ptr(), _ptr(tier_of_head)
+    a.head_lists, a.head_counts = head_lists.data_ptr(), head_counts.data_ptr()
+    a.repair_list, a.repair_count = repair_list.data_ptr(), repair_count.data_ptr()
+    a.state_of_head, a.rel = state.data_ptr(), rel.data_ptr()
+    _C.check(_C.lib().vorta_route_repair(C.byref(a), _stream()), "vorta_route_repair")
+    return repair_list, repair_count, state, rel
+
+
 class SampledFidelity(NamedTuple):
     """vorta_sampled_fidelity's statistics: per head how far the rows a ROUTED call wrote are from dense attention in the input
     dtype, on a sample of `rows.numel()` query rows.  Float32 tensors with any leading dimensions (a layer axis,

@@ -18,11 +18,14 @@ full attention) and the host helpers `routes_from_fidelity` / `evaluate_routing`
 `measured_routes(model, max_rel_error=... | max_flops_share=...)` / `measured_routes_of(model)`: route every layer of every
 forward by its own measurement on the device -- a stated error bound or FLOP budget, no router checkpoint, no host read;
 `routes_from_fidelity_tiers`: the error-bound rule over (precision tier, expert) pairs, from one record per tier -- the
-definition `ops.route_fidelity_tiers` (vorta_route_fidelity_tiers) equals on the device."""
+definition `ops.route_fidelity_tiers` (vorta_route_fidelity_tiers) equals on the device; `repair_routes`: which heads, as
+launched, are over a stated error on the sampled rows and the routes without them -- the definition `ops.route_repair`
+(vorta_route_repair) equals; `measured_routes(..., repair_above=...)` / `fixed_routes(..., repair_above=...)` verify and repair
+every forward by it, and `repaired_routes_of(model)` reads the latest forward's tables."""
 from ._engine import all_reduce_router_grads, original_attention, routing_scores_of, token_sharded
 from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, measured_precisions_of,
-                       measured_routes, measured_routes_of, routed_fidelity, routed_fidelity_of, routes_from_fidelity, routes_from_fidelity_tiers,
-                       sampled_expert_fidelity, sampled_expert_fidelity_of)
+                       measured_routes, measured_routes_of, repair_routes, repaired_routes_of, routed_fidelity, routed_fidelity_of,
+                       routes_from_fidelity, routes_from_fidelity_tiers, sampled_expert_fidelity, sampled_expert_fidelity_of)
 from .router import Router, load_router_checkpoint
 from .utils import (Pixel2TokenFactory, hunyuan_pixel2token, prepare_hunyuan_self_attn_kwargs,
                     prepare_wan_self_attn_kwargs, wan_pixel2token)

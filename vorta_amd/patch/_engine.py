@@ -155,6 +155,9 @@ class ForwardState:
     # measures (forwards 0, k, 2k, ... of the context) or launches the lists the latest measuring forward stored
     measured_routes: Any = None
     measures_routes: bool = False
+    # inside `measured_routes(..., repair_above=b)` / `fixed_routes(..., repair_above=b)`: the context's RouteRepair
+    # (patch/fidelity.py): every routed call of this forward verifies what it launched and repairs the heads over the bound
+    route_repair: Any = None
     token_shard: bool = False                    # sequence parallel: this forward got the WHOLE latent and cuts its tokens itself
 
 
@@ -257,6 +260,8 @@ class StepContext:
     fixed_precisions: Optional[List[List[int]]] = None  # ... and with `precisions=`: the (L, H) table of global tier ids
     measured_routes: Any = None  # inside `measured_routes(model, ...)`: its MeasuredRoutes (rule, forward count, stored lists)
     latest_measured_routes: Any = None  # that of the latest context left (what `measured_routes_of` reads outside one)
+    route_repair: Any = None  # inside a context with `repair_above`: its RouteRepair (bound, sample, per-layer tables and records)
+    latest_route_repair: Any = None  # that of the latest context left (what `repaired_routes_of` reads outside one)
 
     def state_for(self, rotary) -> Optional[ForwardState]:
         """the state of the forward a processor call belongs to: the running forward's (in grad mode filed under `rotary`
@@ -347,7 +352,31 @@ class BoundProcessor:
             if "experts_host" in self._accepted and SP_STATE.enabled:
                 kw["experts_host"] = ctx.plan.experts_host(self.layer)
         if "fidelity_rows" in self._accepted:  # a hard-routing (Eval) processor: its sinks take the ROUTED call's statistics
-            if state.fixed_routes is not None:
+            repair, psink = state.route_repair, None
+            if repair is not None:
+                # every routed call verifies what it launched on the context's sample and repairs the heads over the bound
+                if "repair_above" not in self._accepted:
+                    raise ValueError("repair_above: this model's Eval processor takes no `repair_above`")
+                if SP_STATE.enabled:
+                    raise NotImplementedError("repair_above: verifying and repairing launched routes does not run under "
+                                              "sequence parallelism")
+                psink = []
+                kw["repair_above"], kw["repair_sink"] = repair.bound, psink
+                kw["fidelity_rows"] = repair.rows(kw.get("latent_shape", self._default_latent), hidden_states.device)
+            if state.fixed_routes is not None and repair is not None:
+                # under `fixed_routes(model, table, repair_above=b)`: this layer's rows of the tables as DEVICE tables, placed
+                # once per context entry -- the repairs of a forward persist in them until the context exits
+                kw.setdefault("tau_sparse", 0.0)
+                routes = repair.fixed_tables(self.layer, state.fixed_routes[self.layer],
+                                             None if state.fixed_precisions is None else state.fixed_precisions[self.layer],
+                                             hidden_states.device)
+                if routes.tier_index is None:
+                    kw["head_routing"] = HeadRouting.from_device(routes.lists[0], routes.counts[0], routes.expert_ids)
+                elif "tier_routing" not in self._accepted:
+                    raise ValueError("fixed_routes(precisions=...): this model's Eval processor takes no `tier_routing`")
+                else:
+                    kw["tier_routing"] = routes
+            elif state.fixed_routes is not None:
                 # under `fixed_routes(model, table)`: this layer's row of the table, host counts; the plan's routes and
                 # `tau_sparse` are not consulted
                 if self.layer not in state.fixed_routing:
@@ -381,13 +410,17 @@ class BoundProcessor:
                 elif state.measured_routes.stores_tiers(self.layer):
                     if "tier_routing" not in self._accepted:
                         raise ValueError("measured_routes(covers_precision=True): this model's Eval processor takes no `tier_routing`")
-                    kw["tier_routing"] = state.measured_routes.stored_tier_routing(self.layer)
+                    # (with a repair: the stored joint tables themselves, which the call rewrites in place)
+                    kw["tier_routing"] = (state.measured_routes.stored_tier_routing(self.layer) if repair is None
+                                          else state.measured_routes.stored_repairable(self.layer))
                 else:
                     kw["head_routing"] = state.measured_routes.stored_routing(self.layer)  # (raises where there is none)
             if state.routed_fidelity is None and state.sampled_experts is None:
                 out = self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
                 if rsink:  # (a cross-attention call measures nothing)
                     state.measured_routes.file(self.layer, rsink)
+                if psink:
+                    repair.file(self.layer, psink[0])
                 return out
             # under `routed_fidelity(model)` / `sampled_expert_fidelity(model)`: the sample is fixed per (S, n, seed) -- one
             # cached table, no host work per layer; the two share it
@@ -412,6 +445,8 @@ class BoundProcessor:
                 state.sampled_experts[self.layer] = esink
             if rsink:
                 state.measured_routes.file(self.layer, rsink)
+            if psink:
+                repair.file(self.layer, psink[0])
             return out
         if state.fidelity is None or "fidelity" not in self._accepted:
             return self.inner(attn, hidden_states, encoder_hidden_states, attention_mask, rotary, **kw)
@@ -482,6 +517,7 @@ def install_forward_protocol(model: nn.Module, ctx: StepContext, prepare_kwargs=
                                    measure_experts=ctx.measure_experts,
                                    fixed_routes=None if ctx.teacher else ctx.fixed_routes,
                                    fixed_precisions=None if ctx.teacher else ctx.fixed_precisions,
+                                   route_repair=None if ctx.teacher else ctx.route_repair,
                                    token_shard=token_shard)
         ctx.return_routing_scores = bool(extra.get("return_routing_scores", ctx.default_return_routing_scores))
         ctx.forwards += 1

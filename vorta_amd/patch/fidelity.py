@@ -48,13 +48,21 @@ And with the bound over the 8-bit PRECISION of what is launched (process precisi
     tiers = measured_precisions_of(model)             # (L, H) global tier ids: 0 native, 1 fp8pv, 2 i8pv
     with fixed_routes(model, measured_routes_of(model)[0], precisions=tiers):   # the same launches, nothing measured
         model(hidden_states, ..., self_attention_kwargs=kw)
+
+And a bound on what every forward LAUNCHED -- stored routes between two measurements, a reused table, the 8-bit launches:
+
+    with measured_routes(model, max_rel_error=0.05, refresh_every=4, repair_above=0.08):   # verify on the sampled rows, repair
+        model(hidden_states, ..., self_attention_kwargs=kw)            # routed.routed_attention_repaired (vorta_route_repair)
+    rel, state, experts, tiers = repaired_routes_of(model)             # (L, H): as checked | 0 / 1 kept / 2 repaired | after
+    with fixed_routes(model, table, precisions=tiers, repair_above=0.08):   # `repair_routes` is the rule on the host
+        model(hidden_states, ..., self_attention_kwargs=kw)
 """
 from __future__ import annotations
 
 import contextlib
 import math
 from dataclasses import dataclass, field
-from typing import Any, Dict, Mapping, Optional, Tuple, Union
+from typing import Any, Dict, Mapping, NamedTuple, Optional, Tuple, Union
 
 import torch
 from torch import nn
@@ -119,7 +127,11 @@ def routed_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0, heads: 
     experts, "all" = the full-attention heads as well (what an 8-bit precision costs them).  The flag is read once per
     forward, when it starts; teacher forwards (`original_attention`) measure nothing.  The forward stays free of host
     synchronisation and graph-capturable: the table is fixed, the gather, the launches and the compare run on the caller's
-    stream.  Outside the context the forwards launch what they launch today."""
+    stream.  Outside the context the forwards launch what they launch today.
+    Together with `repair_above` (`measured_routes(..., repair_above=b)`, `fixed_routes(..., repair_above=b)`; the same
+    (n_rows, seed): the two share one sample) the record reports the rows AS THEY WERE BEFORE THE REPAIR -- it is the record
+    the repair was decided by, with `expert` the routes as launched -- and its heads are the verification's, whatever `heads`
+    says: the sparse heads of the native tier, every head of an 8-bit tier."""
     from ..routed import FIDELITY_HEADS
     ctx = context_of(model)
     if ctx.plan is None:
@@ -133,6 +145,10 @@ def routed_fidelity(model: nn.Module, n_rows: int = 2048, seed: int = 0, heads: 
     if rule is not None and (rule.n_rows, rule.seed) != (int(n_rows), int(seed)):
         raise ValueError(f"routed_fidelity(n_rows={n_rows}, seed={seed}) inside measured_routes(n_rows={rule.n_rows}, "
                          f"seed={rule.seed}): the two share one sample")
+    repair = ctx.route_repair
+    if repair is not None and (repair.n_rows, repair.seed) != (int(n_rows), int(seed)):
+        raise ValueError(f"routed_fidelity(n_rows={n_rows}, seed={seed}) inside a context with repair_above (n_rows="
+                         f"{repair.n_rows}, seed={repair.seed}): the two share one sample")
     previous, ctx.measure_routed = ctx.measure_routed, (int(n_rows), int(seed), heads)
     try:
         yield model
@@ -210,7 +226,8 @@ def sampled_expert_fidelity_of(model: nn.Module, item: int = 0) -> ExpertFidelit
 
 
 @contextlib.contextmanager
-def fixed_routes(model: nn.Module, table, precisions=None):
+def fixed_routes(model: nn.Module, table, precisions=None, *, repair_above: Optional[float] = None, n_rows: int = 512,
+                 seed: int = 0):
     """While active, the hard-routing (Eval) processors of `model` (patched with apply_vorta_transformer) launch the (L, H)
     expert `table` (0 full attention, 1 coreset, 2 sliding tile; e.g. `routes_from_fidelity`'s): every layer is routed by
     `HeadRouting.from_expert_ids(table[layer])`, with host counts, so an expert no head has launches nothing.  The routers'
@@ -221,10 +238,34 @@ def fixed_routes(model: nn.Module, table, precisions=None):
     precisions: an (L, H) table of GLOBAL precision tier ids (0 native, 1 fp8pv, 2 i8pv; `measured_precisions_of(model)`'s):
     every head runs its expert in that tier (`routed.routed_attention_tiers`), whatever the process precision would have
     chosen for it.  ValueError for an id outside 0..2 and for a tier the process precision does not offer
-    (`routed.TIERS_OF_PRECISION`, read when the context is entered).  None: every head in the process precision, as ever."""
+    (`routed.TIERS_OF_PRECISION`, read when the context is entered).  None: every head in the process precision, as ever.
+    repair_above: a bound >= 0 (None: nothing below applies, every forward launches what it launches today).  A reused table
+    has no error bound of its own; with one, every forward VERIFIES what it launched on `n_rows` sampled video rows per head
+    (`routed.sample_rows(S, n_rows, seed)`, the table shared with `routed_fidelity(model)`) and re-runs every head further than
+    `repair_above` from dense attention, dense in the input dtype, in the same forward (`routed.routed_attention_repaired`;
+    `repair_routes` is the rule).  The table is placed in DEVICE lists once per context entry and layer; a repaired head stays
+    on full attention in the input dtype until the context exits (entering again starts from the table).
+    `repaired_routes_of(model)` reads the latest forward's tables.  Refused by name: a negative or NaN bound; an 8-bit process
+    precision without `precisions=` (the bound is on what is launched, so the routes must name the tier of every launch);
+    sequence parallelism."""
     ctx = context_of(model)
     if ctx.plan is None:
         raise ValueError("fixed_routes: the model was not patched with apply_vorta_transformer")
+    bound = _check_repair_above("fixed_routes", repair_above)
+    if bound is not None:
+        from ..routed import precision_of
+        if int(n_rows) < 1:
+            raise ValueError(f"fixed_routes: n_rows={n_rows} (at least 1: without a sampled row every error reads 0)")
+        if precisions is None and precision_of(None) != "native":
+            raise ValueError(f"fixed_routes: repair_above under the 8-bit process precision {precision_of(None)!r} needs tier "
+                             "routes: give precisions= (measured_precisions_of(model)); a bound on what is launched has to route "
+                             "over what is launched")
+        if ctx.measure_routed is not None and ctx.measure_routed[:2] != (int(n_rows), int(seed)):
+            raise ValueError(f"fixed_routes(repair_above=..., n_rows={n_rows}, seed={seed}) inside routed_fidelity(n_rows="
+                             f"{ctx.measure_routed[0]}, seed={ctx.measure_routed[1]}): the two share one sample")
+        if ctx.measure_experts is not None:
+            raise ValueError("fixed_routes(repair_above=...) inside sampled_expert_fidelity: the per-expert sink does not go "
+                             "with a repair")
     tier_table = None
     if precisions is not None:
         from ..routed import tiers_of
@@ -255,10 +296,65 @@ def fixed_routes(model: nn.Module, table, precisions=None):
         raise NotImplementedError("fixed_routes: routing by a table does not run under sequence parallelism")
     previous, ctx.fixed_routes = ctx.fixed_routes, [[int(x) for x in row] for row in t.tolist()]
     previous_tiers, ctx.fixed_precisions = ctx.fixed_precisions, tier_table
+    previous_repair = ctx.route_repair
+    if bound is not None:
+        ctx.route_repair = RouteRepair(bound, int(n_rows), int(seed))
     try:
         yield model
     finally:
         ctx.fixed_routes, ctx.fixed_precisions = previous, previous_tiers
+        if bound is not None:
+            ctx.route_repair, ctx.latest_route_repair = previous_repair, ctx.route_repair
+
+
+@dataclass(eq=False)
+class RouteRepair:
+    """The state of one context with `repair_above`: the bound, the sample, per layer the device tables a `fixed_routes`
+    table was placed in (they hold the repairs until the context exits) and the record of the latest forward's call"""
+    bound: float
+    n_rows: int = 512
+    seed: int = 0
+    tables: Dict[int, Any] = field(default_factory=dict)    # layer -> routed.RepairableRoutes (fixed_routes)
+    latest: Dict[int, Any] = field(default_factory=dict)    # layer -> routed.RepairRecord of the latest forward
+
+    def rows(self, latent_shape, device) -> torch.Tensor:
+        from ..routed import sample_rows
+        S = 1
+        for x in latent_shape:
+            S *= int(x)
+        return sample_rows(S, min(self.n_rows, S), self.seed, device)
+
+    def fixed_tables(self, layer: int, experts, tiers, device):
+        """the layer's rows of a `fixed_routes` table as device tables, built once per context entry: under one `native`
+        tier without `tiers` (the global tier ids of `precisions=`), else over the tiers the row names and `native`, the
+        cheapest first as `fixed_routes` launches them"""
+        if layer not in self.tables:
+            from ..ops import TIER_NAMES
+            from ..routed import HeadRouting, RepairableRoutes
+            i32 = lambda x: torch.tensor(x, dtype=torch.int32).to(device)  # noqa: E731
+            if tiers is None:
+                routing = HeadRouting.from_expert_ids(experts, device)
+                made = RepairableRoutes(("native",), i32(list(experts)), None, routing.lists.view(1, 3, len(experts)),
+                                        i32([routing.counts_host]))
+            else:
+                order = sorted(set(tiers) | {0}, reverse=True)
+                per = [HeadRouting.from_expert_ids([e if p == t else -1 for e, p in zip(experts, tiers)], device) for t in order]
+                made = RepairableRoutes(tuple(TIER_NAMES[t] for t in order), i32(list(experts)),
+                                        i32([order.index(t) for t in tiers]), torch.stack([r.lists for r in per]),
+                                        i32([r.counts_host for r in per]))
+            self.tables[layer] = made
+        return self.tables[layer]
+
+    def file(self, layer: int, record) -> None:
+        self.latest[layer] = record
+
+
+def _check_repair_above(who: str, repair_above) -> Optional[float]:
+    if repair_above is None:
+        return None
+    if isinstance(repair_above, (bool, str)) or not float(repair_above) >= 0:
+        raise ValueError(f"{who}: repair_above={repair_above!r} (a bound >= 0, or None: a negative or NaN bound keeps no head)")
+    return float(repair_above)
 
 
 @dataclass(eq=False)
@@ -269,6 +365,7 @@ class MeasuredRoutes:
     refresh_every: int = 1
     forwards: int = 0
     filed: Dict[int, list] = field(default_factory=dict)
+    repairable: Dict[int, Any] = field(default_factory=dict)   # layer -> routed.RepairableRoutes of `filed` (stored_repairable)
 
     def begin_forward(self) -> bool:
         """counts a forward; True where it measures: forwards 0, k, 2k, ... of the context"""
@@ -278,6 +375,7 @@ class MeasuredRoutes:
 
     def file(self, layer: int, entries: list) -> None:
         self.filed[layer] = entries
+        self.repairable.pop(layer, None)
 
     def stored_routing(self, layer: int):
         """the device lists and counts the latest measuring forward stored for `layer`, as a HeadRouting: nothing is launched"""
@@ -288,7 +386,22 @@ class MeasuredRoutes:
                                "measurements (the latest measuring forward did not run this layer's self-attention)")
         if len(entries[0]) > 4:
             raise RuntimeError(f"measured_routes: layer {layer} stored routes over precision tiers (stored_tier_routing)")
-        return HeadRouting.from_device(entries[0][1], entries[0][2])
+        return HeadRouting.from_device(entries[0][1], entries[0][2], entries[0][0])
+
+    def stored_repairable(self, layer: int):
+        """the joint device tables the latest measuring forward stored for `layer`, routed over precision tiers, as ONE
+        routed.RepairableRoutes -- made once per measurement, so that what a forward repairs in place (the caller's tier index
+        included) is what the next one launches"""
+        from ..routed import RepairableRoutes
+        if layer not in self.repairable:
+            ids, lists, counts, _, data = self.filed[layer][0]
+            from ..ops import TIER_NAMES
+            index = torch.zeros_like(data["tier_ids"])
+            for i, name in enumerate(data["tiers"]):
+                index = torch.where(data["tier_ids"] == TIER_NAMES.index(name), i, index)
+            self.repairable[layer] = RepairableRoutes(tuple(data["tiers"]), ids, index.to(torch.int32), lists, counts,
+                                                      data["tier_ids"])
+        return self.repairable[layer]
 
     def stores_tiers(self, layer: int) -> bool:
         """whether the latest measuring forward routed `layer` over precision tiers (a 5-tuple in the sink)"""
@@ -306,7 +419,7 @@ class MeasuredRoutes:
 @contextlib.contextmanager
 def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
                     n_rows: int = 512, seed: int = 0, refresh_every: int = 1, covers_precision: bool = False,
-                    tier_cost: Optional[Mapping] = None):
+                    tier_cost: Optional[Mapping] = None, repair_above: Optional[float] = None):
     """While active, every non-teacher forward of `model` (patched with apply_vorta_transformer, hard-routing Eval processors)
     routes each layer by a MEASUREMENT of that layer on its own q, k, v, held per prompt, per layer and per step, without a
     router checkpoint and without a host read (`routed.route_by_fidelity`: `n_rows` sampled video rows per head,
@@ -330,8 +443,19 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     routes.  The routers' routes, `tau_sparse` (a forward may leave it out) and `head_routing` are not consulted; teacher
     forwards stay dense.  Inside `routed_fidelity(model)` with the same (n_rows, seed) -- the two share one sample -- that
     record's `expert` reports the measured routes.  Outside the context nothing changes.
+    `repair_above=b` (None: nothing of this applies): every non-teacher forward in the context -- the measuring ones and
+    the ones that launch stored routes -- VERIFIES every routed self-attention call on the context's sample (`n_rows`, `seed`)
+    and re-runs every head whose launched output is further than b from dense attention, dense in the input dtype, in the
+    same forward (`routed.routed_attention_repaired`; `repair_routes` is the rule).  The repair is written into the stored
+    device tables: the forwards up to the next measurement launch a repaired head dense, and a measuring forward writes fresh
+    tables.  The bound then covers what was LAUNCHED on the sampled rows -- stale routes between two measurements and the
+    8-bit precision of the launches included -- where `max_rel_error` covers the candidates of a measuring forward; under
+    `max_flops_share` it is the only error bound there is.  `repaired_routes_of(model)` reads the latest forward's tables;
+    `measured_routes_of(model)` then reports the experts after the repairs.
     Refused by name: a model that was not patched; both rules or neither; nesting with `fixed_routes`, `sampled_expert_fidelity`
-    or another `measured_routes`, either way round; sequence parallelism (NotImplementedError, as `fixed_routes`)."""
+    or another `measured_routes`, either way round; sequence parallelism (NotImplementedError, as `fixed_routes`); a negative or
+    NaN `repair_above`; `repair_above` under an 8-bit process precision without `covers_precision=True` (the bound is on what
+    is launched, so the routes must name the tier of every launch)."""
     from ..routed import ROUTE_RULE_MODES, RouteRule
     ctx = context_of(model)
     if ctx.plan is None:
@@ -370,12 +494,23 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     from ..ulysses import SP_STATE
     if SP_STATE.enabled:
         raise NotImplementedError("measured_routes: routing by a measurement does not run under sequence parallelism")
-    ctx.measured_routes = MeasuredRoutes(RouteRule(mode, value, int(n_rows), int(seed), bool(covers_precision), tier_cost),
+    bound = _check_repair_above("measured_routes", repair_above)
+    if bound is not None:
+        from ..routed import precision_of
+        if not covers_precision and precision_of(None) != "native":
+            raise ValueError(f"measured_routes: repair_above under the 8-bit process precision {precision_of(None)!r} needs tier "
+                             "routes: give covers_precision=True; a bound on what is launched has to route over what is launched")
+    ctx.measured_routes = MeasuredRoutes(RouteRule(mode, value, int(n_rows), int(seed), bool(covers_precision), tier_cost, bound),
                                          int(refresh_every))
+    previous_repair = ctx.route_repair
+    if bound is not None:
+        ctx.route_repair = RouteRepair(bound, int(n_rows), int(seed))
     try:
         yield model
     finally:
         ctx.measured_routes, ctx.latest_measured_routes = None, ctx.measured_routes
+        if bound is not None:
+            ctx.route_repair, ctx.latest_route_repair = previous_repair, ctx.route_repair
 
 
 def measured_routes_of(model: nn.Module, item: int = 0) -> Tuple[torch.Tensor, ExpertFidelity]:
@@ -391,6 +526,32 @@ def measured_routes_of(model: nn.Module, item: int = 0) -> Tuple[torch.Tensor, E
                            "hard-routing (Eval) processors")
     entries = [measured.filed[layer][item] for layer in sorted(measured.filed)]
     return torch.stack([e[0] for e in entries]), stack_fidelity(e[3] for e in entries)
+
+
+def repaired_routes_of(model: nn.Module) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(rel, state, experts, tiers) of the model's latest forward inside a context with `repair_above`
+    (`measured_routes(..., repair_above=b)`, `fixed_routes(..., repair_above=b)`), each (L, H) on the device, layers in block
+    order: `rel` float32, the error of every head AS CHECKED (as launched, before the repair; NaN for a head that was not
+    checked); `state` int32, 0 not checked (its launch is full attention in the input dtype), 1 kept, 2 repaired by that
+    forward; `experts` int32, the head -> expert table AFTER the repair, and `tiers` int32, the GLOBAL precision tier ids
+    (0 native, 1 fp8pv, 2 i8pv) after it.  The two tables are the live ones: read them before the next forward runs."""
+    from ..ops import TIER_NAMES
+    ctx = context_of(model)
+    repair = ctx.route_repair if ctx.route_repair is not None else ctx.latest_route_repair
+    if repair is None or not repair.latest:
+        raise RuntimeError("repaired_routes_of: no forward of this model has run inside measured_routes(model, ..., "
+                           "repair_above=...) or fixed_routes(model, ..., repair_above=...) with hard-routing (Eval) processors")
+    records = [repair.latest[layer] for layer in sorted(repair.latest)]
+    tiers = []
+    for r in records:
+        routes = r.routes
+        if routes.tier_index is None:
+            tiers.append(torch.zeros_like(routes.expert_ids))
+        else:
+            ids = torch.tensor([TIER_NAMES.index(name) for name in routes.tiers], dtype=torch.int32).to(routes.expert_ids.device)
+            tiers.append(ids[routes.tier_index.long()])
+    return (torch.stack([r.rel for r in records]), torch.stack([r.state_of_head for r in records]),
+            torch.stack([r.routes.expert_ids for r in records]), torch.stack(tiers))
 
 
 def measured_precisions_of(model: nn.Module, item: int = 0) -> torch.Tensor:
@@ -570,6 +731,106 @@ def routes_from_fidelity_tiers(fids, max_rel_error: Optional[float] = None, geom
             t, e = (T - 1, 0) if best is None else (best[1], -best[2])
             experts[layer, h], tiers[layer, h] = e, ids[t]
     return experts.reshape(shape), tiers.reshape(shape)
+
+
+class RepairedRoutes(NamedTuple):
+    """`repair_routes`: the tables of one layer after the rule, all int64 on the CPU (rel float32)"""
+    expert_of_head: torch.Tensor   # (H,): as given, a repaired head 0
+    tier_of_head: torch.Tensor     # (H,) caller's tier indices: as given (zeros for None), a repaired head `exact_tier`
+    lists: torch.Tensor            # (n_tiers, 3, H): ascending heads per (tier, expert); -1 at and past the count
+    counts: torch.Tensor           # (n_tiers, 3)
+    repair_list: torch.Tensor      # (H,): ascending heads repaired by THIS call; -1 at and past the count
+    repair_count: int
+    state_of_head: torch.Tensor    # (H,): 0 not checked, 1 kept, 2 repaired
+    rel: torch.Tensor              # (H,) float32: the error as checked; NaN for a head that was not checked
+
+
+REPAIR_NOT_CHECKED, REPAIR_KEPT, REPAIR_REPAIRED = 0, 1, 2
+
+
+def _rel_error_float32(sq_err: torch.Tensor, sq_ref: torch.Tensor) -> list:
+    """`SampledFidelity.rel_error` of CPU float32 (H,) tensors as Python floats, with BOTH operations correctly rounded in
+    float32 and the zero rules of `csrc/route_rel_error.h`.  Element by element in numpy float32, whose divide and square root
+    are the IEEE ones: a vectorised `torch.sqrt` on the host may be a math library's, good to an ulp and not to the bit, and a
+    head whose error sits on the bound must fall on the same side on the host and on the device."""
+    import numpy as np
+    err, ref = sq_err.numpy().astype(np.float32), sq_ref.numpy().astype(np.float32)
+    with np.errstate(all="ignore"):
+        rel = np.sqrt(np.divide(err, ref, dtype=np.float32), dtype=np.float32)
+    zero = ref == 0
+    rel = np.where(zero & (err == 0), np.float32(0), rel)
+    rel = np.where(zero & (err > 0), np.float32(np.inf), rel)
+    return [float(x) for x in rel]
+
+
+def repair_routes(expert_of_head, tier_of_head, n_tiers: int, exact_tier: int, sq_ref, sq_err,
+                  repair_above: float) -> RepairedRoutes:
+    """Which heads of one layer, AS LAUNCHED, are further than `repair_above` from dense attention on the sampled rows, and the
+    routes without them.  `expert_of_head` (H,): 0 / 1 / 2, -1 = no list names the head; `tier_of_head` (H,): the caller's tier
+    index of every head, None for one tier; `exact_tier`: the index of the tier whose full attention is the reference
+    (`native`); `sq_ref`, `sq_err` (H,): the fields of the `ops.SampledFidelity` the launches were verified by.
+    The rule, per head.  A head with expert -1, or already at (expert 0, `exact_tier`), is NOT CHECKED and kept as it is.
+    Every other head is checked: rel = `SampledFidelity.rel_error` in float32 (a correctly rounded divide and square root;
+    sq_ref == 0 gives 0 where sq_err == 0 and inf where sq_err > 0); it is KEPT iff rel <= float32(repair_above).  NaN meets
+    no bound: a NaN record, and a head the measurement left out, are repaired.  A head that is not kept is REPAIRED: it
+    becomes (expert 0, `exact_tier`).  Applied again to its own output with the same record the rule repairs nothing.
+    ValueError for n_tiers outside 1..3, exact_tier outside 0..n_tiers-1, a NaN or negative bound, 0 or more than 1024
+    heads, tables of other shapes, an expert outside -1..2, a tier outside 0..n_tiers-1 and a missing `tier_of_head` with
+    more than one tier.
+    This function is the definition: `ops.route_repair` (vorta_route_repair) applies it on the device, in place."""
+    n_tiers, exact_tier = int(n_tiers), int(exact_tier)
+    if not 1 <= n_tiers <= 3:
+        raise ValueError(f"repair_routes: n_tiers={n_tiers} (1 to 3)")
+    if not 0 <= exact_tier < n_tiers:
+        raise ValueError(f"repair_routes: exact_tier={exact_tier} (0 to n_tiers-1 = {n_tiers - 1})")
+    if repair_above is None or not float(repair_above) >= 0:
+        raise ValueError(f"repair_routes: repair_above={repair_above} (a bound >= 0)")
+    experts = torch.as_tensor(expert_of_head).detach().cpu()
+    H = experts.numel()
+    if experts.dim() != 1 or experts.is_floating_point() or not 1 <= H <= 1024:
+        raise ValueError("repair_routes: expert_of_head: an integer table (H,) of 1 to 1024 heads (the tables of ONE layer)")
+    if tier_of_head is None:
+        if n_tiers != 1:
+            raise ValueError(f"repair_routes: tier_of_head=None with n_tiers={n_tiers}: only one tier goes without the table")
+        tiers = torch.zeros(H, dtype=torch.int64)
+    else:
+        tiers = torch.as_tensor(tier_of_head).detach().cpu()
+        if tiers.is_floating_point() or tuple(tiers.shape) != (H,):
+            raise ValueError(f"repair_routes: tier_of_head: an integer table ({H},), got {tuple(tiers.shape)} {tiers.dtype}")
+    experts, tiers = experts.long().clone(), tiers.long().clone()
+    if bool(((experts < -1) | (experts > 2)).any()):
+        raise ValueError("repair_routes: expert ids are -1 (no list), 0 (full), 1 (coreset), 2 (sliding tile)")
+    if bool(((tiers < 0) | (tiers >= n_tiers)).any()):
+        raise ValueError(f"repair_routes: tier indices are 0 to n_tiers-1 = {n_tiers - 1}")
+    ref, err = (torch.as_tensor(x).detach().cpu().float() for x in (sq_ref, sq_err))
+    if tuple(ref.shape) != (H,) or tuple(err.shape) != (H,):
+        raise ValueError(f"repair_routes: sq_ref and sq_err ({H},), got {tuple(ref.shape)} and {tuple(err.shape)}")
+    bound = float(torch.tensor(float(repair_above), dtype=torch.float32))  # the comparison is float32's
+    rel_all = _rel_error_float32(err, ref)
+    state = torch.zeros(H, dtype=torch.int64)
+    rel = torch.full((H,), float("nan"), dtype=torch.float32)
+    repaired = []
+    for h in range(H):
+        e, t = int(experts[h]), int(tiers[h])
+        if e < 0 or (e == 0 and t == exact_tier):
+            continue
+        rel[h] = rel_all[h]
+        if rel_all[h] <= bound:  # (NaN meets no bound)
+            state[h] = REPAIR_KEPT
+            continue
+        state[h] = REPAIR_REPAIRED
+        experts[h], tiers[h] = 0, exact_tier
+        repaired.append(h)
+    lists = torch.full((n_tiers, 3, H), -1, dtype=torch.int64)
+    counts = torch.zeros((n_tiers, 3), dtype=torch.int64)
+    for h in range(H):
+        e, t = int(experts[h]), int(tiers[h])
+        if e >= 0:
+            lists[t, e, counts[t, e]] = h
+            counts[t, e] += 1
+    repair_list = torch.full((H,), -1, dtype=torch.int64)
+    repair_list[:len(repaired)] = torch.tensor(repaired, dtype=torch.int64)
+    return RepairedRoutes(experts, tiers, lists, counts, repair_list, len(repaired), state, rel)
 
 
 def evaluate_routing(experts_or_scores: torch.Tensor, fid: Union[ExpertFidelity, SampledFidelity], geometry: Geometry,

@@ -32,6 +32,9 @@ class HeadRouting:
     # ulysses/engine.py split_placement): (one-entry int32 device list with the head, first query token, end); such a
     # head is not in lists[0]
     partials: Optional[List[Tuple[torch.Tensor, int, int]]] = None
+    # the int32 (H,) head -> expert table on the device the lists were built from, where the maker has one: what
+    # `routed_attention_repaired` rewrites in place beside the lists (None: the launches never read it)
+    expert_ids: Optional[torch.Tensor] = None
 
     @staticmethod
     def from_expert_ids(expert_of_head: Sequence[int], device, q_ranges: Optional[dict] = None) -> "HeadRouting":
@@ -54,8 +57,8 @@ class HeadRouting:
         return HeadRouting(lists.to(device), counts, None, partials)
 
     @staticmethod
-    def from_device(lists: torch.Tensor, counts: torch.Tensor) -> "HeadRouting":
-        return HeadRouting(lists, None, counts)
+    def from_device(lists: torch.Tensor, counts: torch.Tensor, expert_ids: Optional[torch.Tensor] = None) -> "HeadRouting":
+        return HeadRouting(lists, None, counts, None, expert_ids)
 
     @staticmethod
     def every_head_everywhere(H: int, device) -> "HeadRouting":
@@ -676,8 +679,13 @@ class RouteRule:
     seed: int = 0
     covers_precision: bool = False       # route over (precision tier, expert) pairs of the process precision: `tiers()`
     tier_cost: Optional[dict] = None     # tier -> cost of a FLOP there; None: DEFAULT_TIER_COST
+    # verify what every call launched on the sampled rows and re-run the heads further than this from dense attention
+    # (`routed_attention_repaired`); None: nothing is verified.  The patch layer reads it; `route()` does not
+    repair_above: Optional[float] = None
 
     def __post_init__(self):
+        if self.repair_above is not None and not float(self.repair_above) >= 0:
+            raise ValueError(f"RouteRule: repair_above={self.repair_above} (a bound >= 0, or None)")
         if self.mode not in ROUTE_RULE_MODES or int(self.n_rows) < 1:
             raise ValueError(f"RouteRule: mode={self.mode!r} (one of {ROUTE_RULE_MODES}), n_rows={self.n_rows} (at least 1)")
         if self.covers_precision and self.mode != ROUTE_RULE_MODES[0]:
@@ -1061,6 +1069,137 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             done.record(st)
         cur.wait_event(done)
     return measured(out)
+
+
+@dataclass(eq=False)
+class RepairableRoutes:
+    """The device route tables of one layer in the form `routed_attention_repaired` verifies and vorta_route_repair rewrites
+    IN PLACE: the tiers' names in launch order, the int32 head -> expert (H,) and head -> tier INDEX (H,; None with the single
+    tier) tables, and the contiguous (n_tiers,3,H) lists and (n_tiers,3) counts the launches read.  `routings` are views of
+    the lists and counts: a repair shows in the next launch, and in a captured graph's replay."""
+    tiers: Tuple[str, ...]
+    expert_ids: torch.Tensor
+    tier_index: Optional[torch.Tensor]
+    lists: torch.Tensor
+    counts: torch.Tensor
+    tier_ids: Optional[torch.Tensor] = None              # a `TierRoutes`' GLOBAL ids: kept in step with `tier_index`
+
+    @property
+    def routings(self) -> Dict[str, "HeadRouting"]:
+        return {name: HeadRouting.from_device(self.lists[i], self.counts[i]) for i, name in enumerate(self.tiers)}
+
+    @staticmethod
+    def from_routes(routes, precision: str = "native") -> "RepairableRoutes":
+        """of a `TierRoutes`, of a (HeadRouting.from_device, expert_ids) pair under the single `native` tier (a HeadRouting
+        that carries its `expert_ids` goes alone), or of a RepairableRoutes (itself).  `precision`: the precision a single
+        routing would be launched in: an 8-bit one is refused by name (a bound on what is launched has to route over what is
+        launched)."""
+        if isinstance(routes, RepairableRoutes):
+            made = routes
+        elif isinstance(routes, TierRoutes):
+            names = tuple(ops.TIER_NAMES[ops.tier_id(t)] for t in routes.routings)
+            index = torch.zeros_like(routes.tier_ids)
+            for i, name in enumerate(names):  # the global id -> the caller's index, on the device
+                index = torch.where(routes.tier_ids == ops.TIER_NAMES.index(name), i, index)
+            made = RepairableRoutes(names, routes.expert_ids, index.to(torch.int32), routes.lists, routes.counts,
+                                    routes.tier_ids)
+        else:
+            routing = expert_ids = None
+            if isinstance(routes, HeadRouting):
+                routing, expert_ids = routes, routes.expert_ids
+                if expert_ids is None and routes.counts_dev is not None:  # (derived from the lists, on the device)
+                    expert_ids = _expert_ids(routes, routes.lists.shape[-1], routes.lists.device)
+            elif isinstance(routes, (tuple, list)) and len(routes) == 2:
+                routing, expert_ids = routes
+            if not isinstance(routing, HeadRouting) or not torch.is_tensor(expert_ids):
+                raise ValueError("routed_attention_repaired: routes are a TierRoutes, a RepairableRoutes or a "
+                                 "(HeadRouting.from_device(lists, counts), expert_ids) pair")
+            if routing.counts_dev is None or routing.partials:
+                raise ValueError("routed_attention_repaired: the routes are repaired on the device: a HeadRouting.from_device "
+                                 "(device counts, no heads split by query range)")
+            H = expert_ids.numel()
+            made = RepairableRoutes(("native",), expert_ids, None, routing.lists.view(1, 3, H), routing.counts_dev.view(1, 3))
+        if made.tier_index is None and precision != "native":
+            raise ValueError(f"routed_attention_repaired: under the 8-bit precision {precision!r} the routes must be tier "
+                             "routes (measured_routes(covers_precision=True), route_by_fidelity(tiers=...) or "
+                             "fixed_routes(precisions=...)): 'auto8' is not a tier name, and a bound on what is launched has "
+                             "to route over what is launched")
+        if "native" not in made.tiers:
+            raise ValueError(f"routed_attention_repaired: the tiers {made.tiers} must include 'native': a repaired head runs full "
+                             "attention in the input dtype")
+        return made
+
+
+class RepairRecord(NamedTuple):
+    """`routed_attention_repaired`: what was verified and what was done about it, all on the device"""
+    fidelity: "ops.SampledFidelity"   # the rows AS LAUNCHED, before the repair
+    state_of_head: torch.Tensor       # int32 (H,): 0 not checked, 1 kept, 2 repaired
+    rel: torch.Tensor                 # float32 (H,): the error as checked, NaN for a head that was not checked
+    repair_list: torch.Tensor         # int32 (H,): the heads repaired by this call, ascending; entries past the count unwritten
+    repair_count: torch.Tensor        # int32 (1,)
+    routes: Optional[RepairableRoutes] = None   # the tables the call verified, as they stand after the repair
+
+
+def routed_attention_repaired(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routes, geom: RoutedGeometry, *,
+                              repair_above: Optional[float], rows=None, model: str, text_len: int = 0, text_valid: int = 0,
+                              out: Optional[torch.Tensor] = None, scale: Optional[float] = None, fp8=None,
+                              operands: Optional[Dict[str, AttnOperands]] = None, record: Optional[list] = None,
+                              **kw) -> Tuple[torch.Tensor, Optional[RepairRecord]]:
+    """A routed call that VERIFIES what it launched on sampled rows and re-runs the heads over a stated error, in one forward
+    and without a host read.  `routes`: a `TierRoutes`, a `RepairableRoutes`, or a (HeadRouting.from_device, expert_ids) pair,
+    which runs under the single `native` tier.  `rows`: the sampled video rows, as `routed_attention(fidelity_rows=...)`.
+    operands: tier -> AttnOperands prepared already FOR THESE q, k, v (`TierRoutes.operands` of a measurement on them), as
+    `routed_attention_tiers` takes them.
+    (a) The routings are launched as `routed_attention_tiers` / `routed_attention` launch them, with a fidelity sink on
+    `rows`.  A head whose launch is the reference itself -- full attention in the input dtype -- is not measured: the native
+    tier measures its sparse heads, an 8-bit tier every head.  (b) `ops.route_repair` on that record: a checked head with
+    rel > repair_above (or NaN) becomes (expert 0, native) in the route tables, IN PLACE -- later calls with the same tables
+    launch it dense.  (c) One dense launch in the input dtype over the repaired heads, with the device count, writes them into
+    the same `out`: the arguments of `routed_attention`'s expert 0, Hunyuan's text rows included; no coreset selection runs
+    for it, and with a zero count its workgroups exit at once.
+    Returns (out, RepairRecord).  On the sampled rows no head leaves the call further than `repair_above` from dense
+    attention; the repaired heads are dense launches with their own key cut.  Graph-capturable once the geometry's tables are
+    built.  `repair_above=None`: the routings are launched as today, nothing more; returns (out, None).
+    ValueError by name for tiers without `native`, for a single routing under an 8-bit precision (`fp8`; None: the process
+    precision), and for a negative or NaN bound."""
+    if repair_above is not None and not float(repair_above) >= 0:
+        raise ValueError(f"routed_attention_repaired: repair_above={repair_above} (a bound >= 0, or None)")
+    rr = RepairableRoutes.from_routes(routes, "native" if repair_above is None else precision_of(fp8))
+    if out is None:
+        out = torch.empty_like(q)
+    common = dict(model=model, text_len=text_len, text_valid=text_valid, out=out, scale=scale, record=record, **kw)
+    single = rr.tier_index is None
+    if repair_above is None:
+        if single:
+            routed_attention(q, k, v, HeadRouting.from_device(rr.lists[0], rr.counts[0]), geom, fp8=fp8, **common)
+        else:
+            routed_attention_tiers(q, k, v, rr.routings, geom, operands=operands, **common)
+        return out, None
+    records: list = []
+    for name, routing in rr.routings.items():
+        native = name == "native"
+        routed_attention(q, k, v, routing, geom, fp8=False if native else name,
+                         operands=None if operands is None else operands.get(name), fidelity=records,
+                         fidelity_rows=rows, fidelity_heads="sparse" if native else "all", **common)
+    fid = _merge_sampled(records)
+    exact = rr.tiers.index("native")
+    repair_list, repair_count, state, rel = ops.route_repair(fid.sq_ref, fid.sq_err, rr.expert_ids, rr.tier_index, rr.lists,
+                                                             rr.counts, exact_tier=exact, repair_above=float(repair_above))
+    if rr.tier_ids is not None:  # (a TierRoutes' global ids follow: every repaired head is in `native` now)
+        rr.tier_ids.masked_fill_(state == 2, ops.TIER_NAMES.index("native"))
+    hy = model == "hunyuan"
+    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
+    S, T, te, rm = geom.S, (text_len if hy else 0), (text_valid if hy else 0), geom.row_map
+    H, D = q3.shape[0], q3.shape[-1]
+    splits = int(kw.get("kv_splits") or 1)
+    dense = dict(q=q3, k=k3, v=v3, scale=scale, out=out[0] if out.dim() == 4 else out, n_q=S + T, n_kv=S + te,
+                 q_valid=S + te, tag="repair", q_rows=None if rm is None else rm[:S + T],
+                 kv_rows=None if rm is None else rm[:S + te], flops=0.0, head_list=repair_list, n_heads=H,
+                 n_heads_dev=repair_count, **(dict(n_splits=splits) if splits > 1 else {}))
+    if record is not None:
+        record.append(dense)
+    ops.attn_fwd_batch([dense])
+    return out, RepairRecord(fid, state, rel, repair_list, repair_count, rr)
 
 
 def soft_mixture_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing_score: torch.Tensor,

@@ -18,6 +18,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
                                                       -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
     vorta::route_fidelity_tiers(sq_ref, sq_err, tiers, max_rel_error, work, tier_cost)
                                                       -> (expert_of_head, tier_of_head, head_lists, head_counts, cost_share)   vorta_route_fidelity_tiers
+    vorta::route_repair(sq_ref, sq_err, expert_of_head, tier_of_head, head_lists, head_counts, exact_tier, repair_above)
+                                                      -> (repair_list, repair_count, state_of_head, rel)   mutates the four tables   vorta_route_repair
     vorta::router_route(temb, weight, bias, heads, tau) -> (scores, expert_of_head, head_lists, head_counts)
     vorta::qk_norm_rope(x, weight, eps, cos, sin, rope_tokens, across_heads) -> () mutates x
     vorta::mix_experts(x0,x1,x2, scores, out)         -> ()    mutates out
@@ -154,6 +156,26 @@ def _(sq_ref, sq_err, tiers, max_rel_error, work=None, tier_cost=None):
     i32 = dict(dtype=torch.int32)
     return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((H,), **i32), sq_ref.new_empty((T, 3, H), **i32),
             sq_ref.new_empty((T, 3), **i32), sq_ref.new_empty((1,), dtype=torch.float32))
+
+
+@torch.library.custom_op("vorta::route_repair", mutates_args=("expert_of_head", "tier_of_head", "head_lists", "head_counts"),
+                         device_types="cuda")
+def route_repair(sq_ref: torch.Tensor, sq_err: torch.Tensor, expert_of_head: torch.Tensor,
+                 tier_of_head: Optional[torch.Tensor], head_lists: torch.Tensor, head_counts: torch.Tensor, exact_tier: int,
+                 repair_above: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.route_repair on the record of one layer, sq_ref (H,) and sq_err (H,): the int32 route tables expert_of_head (H,),
+    tier_of_head (H,) or None, head_lists (n_tiers,3,H) and head_counts (n_tiers,3) are updated in place; returns the heads
+    repaired by this call int32 (H,), their count int32 (1,), the state int32 (H,) and rel float32 (H,)"""
+    return ops.route_repair(sq_ref, sq_err, expert_of_head, tier_of_head, head_lists, head_counts, exact_tier=exact_tier,
+                            repair_above=repair_above)
+
+
+@route_repair.register_fake
+def _(sq_ref, sq_err, expert_of_head, tier_of_head, head_lists, head_counts, exact_tier, repair_above):
+    H = sq_ref.shape[0]
+    i32 = dict(dtype=torch.int32)
+    return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((1,), **i32), sq_ref.new_empty((H,), **i32),
+            sq_ref.new_empty((H,), dtype=torch.float32))
 
 
 @torch.library.custom_op("vorta::router_route", mutates_args=(), device_types="cuda")
