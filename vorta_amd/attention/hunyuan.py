@@ -10,11 +10,11 @@ from typing import List, Optional, Tuple
 import torch
 
 from .. import ops
-from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import (HeadRouting, RepairableRoutes, TierRoutes, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
-                      routed_attention_repaired, routed_attention_tiers, soft_mixture_attention_autograd, tier_sink_entry)
+from ..routed import (HeadRouting, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
+                      soft_mixture_attention_autograd)
 from ..ulysses import SP_STATE, shrink_dim
+from ._eval import check_eval_input, launch_routes, refuse_under_sequence_parallel, resolve_routes
 from .coreset_select import LowresGroupInfo
 from .sliding_tile import SlidingTileDescriptor
 
@@ -298,29 +298,10 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
         self.check_input = check_input
 
     def _check_input(self, hidden_states, lowres_group_info, latent_shape, window_size, tile_size):
-        """hunyuan.py:247-272 (same conditions, same messages).  With partial geometry switched on (set_partial_geometry) the two divisibility
-        conditions fall away for a geometry that does not divide: one whole coreset window per dimension is needed, and a group
-        info built for this latent shape.  A geometry that divides is checked as ever."""
+        """hunyuan.py:247-272: attention/_eval.py `check_eval_input`"""
         if not self.check_input:
             return
-        seq_length = hidden_states.shape[1] * SP_STATE.sp_size
-        num_groups = lowres_group_info.center_indices.shape[0]
-        group_size = lowres_group_info.center_indices.shape[1] + lowres_group_info.margin_indices.shape[1]
-        if seq_length != latent_shape[0] * latent_shape[1] * latent_shape[2]:
-            raise ValueError(f"Input sequence length {seq_length} does not match latent shape {latent_shape}.")
-        if partial_geometry() and not divides(latent_shape, tile_size, lowres_group_info.window_size):
-            # a partial geometry: the group info must still be the cropped windows of THIS latent shape
-            want = coreset_numbers(latent_shape, lowres_group_info.window_size, lowres_group_info.reduction_rate)[0]
-            if num_groups != want or tuple(lowres_group_info.latent_shape) != tuple(int(x) for x in latent_shape):
-                raise ValueError(f"Low-res info {num_groups}x{group_size} was not built for latent shape {latent_shape} "
-                                 f"({want} whole windows).")
-            return
-        for t_size, l_size in zip(tile_size, latent_shape):
-            if l_size % t_size != 0:
-                raise ValueError(
-                    f"Tile size {tile_size} (dim={t_size}) does not divide latent shape {latent_shape} (dim={l_size}).")
-        if seq_length != num_groups * group_size:
-            raise ValueError(f"Input sequence length {seq_length} does not match low-res info {num_groups}x{group_size}.")
+        check_eval_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
 
     @torch.no_grad()
     def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask, image_rotary_emb,
@@ -366,82 +347,21 @@ class HunyuanVideoFlashAttnProcessorTripleEval(HunyuanVideoFlashAttnProcessor):
         assert q.shape[0] == 1, f"Batch size {q.shape[0]} is not supported for {self.__class__.__name__}."
         te = self._text_valid(attention_mask, T, flex_attn_mask_func)
         if SP_STATE.enabled:
-            if expert_fidelity is not None:
-                raise NotImplementedError("sampled_expert_fidelity: the per-expert measurement on sampled rows does not run "
-                                          "under sequence parallelism (its gather reads whole heads of one process)")
-            if route_rule is not None:
-                raise NotImplementedError("route_rule: routing by a measured error bound or FLOP budget does not run under "
-                                          "sequence parallelism (its gather reads whole heads of one process)")
-            if tier_routing is not None:
-                raise NotImplementedError("tier_routing: launching by precision tiers does not run under sequence parallelism")
-            if repair_above is not None:
-                raise NotImplementedError("repair_above: verifying and repairing launched routes does not run under sequence "
-                                          "parallelism (its dense repair launch reads whole heads of one process)")
+            refuse_under_sequence_parallel(expert_fidelity, route_rule, tier_routing, repair_above)
             from ._sp import sp_attention
             buf = sp_attention(q, k, v, T, routing_score, tau_sparse, model="hunyuan", text_valid=te,
                                lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
                                latent_shape=latent_shape, experts_host=experts_host, fidelity=fidelity,
                                fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
             return self._output(attn, buf, T)
-        # top-1 / tau dispatch on the device: no torch.nonzero host sync (hunyuan.py:612-640)
-        tier_operands = None
-        if route_rule is not None:
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            routes = route_rule.route(q, k, v, geom, model="hunyuan", text_len=T, text_valid=te)
-            if isinstance(routes, TierRoutes):
-                tier_routing, tier_operands, repairable = routes.routings, routes.operands, routes
-                if route_sink is not None:
-                    route_sink.append(tier_sink_entry(routes))
-            else:
-                head_routing, ids, fid = routes
-                repairable = (head_routing, ids)
-                if route_sink is not None:
-                    route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
-        elif tier_routing is not None:
-            tier_operands, repairable = None, tier_routing
-            if isinstance(tier_routing, RepairableRoutes):  # (the joint tables of the tiers: launched by their views)
-                tier_routing = tier_routing.routings
-        elif head_routing is None:
-            ids, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
-            head_routing = HeadRouting.from_device(lists, counts, ids)
-            repairable = head_routing
-        else:
-            repairable = head_routing
+        geometry = _torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape)
+        routes = resolve_routes(q, k, v, geometry, model="hunyuan", text_len=T, text_valid=te, routing_score=routing_score,
+                                tau_sparse=tau_sparse, head_routing=head_routing, route_rule=route_rule, route_sink=route_sink,
+                                tier_routing=tier_routing)
         buf, out = self._new_out(q)
-        if repair_above is not None:
-            if expert_fidelity is not None:
-                raise ValueError("expert_fidelity: the per-expert sink does not go with repair_above")
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            _, repaired = routed_attention_repaired(q, k, v, repairable, geom, repair_above=repair_above, rows=fidelity_rows,
-                                                    operands=tier_operands, model="hunyuan", text_len=T, text_valid=te, out=out)
-            if repair_sink is not None:
-                repair_sink.append(repaired)
-            if fidelity is not None:  # (the rows as they were BEFORE the repair: the record the repair was decided by)
-                fidelity.append(repaired.fidelity)
-            return self._output(attn, buf, T)
-        if tier_routing is not None:
-            if expert_fidelity is not None:
-                raise ValueError("expert_fidelity: the per-expert sink does not go with a launch by precision tiers")
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            fkw = {} if fidelity is None else dict(fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
-            routed_attention_tiers(q, k, v, tier_routing, geom, model="hunyuan", text_len=T, text_valid=te, out=out,
-                                   operands=tier_operands, **fkw)
-            return self._output(attn, buf, T)
-        if fidelity is not None or expert_fidelity is not None:
-            # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
-            from ..routed import routed_attention
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            routed_attention(q, k, v, head_routing, geom, model="hunyuan", text_len=T, text_valid=te, out=out,
-                             fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads,
-                                 expert_fidelity=expert_fidelity)
-            return self._output(attn, buf, T)
-        torch.ops.vorta.routed_attention(q, k, v, out, **_torch_ops.routing_args(head_routing),
-                                         **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                         model="hunyuan", text_len=T, text_valid=te)
+        launch_routes(q, k, v, out, routes, geometry, model="hunyuan", text_len=T, text_valid=te, fidelity=fidelity,
+                      fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads, expert_fidelity=expert_fidelity,
+                      repair_above=repair_above, repair_sink=repair_sink)
         return self._output(attn, buf, T)
 
 

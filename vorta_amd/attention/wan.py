@@ -8,12 +8,11 @@ from typing import List, Optional, Tuple
 import torch
 
 from .. import ops
-from .._partial import coreset_numbers, divides, partial_geometry
 from .. import torch_ops as _torch_ops  # registers torch.ops.vorta.*: what the processors launch through
-from ..routed import (HeadRouting, RepairableRoutes, TierRoutes, routed_attention_repaired, routed_attention_tiers, tier_sink_entry,
-                      dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
+from ..routed import (HeadRouting, dense_attention, dense_attention_autograd, geometry_for, qk_norm_rope_autograd,
                       soft_mixture_attention_autograd)
 from ..ulysses import SP_STATE, shrink_dim
+from ._eval import check_eval_input, launch_routes, refuse_under_sequence_parallel, resolve_routes
 from .coreset_select import LowresGroupInfo
 from .sliding_tile import SlidingTileDescriptor
 
@@ -184,29 +183,10 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         self.check_input = check_input
 
     def _check_input(self, hidden_states, lowres_group_info, latent_shape, window_size, tile_size):
-        """wan.py:168-193.  With partial geometry switched on (set_partial_geometry) the two divisibility
-        conditions fall away for a geometry that does not divide: one whole coreset window per dimension is needed, and a group
-        info built for this latent shape.  A geometry that divides is checked as ever."""
+        """wan.py:168-193: attention/_eval.py `check_eval_input`"""
         if not self.check_input:
             return
-        seq_length = hidden_states.shape[1] * SP_STATE.sp_size
-        num_groups = lowres_group_info.center_indices.shape[0]
-        group_size = lowres_group_info.center_indices.shape[1] + lowres_group_info.margin_indices.shape[1]
-        if seq_length != latent_shape[0] * latent_shape[1] * latent_shape[2]:
-            raise ValueError(f"Input sequence length {seq_length} does not match latent shape {latent_shape}.")
-        if partial_geometry() and not divides(latent_shape, tile_size, lowres_group_info.window_size):
-            # a partial geometry: the group info must still be the cropped windows of THIS latent shape
-            want = coreset_numbers(latent_shape, lowres_group_info.window_size, lowres_group_info.reduction_rate)[0]
-            if num_groups != want or tuple(lowres_group_info.latent_shape) != tuple(int(x) for x in latent_shape):
-                raise ValueError(f"Low-res info {num_groups}x{group_size} was not built for latent shape {latent_shape} "
-                                 f"({want} whole windows).")
-            return
-        for t_size, l_size in zip(tile_size, latent_shape):
-            if l_size % t_size != 0:
-                raise ValueError(
-                    f"Tile size {tile_size} (dim={t_size}) does not divide latent shape {latent_shape} (dim={l_size}).")
-        if seq_length != num_groups * group_size:
-            raise ValueError(f"Input sequence length {seq_length} does not match low-res info {num_groups}x{group_size}.")
+        check_eval_input(hidden_states, lowres_group_info, latent_shape, window_size, tile_size)
 
     @torch.no_grad()
     def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask, rotary_emb,
@@ -225,13 +205,10 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         as run against dense attention on sampled rows, routed.routed_attention); cross attention and the dense teacher file
         nothing; None: the launches of today.  expert_fidelity: likewise one `ops.ExpertFidelity` per batch item
         (routed.sampled_expert_fidelity on the same `fidelity_rows`); refused by name under sequence parallelism.
-        route_rule / route_sink: see the Hunyuan processor; a batch is routed, every item, by ITEM 0's measurement (the
-        reference's convention for scores, quoted below), so the sink receives one entry per call.  `covers_precision` and
-        `tier_routing`: see the Hunyuan processor; the operands the measurement prepared serve item 0's launches, every other
-        item converts its own.
-        repair_above / repair_sink: see the Hunyuan processor; ITEM 0 is verified and repaired, and every other item launches
-        the repaired tables -- item 0's repaired heads dense -- without a verification of its own; the sink receives one
-        record per call."""
+        route_rule / route_sink, `covers_precision`, `tier_routing`, repair_above / repair_sink: see the Hunyuan processor, and
+        attention/_eval.py for a batch: every item is routed by ITEM 0's measurement (the reference's convention for scores,
+        quoted below; one sink entry per call), item 0 alone launches on the operands the measurement prepared, and item 0
+        alone is verified and repaired (one record per call) -- every other item launches the repaired tables."""
         if encoder_hidden_states is not None or use_original_attn:
             return WanAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
                                                 rotary_emb)
@@ -242,91 +219,20 @@ class WanAttnProcessorTripleEval(WanAttnProcessor2_0):
         # take one item per launch, so a batch is a loop over its items with the same routes (the scripts run B = 1:
         # pipeline_wan.py:322-344 does CFG as two forwards)
         if SP_STATE.enabled:
-            if expert_fidelity is not None:
-                raise NotImplementedError("sampled_expert_fidelity: the per-expert measurement on sampled rows does not run "
-                                          "under sequence parallelism (its gather reads whole heads of one process)")
-            if route_rule is not None:
-                raise NotImplementedError("route_rule: routing by a measured error bound or FLOP budget does not run under "
-                                          "sequence parallelism (its gather reads whole heads of one process)")
-            if tier_routing is not None:
-                raise NotImplementedError("tier_routing: launching by precision tiers does not run under sequence parallelism")
-            if repair_above is not None:
-                raise NotImplementedError("repair_above: verifying and repairing launched routes does not run under sequence "
-                                          "parallelism (its dense repair launch reads whole heads of one process)")
+            refuse_under_sequence_parallel(expert_fidelity, route_rule, tier_routing, repair_above)
             from ._sp import sp_attention
             bufs = [sp_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], 0, routing_score, tau_sparse, model="wan",
                                  lowres_group_info=lowres_group_info, window_size=window_size, tile_size=tile_size,
                                  latent_shape=latent_shape, experts_host=experts_host, fidelity=fidelity,
                                  fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads) for b in range(B)]
             return self._output_proj(attn, bufs[0] if B == 1 else torch.cat(bufs, dim=0))
-        tier_operands = None
-        if route_rule is not None:
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            routes = route_rule.route(q[:1], k[:1], v[:1], geom, model="wan")
-            if isinstance(routes, TierRoutes):
-                tier_routing, tier_operands, repairable = routes.routings, routes.operands, routes
-                if route_sink is not None:
-                    route_sink.append(tier_sink_entry(routes))
-            else:
-                head_routing, ids, fid = routes
-                repairable = (head_routing, ids)
-                if route_sink is not None:
-                    route_sink.append((ids, head_routing.lists, head_routing.counts_dev, fid))
-        elif tier_routing is not None:
-            tier_operands, repairable = None, tier_routing
-            if isinstance(tier_routing, RepairableRoutes):  # (the joint tables of the tiers: launched by their views)
-                tier_routing = tier_routing.routings
-        elif head_routing is None:
-            ids, lists, counts = torch.ops.vorta.route_scores(routing_score, float(tau_sparse))
-            head_routing = HeadRouting.from_device(lists, counts, ids)
-            repairable = head_routing
-        else:
-            repairable = head_routing
+        geometry = _torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape)
+        routes = resolve_routes(q, k, v, geometry, model="wan", routing_score=routing_score, tau_sparse=tau_sparse,
+                                head_routing=head_routing, route_rule=route_rule, route_sink=route_sink, tier_routing=tier_routing)
         buf, out = self._new_out(q)
-        if repair_above is not None:
-            if expert_fidelity is not None:
-                raise ValueError("expert_fidelity: the per-expert sink does not go with repair_above")
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            # item 0 is verified and repaired; the tables are repaired in place, so every other item launches item 0's
-            # repaired heads dense (the convention for routes: a batch follows item 0)
-            _, repaired = routed_attention_repaired(q[:1], k[:1], v[:1], repairable, geom, repair_above=repair_above,
-                                                    rows=fidelity_rows, operands=tier_operands, model="wan", out=out[:1])
-            if repair_sink is not None:
-                repair_sink.append(repaired)
-            if fidelity is not None:  # (the rows as they were BEFORE the repair: the record the repair was decided by)
-                fidelity.append(repaired.fidelity)
-            fkw = {} if fidelity is None else dict(fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
-            for b in range(1, B):
-                routed_attention_repaired(q[b:b + 1], k[b:b + 1], v[b:b + 1], repaired.routes, geom, repair_above=None,
-                                          model="wan", out=out[b:b + 1], **fkw)
-            return self._output_proj(attn, buf)
-        if tier_routing is not None:
-            if expert_fidelity is not None:
-                raise ValueError("expert_fidelity: the per-expert sink does not go with a launch by precision tiers")
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            fkw = {} if fidelity is None else dict(fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads)
-            for b in range(B):
-                routed_attention_tiers(q[b:b + 1], k[b:b + 1], v[b:b + 1], tier_routing, geom, model="wan", out=out[b:b + 1],
-                                       operands=tier_operands if b == 0 else None, **fkw)
-            return self._output_proj(attn, buf)
-        if fidelity is not None or expert_fidelity is not None:
-            # (a list is no operator argument: the launcher behind vorta::routed_attention, directly)
-            from ..routed import routed_attention
-            geom = geometry_for(**_torch_ops.geometry_args(lowres_group_info, window_size, tile_size, latent_shape),
-                                device=q.device)
-            for b in range(B):
-                routed_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], head_routing, geom, model="wan", out=out[b:b + 1],
-                                 fidelity=fidelity, fidelity_rows=fidelity_rows, fidelity_heads=fidelity_heads,
-                                 expert_fidelity=expert_fidelity)
-            return self._output_proj(attn, buf)
-        for b in range(B):
-            torch.ops.vorta.routed_attention(q[b:b + 1], k[b:b + 1], v[b:b + 1], out[b:b + 1],
-                                             **_torch_ops.routing_args(head_routing),
-                                             **_torch_ops.geometry_args(lowres_group_info, window_size, tile_size,
-                                                                        latent_shape), model="wan")
+        launch_routes(q, k, v, out, routes, geometry, model="wan", fidelity=fidelity, fidelity_rows=fidelity_rows,
+                      fidelity_heads=fidelity_heads, expert_fidelity=expert_fidelity, repair_above=repair_above,
+                      repair_sink=repair_sink)
         return self._output_proj(attn, buf)
 
 

@@ -21,6 +21,11 @@ from ._partial import partial_geometry, set_partial_geometry  # noqa: F401  (the
 Triple = Tuple[int, int, int]
 
 
+def _fold(x: torch.Tensor) -> torch.Tensor:
+    """the (H,N,D) view the kernels take of a (1,H,N,D) or (H,N,D) tensor"""
+    return x[0] if x.dim() == 4 else x
+
+
 @dataclass
 class HeadRouting:
     """head -> expert assignment.  Either host lists (counts known on the host) or the device tables written
@@ -467,19 +472,35 @@ def sample_rows(S: int, n: int, seed: int = 0, device=None) -> torch.Tensor:
     return _SAMPLE_ROWS[key]
 
 
+def _named_heads(slot: torch.Tensor, count, head_list: torch.Tensor, H: int) -> torch.Tensor:
+    """per slot of a head list the head it names, int64 on the device without a host read: H -- one past the heads -- for a
+    slot at or past `count` (a host integer or a device count), which no launch reads"""
+    heads = head_list[:slot.numel()].long()
+    return torch.where(slot < count, heads, torch.full_like(heads, H))
+
+
 def _expert_ids(routing: "HeadRouting", H: int, device) -> torch.Tensor:
-    """head -> expert as the launches read it, int32 (H,) on the device without a host read: -1 for a head no list names
-    (slots at or past a device count are not read); a head split by query range is a full-attention head (0)"""
+    """head -> expert as the launches read it, int32 (H,) on the device without a host read: -1 for a head no list names;
+    a head split by query range is a full-attention head (0)"""
     ids = torch.full((H + 1,), -1, dtype=torch.int32, device=device)
     slot = torch.arange(H, device=device)
     for e in range(3):
         count = routing.counts_host[e] if routing.counts_host is not None else routing.counts_dev[e]
-        heads = routing.lists[e][:H].long()
-        ids.scatter_(0, torch.where(slot < count, heads, torch.full_like(heads, H)), torch.full((H,), e, dtype=torch.int32,
-                                                                                                  device=device))
+        ids.scatter_(0, _named_heads(slot, count, routing.lists[e], H), torch.full((H,), e, dtype=torch.int32, device=device))
     for hl, _, _ in routing.partials or ():
         ids.index_fill_(0, hl.long(), 0)
     return ids[:H]
+
+
+def _sample_table(rows, S: int, seed: int, device, name: str) -> torch.Tensor:
+    """`rows` -- a sample size (None: min(DEFAULT_FIDELITY_ROWS, S); `sample_rows` with `seed`) or an int32 table of video
+    tokens -- as the table; `name`: the caller's argument, for the message"""
+    if rows is None:
+        rows = min(DEFAULT_FIDELITY_ROWS, S)
+    tokens = rows if torch.is_tensor(rows) else sample_rows(S, rows, seed, device)
+    if tokens.dim() != 1 or tokens.dtype != torch.int32 or tokens.numel() > S:
+        raise ValueError(f"{name}: a sample size, or an int32 table of video tokens (routed.sample_rows)")
+    return tokens
 
 
 def _measure_routed(fidelity: list, fidelity_rows, fidelity_heads: str, q3, k3, v3, o3, routing: "HeadRouting",
@@ -490,11 +511,7 @@ def _measure_routed(fidelity: list, fidelity_rows, fidelity_heads: str, q3, k3, 
     if fidelity_heads not in FIDELITY_HEADS:
         raise ValueError(f"fidelity_heads={fidelity_heads!r}: one of {FIDELITY_HEADS}")
     H, S, rm = q3.shape[0], geom.S, geom.row_map
-    if fidelity_rows is None:
-        fidelity_rows = min(DEFAULT_FIDELITY_ROWS, S)
-    tokens = fidelity_rows if torch.is_tensor(fidelity_rows) else sample_rows(S, fidelity_rows, 0, q3.device)
-    if tokens.dim() != 1 or tokens.dtype != torch.int32 or tokens.numel() > S:
-        raise ValueError("fidelity_rows: a sample size, or an int32 table of video tokens (routed.sample_rows)")
+    tokens = _sample_table(fidelity_rows, S, 0, q3.device, "fidelity_rows")
     n = tokens.numel()
     rows = tokens if rm is None else rm.index_select(0, tokens)  # the physical rows of q and out
     q_rows = q3.index_select(1, rows)       # compact (H, n, D): the launch below has no query table
@@ -529,6 +546,34 @@ def _head_slots(heads, H: int, device) -> dict:
     if not torch.is_tensor(heads):
         heads = torch.tensor([int(h) for h in heads], dtype=torch.int32).to(device)
     return dict(head_list=heads, n_heads=heads.numel(), n_heads_dev=None)
+
+
+def _coreset_lists(q3, k3, geom: "RoutedGeometry", hy: bool, T: int, te: int, slots: dict):
+    """the coreset expert's selection for the heads of `slots`: (keep_q, drop_q, keep_k) of ops.coreset_select"""
+    S, rm = geom.S, geom.row_map
+    # key side: the same rows as the reference's packed [centres | margins] list (coreset_select.py:116-124) in
+    # group-major ascending order -- softmax does not see the order of the keys, the K/V gather does
+    gm = CORESET_KV_GROUP_MAJOR
+    pk = dict(partial=True) if geom.is_partial else {}  # + the remainder tokens, before the text (vorta_coreset_select_partial)
+    if hy:  # K matched on its own, V follows K (hunyuan.py:433-438)
+        keep_q, drop_q = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T,
+                                            row_map=rm, **pk, **slots)
+        kk = ops.coreset_select(k3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=te, row_map=rm,
+                                want_drop=False, want_keep=not gm, want_kv=gm, **pk, **slots)
+        return keep_q, drop_q, kk[2] if gm else kk[0]
+    # K and V follow Q's matching (wan.py:250-255): one selection, both lists
+    kq = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm,
+                            want_kv=gm, **pk, **slots)
+    return kq[0], kq[1], kq[2] if gm else kq[0]
+
+
+def _full_launch(geom: "RoutedGeometry", T: int, te: int, kv_splits) -> dict:
+    """the lengths and row tables of full attention over every head row -- expert 0, and the dense repair launch: every query
+    (text included), every valid key; the keys cut where `kv_splits` > 1"""
+    S, rm = geom.S, geom.row_map
+    return dict(n_q=S + T, n_kv=S + te, q_valid=S + te, q_rows=None if rm is None else rm[:S + T],
+                kv_rows=None if rm is None else rm[:S + te],
+                **(dict(n_splits=int(kv_splits)) if kv_splits and int(kv_splits) > 1 else {}))
 
 
 def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: RoutedGeometry, *, model: str,
@@ -574,17 +619,13 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
                              "precision or the routed output, not both")
     elif operands is not None:
         raise ValueError("sampled_expert_fidelity: operands= goes with precision=")
-    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
-    o3 = None if out is None else (out[0] if out.dim() == 4 else out)
+    q3, k3, v3 = _fold(q), _fold(k), _fold(v)
+    o3 = None if out is None else _fold(out)
     H, D, S, rm = q3.shape[0], q3.shape[-1], geom.S, geom.row_map
     T, te = (text_len, text_valid) if hy else (0, 0)
     if rm is None and q3.shape[1] != S + T:
         raise ValueError(f"Input sequence length {q3.shape[1] - T} does not match latent shape {geom.latent}.")
-    if rows is None:
-        rows = min(DEFAULT_FIDELITY_ROWS, S)
-    tokens = rows if torch.is_tensor(rows) else sample_rows(S, rows, seed, q3.device)
-    if tokens.dim() != 1 or tokens.dtype != torch.int32 or tokens.numel() > S:
-        raise ValueError("rows: a sample size, or an int32 table of video tokens (routed.sample_rows)")
+    tokens = _sample_table(rows, S, seed, q3.device, "rows")
     n, dev = tokens.numel(), q3.device
     sl = _head_slots(heads, H, dev)
     tabs = geom.sample_tables(te, tokens, SAMPLED_BLOCK_ROWS)
@@ -593,19 +634,7 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     q_own, q_rep, ref, low, sta = (new((H, n, D), dtype=q3.dtype, device=dev) for _ in range(5))
     mixed = new((H, n, D), dtype=q3.dtype, device=dev) if o3 is not None or precision is not None else None
     if n and sl["n_heads"]:
-        pk = dict(partial=True) if geom.is_partial else {}
-        gm = CORESET_KV_GROUP_MAJOR
-        if hy:  # K matched on its own, V follows K: `routed_attention`'s expert_lowres
-            keep_q, drop_q = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm,
-                                                **pk, **sl)
-            kk = ops.coreset_select(k3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=te, row_map=rm,
-                                    want_drop=False, want_keep=not gm, want_kv=gm, **pk, **sl)
-            keep_k = kk[2] if gm else kk[0]
-        else:
-            kq = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm, want_kv=gm,
-                                    **pk, **sl)
-            keep_q, drop_q = kq[0], kq[1]
-            keep_k = kq[2] if gm else keep_q
+        keep_q, drop_q, keep_k = _coreset_lists(q3, k3, geom, hy, T, te, sl)  # as `routed_attention`'s coreset expert
         ops.gather_sample_rows(q3, tabs.rows, dst_q=q_own, dst_qrep=q_rep, dst_out=mixed if o3 is not None else None, out=o3, win=tabs.win,
                                keep_rows=keep_q, drop_rows=drop_q, **sl)
         n_low = geom.S_low + te
@@ -628,10 +657,9 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
             ops.attn_fwd_batch(calls[i:i + ops.MAX_FUSED])
     fid = ops.expert_fidelity([ref, low, sta], mixed)
     if sl["head_list"] is not None:  # NaN for the heads no slot names (slots at or past a device count are not read)
-        slot = torch.arange(sl["n_heads"], device=dev)
         count = sl["n_heads"] if sl["n_heads_dev"] is None else sl["n_heads_dev"]
         named = torch.zeros(H + 1, dtype=torch.bool, device=dev)
-        named.index_fill_(0, torch.where(slot < count, sl["head_list"][:sl["n_heads"]].long(), torch.full_like(slot, H)), True)
+        named.index_fill_(0, _named_heads(torch.arange(sl["n_heads"], device=dev), count, sl["head_list"], H), True)
         named = named[:H]
         nan = lambda x: torch.where(named if x.dim() == 1 else named[:, None], x, torch.full_like(x, float("nan")))  # noqa: E731
         fid = fid._replace(sq_ref=nan(fid.sq_ref), max_ref=nan(fid.max_ref), sq_err=nan(fid.sq_err), max_err=nan(fid.max_err),
@@ -767,7 +795,7 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
 def _route_tiers(q, k, v, geom, native_fid, work, tiers, tier_cost, bound: float, measure_kw: dict) -> TierRoutes:
     """`route_by_fidelity(tiers=...)` after the native measurement"""
     names = [ops.TIER_NAMES[ops.tier_id(t)] for t in tiers]
-    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
+    q3, k3, v3 = _fold(q), _fold(k), _fold(v)
     operands: Dict[str, AttnOperands] = {}
     if "i8pv" in names:
         operands["i8pv"] = prepare_operands("i8pv", q3, k3, v3, measure_kw["scale"])
@@ -807,6 +835,18 @@ def _merge_sampled(records) -> "ops.SampledFidelity":
     return first
 
 
+def _launch_tiers(q, k, v, routings, geom, operands, records: Optional[list], heads_of=None, **kw) -> None:
+    """one `routed_attention` call per tier of `routings`, in their order: `fp8=` the tier (False for `native`), the tier's
+    entry of `operands`, `records` the fidelity sink of every call (None: none measures); heads_of: tier name -> its
+    `fidelity_heads` (None: the caller's keyword, if any)"""
+    for tier, routing in routings.items():
+        name = ops.TIER_NAMES[ops.tier_id(tier)]
+        if heads_of is not None:
+            kw["fidelity_heads"] = heads_of(name)
+        routed_attention(q, k, v, routing, geom, fp8=False if name == "native" else name,
+                         operands=None if operands is None else operands.get(name), fidelity=records, **kw)
+
+
 def routed_attention_tiers(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routings, geom: RoutedGeometry, *,
                            out: Optional[torch.Tensor] = None, operands: Optional[Dict[str, AttnOperands]] = None,
                            fidelity: Optional[list] = None, **kw) -> torch.Tensor:
@@ -822,11 +862,7 @@ def routed_attention_tiers(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ro
     if out is None:
         out = torch.empty_like(q)
     records: list = []
-    for tier, routing in routings.items():
-        name = ops.TIER_NAMES[ops.tier_id(tier)]
-        routed_attention(q, k, v, routing, geom, out=out, fp8=False if name == "native" else name,
-                         operands=None if operands is None else operands.get(name),
-                         fidelity=None if fidelity is None else records, **kw)
+    _launch_tiers(q, k, v, routings, geom, operands, None if fidelity is None else records, out=out, **kw)
     if fidelity is not None:
         fidelity.append(_merge_sampled(records))
     return out
@@ -894,11 +930,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         raise ValueError("fidelity= / expert_fidelity= measure the routed output `out`: they do not go with expert_outs")
     if out is None and expert_outs is None:
         out = torch.empty_like(q)
-    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
-    if expert_outs is not None:
-        o_e = [x[0] if x.dim() == 4 else x for x in expert_outs]
-    else:
-        o_e = [out[0] if out.dim() == 4 else out] * 3
+    q3, k3, v3 = _fold(q), _fold(k), _fold(v)
+    o_e = [_fold(out)] * 3 if expert_outs is None else [_fold(x) for x in expert_outs]
 
     def live(e):
         return routing.counts_host is None or routing.counts_host[e] > 0 or (e == 0 and bool(routing.partials))
@@ -910,18 +943,16 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         # (video_tokens: the sample is summed in eighths of the video tokens + the text, as the sequence-parallel send side sums it)
         operands = prepare_operands(precision_of(fp8), q3, k3, v3, scale, fp8_operands,
                                     video_tokens=S if rm is None and T > 0 else 0)
-    base = operands.kwargs(scale)
-
     split_kw = dict(n_splits=int(kv_splits)) if kv_splits and int(kv_splits) > 1 else {}
-    slot_of = routing.slot_args  # (expert, H) -> head_list / n_heads / n_heads_dev of a launch ("auto8": one of the two parts)
-    slot_part = lambda i, hl: dict(head_list=hl, n_heads=1, n_heads_dev=None)  # noqa: E731  (a head split by query range)
+    # one pass of the experts' launches: (base, slot_of, slot_part) -- the operands' keywords; (expert, H) -> head_list / n_heads /
+    # n_heads_dev of a launch; the same for part i of a head split by query range.  "auto8" makes two passes (below)
+    passes = [(operands.kwargs(scale), routing.slot_args, lambda i, hl: dict(head_list=hl, n_heads=1, n_heads_dev=None))]
 
     # ---- expert 0: full attention (hunyuan.py:136-189 / wan.py:142-145) ----
-    def expert_full():
+    def expert_full(base, slot_of, slot_part):
         calls = []
         if routing.counts_host is None or routing.counts_host[0] > 0:
-            calls.append(dict(base, out=o_e[0], n_q=S + T, n_kv=S + te, q_valid=S + te, tag="full", **split_kw,
-                              q_rows=None if rm is None else rm[:S + T], kv_rows=None if rm is None else rm[:S + te],
+            calls.append(dict(base, out=o_e[0], tag="full", **_full_launch(geom, T, te, kv_splits),
                               flops=nheads(0) * 4.0 * (S + te) ** 2 * D, **slot_of(0, H)))
         for pi, (hl, t0, t1) in enumerate(routing.partials or ()):
             # a head whose other query tokens another rank computes: every key, the query rows [t0, t1) of the VIDEO tokens;
@@ -940,29 +971,15 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         return calls
 
     # ---- expert 1: coreset attention (hunyuan.py:410-457 / wan.py:243-270) ----
-    def expert_lowres():
+    def expert_lowres(base, slot_of, slot_part):
         sl = slot_of(1, H)
-        # key side: the same rows as the reference's packed [centres | margins] list (coreset_select.py:116-124) in
-        # group-major ascending order -- softmax does not see the order of the keys, the K/V gather does
-        gm = CORESET_KV_GROUP_MAJOR
-        pk = dict(partial=True) if geom.is_partial else {}  # + the remainder tokens, before the text (vorta_coreset_select_partial)
-        if hy:  # K matched on its own, V follows K (hunyuan.py:433-438)
-            keep_q, drop_q = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T,
-                                                row_map=rm, **pk, **sl)
-            kk = ops.coreset_select(k3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=te, row_map=rm,
-                                    want_drop=False, want_keep=not gm, want_kv=gm, **pk, **sl)
-            keep_k = kk[2] if gm else kk[0]
-        else:   # K and V follow Q's matching (wan.py:250-255): one selection, both lists
-            kq = ops.coreset_select(q3, geom.latent, geom.group, geom.n_keep, tail_first=S, n_tail=T, row_map=rm,
-                                    want_kv=gm, **pk, **sl)
-            keep_q, drop_q = kq[0], kq[1]
-            keep_k = kq[2] if gm else keep_q
+        keep_q, drop_q, keep_k = _coreset_lists(q3, k3, geom, hy, T, te, sl)
         return [dict(base, out=o_e[1], n_q=geom.S_low + T, n_kv=geom.S_low + te, q_valid=geom.S_low + te, q_rows=keep_q,
                      kv_rows=keep_k, dup_rows=drop_q, n_dup_pos=geom.G, tag="lowres", **split_kw,
                      flops=nheads(1) * 4.0 * (geom.S_low + te) ** 2 * D, **sl)]
 
     # ---- expert 2: sliding-tile attention (hunyuan.py:459-507 / wan.py:272-294) ----
-    def expert_sliding():
+    def expert_sliding(base, slot_of, slot_part):
         sl = slot_of(2, H)
         if geom.is_partial:
             # always the merged form, one launch per key-list length (RoutedGeometry.sta_partial_launches)
@@ -1033,22 +1050,15 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             raise ValueError("'auto8' runs its two parts as fused grids (concurrent=False)")
         parts = [ops.split_heads(operands.tail, **routing.slot_args(e, H)) if on else None for e, (_, on) in enumerate(experts)]
         pparts = [ops.split_heads(operands.tail, hl, 1) for hl, _, _ in routing.partials or ()]
-        for which, b in ((0, base), (1, operands.tail_kwargs(scale))):  # int8-score heads, then 16-bit-score heads
-            base = b
-            slot_of = lambda e, H_, which=which: parts[e][which]  # noqa: E731
-            slot_part = lambda i, hl, which=which: pparts[i][which]  # noqa: E731
-            calls = [c for fn, on in experts if on for c in fn()]
+        passes = [(b, lambda e, H_, which=which: parts[e][which], lambda i, hl, which=which: pparts[i][which])
+                  for which, b in ((0, passes[0][0]), (1, operands.tail_kwargs(scale)))]  # int8-score heads, then 16-bit-score heads
+    if not concurrent:
+        for one in passes:
+            calls = [c for fn, on in experts if on for c in fn(*one)]
             if fused:
                 launch_fused(calls)
             else:
                 launch(calls)
-        return measured(out)
-    if not concurrent:
-        calls = [c for fn, on in experts if on for c in fn()]
-        if fused:
-            launch_fused(calls)
-        else:
-            launch(calls)
         return measured(out)
     # the experts are independent: fork them onto side streams, join before returning (so every later use of
     # q,k,v,out on the current stream is ordered after them)
@@ -1060,11 +1070,11 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         if not on:
             continue
         if st is None:
-            launch(fn())
+            launch(fn(*passes[0]))
             continue
         st.wait_event(fork)
         with torch.cuda.stream(st):
-            launch(fn())
+            launch(fn(*passes[0]))
             done = torch.cuda.Event()
             done.record(st)
         cur.wait_event(done)
@@ -1176,26 +1186,18 @@ def routed_attention_repaired(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             routed_attention_tiers(q, k, v, rr.routings, geom, operands=operands, **common)
         return out, None
     records: list = []
-    for name, routing in rr.routings.items():
-        native = name == "native"
-        routed_attention(q, k, v, routing, geom, fp8=False if native else name,
-                         operands=None if operands is None else operands.get(name), fidelity=records,
-                         fidelity_rows=rows, fidelity_heads="sparse" if native else "all", **common)
+    _launch_tiers(q, k, v, rr.routings, geom, operands, records, lambda name: "sparse" if name == "native" else "all",
+                  fidelity_rows=rows, **common)
     fid = _merge_sampled(records)
     exact = rr.tiers.index("native")
     repair_list, repair_count, state, rel = ops.route_repair(fid.sq_ref, fid.sq_err, rr.expert_ids, rr.tier_index, rr.lists,
                                                              rr.counts, exact_tier=exact, repair_above=float(repair_above))
     if rr.tier_ids is not None:  # (a TierRoutes' global ids follow: every repaired head is in `native` now)
         rr.tier_ids.masked_fill_(state == 2, ops.TIER_NAMES.index("native"))
-    hy = model == "hunyuan"
-    q3, k3, v3 = (x[0] if x.dim() == 4 else x for x in (q, k, v))
-    S, T, te, rm = geom.S, (text_len if hy else 0), (text_valid if hy else 0), geom.row_map
-    H, D = q3.shape[0], q3.shape[-1]
-    splits = int(kw.get("kv_splits") or 1)
-    dense = dict(q=q3, k=k3, v=v3, scale=scale, out=out[0] if out.dim() == 4 else out, n_q=S + T, n_kv=S + te,
-                 q_valid=S + te, tag="repair", q_rows=None if rm is None else rm[:S + T],
-                 kv_rows=None if rm is None else rm[:S + te], flops=0.0, head_list=repair_list, n_heads=H,
-                 n_heads_dev=repair_count, **(dict(n_splits=splits) if splits > 1 else {}))
+    T, te = (text_len, text_valid) if model == "hunyuan" else (0, 0)
+    dense = dict(q=_fold(q), k=_fold(k), v=_fold(v), scale=scale, out=_fold(out), tag="repair", flops=0.0,
+                 head_list=repair_list, n_heads=q.shape[-3], n_heads_dev=repair_count,
+                 **_full_launch(geom, T, te, kw.get("kv_splits")))
     if record is not None:
         record.append(dense)
     ops.attn_fwd_batch([dense])
