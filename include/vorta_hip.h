@@ -63,7 +63,9 @@ extern "C" {
                                    and the same over (precision tier, expert) pairs, vorta_route_fidelity_tiers (a pure
                                    addition: the symbol and vorta_route_fidelity_tiers_args_size())
                                    and the verification and repair of launched routes, vorta_route_repair (a pure addition:
-                                   the symbol and vorta_route_repair_args_size()) */
+                                   the symbol and vorta_route_repair_args_size())
+                                   and routing over (precision tier, expert) pairs by a cost budget, vorta_route_budget_tiers (a
+                                   pure addition: the symbol and vorta_route_budget_tiers_args_size()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -1008,6 +1010,66 @@ typedef struct vorta_route_fidelity_tiers_args {
 
 int vorta_route_fidelity_tiers(const vorta_route_fidelity_tiers_args* args, void* hip_stream);
 int vorta_route_fidelity_tiers_args_size(void);
+
+/*
+ * vorta_route_budget_tiers (ABI 9, a pure addition: a binding asks for the symbol and for
+ * vorta_route_budget_tiers_args_size(); vorta_sizeof keeps its 17 indices) -- routing over (precision tier, expert) PAIRS by
+ * a COST budget: spend at most max_cost_share of what the layer costs with every head on full attention in the last tier,
+ * on any expert in any tier, so that the largest per-head error is as small as that buys.  The record, the tiers, the
+ * candidates, their rel and their cost are vorta_route_fidelity_tiers'.  One launch of one workgroup; no atomics; the same
+ * bits on every run.  The rule is the host function's (vorta.patch.routes_within_cost_share), which is the definition.
+ *
+ * Definitions.
+ *   - state(r), r >= 0 in float32: the table vorta_route_fidelity_tiers gives at max_rel_error = r.
+ *   - cost(table): the sum over (t, e), t-major, of n[t][e] * (work[e] * tier_cost[t]) from the integer counts, in double,
+ *     every product and sum rounded on its own; an empty list adds nothing.
+ *   - budget = max_cost_share * (heads * (work[0] * tier_cost[n_tiers-1])), rounded products in that order.  A table is
+ *     within the budget unless cost > budget: equality is within.
+ *   - The levels are 0 and every finite rel of a candidate.
+ *
+ * Rule.
+ *   - r* is the smallest level whose state is within the budget.  Where no level is, the candidates ran out: r* is the
+ *     largest level, the result is state(r*), and cost_share > max_cost_share shows it.
+ *   - r* == 0: the result is state(0).
+ *   - Else start from state(r-), r- the largest level below r*.  The heads whose pair in state(r*) is STRICTLY cheaper than
+ *     their pair in state(r-) move to it in ascending head id, one at a time, until the cost is within the budget.  No
+ *     other head moves: an equal cost moves nothing.
+ *   - level receives r*: every head that had a qualifying candidate is within it on the sampled rows.
+ * The result minimises the largest per-head rel over all assignments within the budget.  With one tier this is NOT
+ * vorta_route_fidelity's mode 1, which gives a head one candidate; here a head may step down twice.
+ *
+ * The kernel sorts nothing: 32 passes bisect the bit pattern of r*, 1 pass finds r-, 11 bisect the head index of the partial
+ * step; every trip count is fixed at launch.  The two bisections (midpoint lo + (hi - lo) / 2 over 0 .. the pattern of +inf;
+ * (lo + hi) / 2 over 0 .. heads) are how the host function finds r* and the partial step too.  They are the searches of the
+ * rule wherever cost(state(r)) does not grow with r: always with an exact tier, and without one whenever full attention in the
+ * last tier is the dearest pair.  In another order they still end on a level whose state is within the budget (or report that
+ * the candidates ran out), but a smaller such level may exist.
+ *
+ * VORTA_EINVAL for whatever vorta_route_fidelity_tiers refuses (a wrong struct_size; a null sq_ref, sq_err, expert_of_head,
+ * tier_of_head, head_lists or head_counts; heads outside 1..1024; n_tiers outside 1..3; exact_tier outside -1..n_tiers-1; a
+ * work entry, or a tier_cost entry of the first n_tiers, that is not positive and finite), and for a max_cost_share that is
+ * NaN, zero or negative.  Everything is looked at before anything is launched.
+ */
+typedef struct vorta_route_budget_tiers_args {
+  uint32_t struct_size;      /* = sizeof(vorta_route_budget_tiers_args) = vorta_route_budget_tiers_args_size() */
+  int32_t heads;             /* 1..1024 */
+  int32_t n_tiers;           /* 1..3 */
+  int32_t exact_tier;        /* -1..n_tiers-1 */
+  const float* sq_ref;       /* [heads] */
+  const float* sq_err;       /* [n_tiers][heads][3]; column 0 coreset, column 1 sliding tile, column 2 full attention, in that tier */
+  double max_cost_share;     /* > 0 */
+  double work[3];            /* FLOPs of one head under expert 0 / 1 / 2 (patch.fidelity.expert_work); all > 0 */
+  double tier_cost[3];       /* cost of a FLOP in tier t relative to any common unit; the first n_tiers > 0 */
+  int32_t* expert_of_head;   /* [heads] */
+  int32_t* tier_of_head;     /* [heads], the caller's tier index */
+  int32_t* head_lists;       /* [n_tiers][3][heads], ascending head ids; entries at or past the count are not written */
+  int32_t* head_counts;      /* [n_tiers][3] */
+  float* cost_share;         /* optional, 1 float: cost(result) over heads (work[0] tier_cost[n_tiers-1]), in double, rounded once */
+  float* level;              /* optional, 1 float: r* */
+} vorta_route_budget_tiers_args;
+
+int vorta_route_budget_tiers(const vorta_route_budget_tiers_args* args, void* hip_stream);
+int vorta_route_budget_tiers_args_size(void);
 
 /*
  * vorta_route_repair (ABI 9, a pure addition: a binding asks for the symbol and for vorta_route_repair_args_size();

@@ -212,6 +212,15 @@ class RouteFidelityTiersArgs(C.Structure):
     ]
 
 
+class RouteBudgetTiersArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("heads", _i32), ("n_tiers", _i32), ("exact_tier", _i32), ("sq_ref", _vp), ("sq_err", _vp),
+        ("max_cost_share", C.c_double), ("work", C.c_double * 3), ("tier_cost", C.c_double * 3),
+        ("expert_of_head", _vp), ("tier_of_head", _vp), ("head_lists", _vp), ("head_counts", _vp), ("cost_share", _vp),
+        ("level", _vp),
+    ]
+
+
 class RouteRepairArgs(C.Structure):
     _fields_ = [
         ("struct_size", _u32), ("heads", _i32), ("n_tiers", _i32), ("exact_tier", _i32), ("repair_above", C.c_float),
@@ -291,6 +300,8 @@ SYMBOLS = {
     "vorta_route_fidelity_args_size": (C.c_int, []),
     "vorta_route_fidelity_tiers": (C.c_int, [C.POINTER(RouteFidelityTiersArgs), _vp]),
     "vorta_route_fidelity_tiers_args_size": (C.c_int, []),
+    "vorta_route_budget_tiers": (C.c_int, [C.POINTER(RouteBudgetTiersArgs), _vp]),
+    "vorta_route_budget_tiers_args_size": (C.c_int, []),
     "vorta_route_repair": (C.c_int, [C.POINTER(RouteRepairArgs), _vp]),
     "vorta_route_repair_args_size": (C.c_int, []),
     "vorta_seq_row_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
@@ -331,7 +342,7 @@ def lib():
             fn = getattr(h, name)
         except AttributeError:
             # ABI 9 gained vorta_qk_norm_rope_bwd, the key-major and the deterministic backward, vorta_expert_fidelity, the
-            # partial-geometry entry points, vorta_sampled_fidelity, vorta_gather_sample_rows, the ticket-order fused grid, vorta_route_fidelity, vorta_route_fidelity_tiers and vorta_route_repair without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
+            # partial-geometry entry points, vorta_sampled_fidelity, vorta_gather_sample_rows, the ticket-order fused grid, vorta_route_fidelity, vorta_route_fidelity_tiers, vorta_route_budget_tiers and vorta_route_repair without a new number: an older ABI-9 build (VORTA_HIP_LIB) lacks them
             raise VortaHipError(f"{LIB_PATH} does not export {name} (include/vorta_hip.h declares it): the library is "
                                 "older than this binding -- rebuild it with `python -m vorta_amd.build`") from None
         fn.restype = res
@@ -363,6 +374,9 @@ def lib():
     if h.vorta_route_fidelity_tiers_args_size() != C.sizeof(RouteFidelityTiersArgs):
         raise VortaHipError(f"struct layout mismatch for RouteFidelityTiersArgs: C {h.vorta_route_fidelity_tiers_args_size()} "
                             f"vs ctypes {C.sizeof(RouteFidelityTiersArgs)}")
+    if h.vorta_route_budget_tiers_args_size() != C.sizeof(RouteBudgetTiersArgs):
+        raise VortaHipError(f"struct layout mismatch for RouteBudgetTiersArgs: C {h.vorta_route_budget_tiers_args_size()} "
+                            f"vs ctypes {C.sizeof(RouteBudgetTiersArgs)}")
     if h.vorta_route_repair_args_size() != C.sizeof(RouteRepairArgs):
         raise VortaHipError(f"struct layout mismatch for RouteRepairArgs: C {h.vorta_route_repair_args_size()} "
                             f"vs ctypes {C.sizeof(RouteRepairArgs)}")

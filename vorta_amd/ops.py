@@ -1301,6 +1301,57 @@ def route_fidelity_tiers(fids, *, max_rel_error: Optional[float] = None, max_flo
     return (expert, tier, lists, counts) + ((share,) if cost_share else ())
 
 
+def route_budget_tiers(fids, *, max_cost_share: float, work=None, tier_cost=None, cost_share: bool = False):
+    """vorta_route_budget_tiers: the head -> (tier, expert) tables of one layer from its measured statistics per precision
+    tier, by `vorta.patch.routes_within_cost_share`'s rule, without a host read: spend at most `max_cost_share` of what the
+    layer costs with every head on full attention in the last tier, on any expert in any tier, so that the largest per-head
+    error is as small as that buys.  `fids`, `work`, `tier_cost`: as `route_fidelity_tiers` takes them (the same validation,
+    the same `tier_plan`).  With one tier this is NOT `route_fidelity(max_flops_share=...)`'s rule: that one gives a head one
+    candidate, this one lets a head step down twice.
+    Returns (expert_of_head (H,), tier_of_head (H,) = the INDEX into the caller's tiers, head_lists (n_tiers,3,H),
+    head_counts (n_tiers,3)) int32 and level (1,) float32 on the device -- the error the budget bought: every head that had a
+    qualifying candidate is within it on the sampled rows -- and with `cost_share=True` a sixth, one float32: the routed
+    layer's cost over all heads on full attention in the last tier (over `max_cost_share` where the candidates ran out)."""
+    import math
+    if max_cost_share is None or isinstance(max_cost_share, (bool, str)) or math.isnan(float(max_cost_share)) \
+            or not float(max_cost_share) > 0:
+        raise ValueError(f"route_budget_tiers: max_cost_share={max_cost_share!r} (a positive share)")
+    ids, costs, exact = tier_plan(fids, tier_cost)
+    records = list(fids.values())
+    sq_ref = records[0].sq_ref
+    _require_gpu(sq_ref, *(f.sq_err for f in records))
+    for f in records:
+        if sq_ref.dim() != 1 or tuple(f.sq_err.shape) != (sq_ref.shape[0], 3) or sq_ref.dtype != torch.float32 \
+                or f.sq_err.dtype != torch.float32:
+            raise ValueError("route_budget_tiers: the statistics of ONE layer, sq_ref (H,) and per tier sq_err (H, 3) in float32")
+    T = len(records)
+    sq_ref = sq_ref.contiguous()
+    sq_err = records[0].sq_err.contiguous() if T == 1 else torch.stack([f.sq_err for f in records])
+    H, dev = sq_ref.shape[0], sq_ref.device
+    expert = torch.empty(H, dtype=torch.int32, device=dev)
+    tier = torch.empty(H, dtype=torch.int32, device=dev)
+    lists = torch.empty((T, 3, H), dtype=torch.int32, device=dev)  # (entries at or past a count are not written, and not read)
+    counts = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    level = torch.empty(1, dtype=torch.float32, device=dev)
+    share = torch.empty(1, dtype=torch.float32, device=dev) if cost_share else None
+    a = _C.RouteBudgetTiersArgs()
+    a.struct_size = C.sizeof(_C.RouteBudgetTiersArgs)
+    a.heads, a.n_tiers, a.exact_tier = H, T, exact
+    a.sq_ref, a.sq_err = sq_ref.data_ptr(), sq_err.data_ptr()
+    a.max_cost_share = float(max_cost_share)
+    for e, w in enumerate(DEFAULT_ROUTE_WORK if work is None else work):
+        a.work[e] = float(w)
+    for t, c in enumerate(costs):
+        a.tier_cost[t] = c
+    a.expert_of_head, a.tier_of_head = expert.data_ptr(), tier.data_ptr()
+    a.head_lists, a.head_counts = lists.data_ptr(), counts.data_ptr()
+    a.level = level.data_ptr()
+    if share is not None:
+        a.cost_share = share.data_ptr()
+    _C.check(_C.lib().vorta_route_budget_tiers(C.byref(a), _stream()), "vorta_route_budget_tiers")
+    return (expert, tier, lists, counts, level) + ((share,) if cost_share else ())
+
+
 def route_repair(sq_ref: torch.Tensor, sq_err: torch.Tensor, expert_of_head: torch.Tensor,
                  tier_of_head: Optional[torch.Tensor], head_lists: torch.Tensor, head_counts: torch.Tensor, *,
                  exact_tier: int, repair_above: float, out=None):

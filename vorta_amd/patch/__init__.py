@@ -21,11 +21,16 @@ forward by its own measurement on the device -- a stated error bound or FLOP bud
 definition `ops.route_fidelity_tiers` (vorta_route_fidelity_tiers) equals on the device; `repair_routes`: which heads, as
 launched, are over a stated error on the sampled rows and the routes without them -- the definition `ops.route_repair`
 (vorta_route_repair) equals; `measured_routes(..., repair_above=...)` / `fixed_routes(..., repair_above=...)` verify and repair
-every forward by it, and `repaired_routes_of(model)` reads the latest forward's tables."""
+every forward by it, and `repaired_routes_of(model)` reads the latest forward's tables;
+`routes_within_cost_share`: the COST-budget rule over (precision tier, expert) pairs -- at most this share of the dense layer's
+cost, any expert in any precision, the smallest largest error that buys; the definition `ops.route_budget_tiers`
+(vorta_route_budget_tiers) equals -- `measured_routes(model, max_cost_share=...)` routes every layer by it and
+`measured_levels_of(model)` reads the error each layer's budget bought."""
 from ._engine import all_reduce_router_grads, original_attention, routing_scores_of, token_sharded
-from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, measured_precisions_of,
-                       measured_routes, measured_routes_of, repair_routes, repaired_routes_of, routed_fidelity, routed_fidelity_of,
-                       routes_from_fidelity, routes_from_fidelity_tiers, sampled_expert_fidelity, sampled_expert_fidelity_of)
+from .fidelity import (evaluate_routing, expert_fidelity, expert_work, fidelity_of, fixed_routes, measured_levels_of,
+                       measured_precisions_of, measured_routes, measured_routes_of, repair_routes, repaired_routes_of,
+                       routed_fidelity, routed_fidelity_of, routes_from_fidelity, routes_from_fidelity_tiers,
+                       routes_within_cost_share, sampled_expert_fidelity, sampled_expert_fidelity_of)
 from .router import Router, load_router_checkpoint
 from .utils import (Pixel2TokenFactory, hunyuan_pixel2token, prepare_hunyuan_self_attn_kwargs,
                     prepare_wan_self_attn_kwargs, wan_pixel2token)

@@ -49,6 +49,12 @@ And with the bound over the 8-bit PRECISION of what is launched (process precisi
     with fixed_routes(model, measured_routes_of(model)[0], precisions=tiers):   # the same launches, nothing measured
         model(hidden_states, ..., self_attention_kwargs=kw)
 
+Or a BUDGET over the same pairs -- a time target: this share of the dense 16-bit layer's cost, any expert in any precision:
+
+    with measured_routes(model, max_cost_share=0.4):                   # routes_within_cost_share is the rule (vorta_route_budget_tiers)
+        model(hidden_states, ..., self_attention_kwargs=kw)
+    measured_levels_of(model)                         # (L,) the error each layer's budget bought
+
 And a bound on what every forward LAUNCHED -- stored routes between two measurements, a reused table, the 8-bit launches:
 
     with measured_routes(model, max_rel_error=0.05, refresh_every=4, repair_above=0.08):   # verify on the sampled rows, repair
@@ -59,6 +65,7 @@ And a bound on what every forward LAUNCHED -- stored routes between two measurem
 """
 from __future__ import annotations
 
+import bisect
 import contextlib
 import math
 from dataclasses import dataclass, field
@@ -72,6 +79,7 @@ from ..ops import ExpertFidelity, SampledFidelity
 from ._engine import context_of
 
 _COLUMN_OF_EXPERT = {1: 0, 2: 1}  # expert id -> column of sq_err / max_err / rel_error
+_INF_PATTERN = 0x7F800000  # float32 +inf: non-negative float32 values order like their patterns below it
 
 
 @contextlib.contextmanager
@@ -419,7 +427,8 @@ class MeasuredRoutes:
 @contextlib.contextmanager
 def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
                     n_rows: int = 512, seed: int = 0, refresh_every: int = 1, covers_precision: bool = False,
-                    tier_cost: Optional[Mapping] = None, repair_above: Optional[float] = None):
+                    tier_cost: Optional[Mapping] = None, repair_above: Optional[float] = None,
+                    max_cost_share: Optional[float] = None):
     """While active, every non-teacher forward of `model` (patched with apply_vorta_transformer, hard-routing Eval processors)
     routes each layer by a MEASUREMENT of that layer on its own q, k, v, held per prompt, per layer and per step, without a
     router checkpoint and without a host read (`routed.route_by_fidelity`: `n_rows` sampled video rows per head,
@@ -452,7 +461,14 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     8-bit precision of the launches included -- where `max_rel_error` covers the candidates of a measuring forward; under
     `max_flops_share` it is the only error bound there is.  `repaired_routes_of(model)` reads the latest forward's tables;
     `measured_routes_of(model)` then reports the experts after the repairs.
-    Refused by name: a model that was not patched; both rules or neither; nesting with `fixed_routes`, `sampled_expert_fidelity`
+    `max_cost_share=s`, the third rule: a budget that covers the precision -- per layer at most the share s of what the layer
+    costs with every head on full attention in the input dtype, spent on ANY expert in ANY tier of the process precision so
+    that the largest per-head error is as small as that buys (`routes_within_cost_share` is the rule; vorta_route_budget_tiers
+    applies it).  `covers_precision` is implied -- one measurement per tier, launched tier by tier, as above -- and
+    `tier_cost`, `refresh_every` and `repair_above` work as for the bound over tiers; under "native" the one tier is routed.
+    `measured_levels_of(model)` reads the error each layer's budget bought.  A time target, not an error target: where
+    `max_flops_share` cannot spend on the 8-bit kernels, this rule can.
+    Refused by name: a model that was not patched; more than one rule or none; nesting with `fixed_routes`, `sampled_expert_fidelity`
     or another `measured_routes`, either way round; sequence parallelism (NotImplementedError, as `fixed_routes`); a negative or
     NaN `repair_above`; `repair_above` under an 8-bit process precision without `covers_precision=True` (the bound is on what
     is launched, so the routes must name the tier of every launch)."""
@@ -463,17 +479,18 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     if covers_precision and max_flops_share is not None:
         raise ValueError("measured_routes: covers_precision with max_flops_share: a FLOP budget has no form over precision "
                          "tiers; give max_rel_error")
+    covers_precision = bool(covers_precision) or max_cost_share is not None  # (the cost budget implies it)
     if tier_cost is not None and not covers_precision:
         raise ValueError("measured_routes: tier_cost goes with covers_precision=True")
-    if (max_rel_error is None) == (max_flops_share is None):
-        raise ValueError("measured_routes: exactly one of max_rel_error and max_flops_share")
+    if sum(x is not None for x in (max_rel_error, max_flops_share, max_cost_share)) != 1:
+        raise ValueError("measured_routes: exactly one of max_rel_error and max_flops_share and max_cost_share")
     if covers_precision:
         from ..ops import tier_plan
         tier_plan({"native": None}, tier_cost)  # (ValueError for a tier that is none of the three, a cost not positive and finite)
         tier_cost = None if tier_cost is None else dict(tier_cost)
-    mode = ROUTE_RULE_MODES[0] if max_flops_share is None else ROUTE_RULE_MODES[1]
-    value = float(max_rel_error if max_flops_share is None else max_flops_share)
-    if not (value >= 0 if max_flops_share is None else value > 0):
+    mode, given = next((m, x) for m, x in zip(ROUTE_RULE_MODES, (max_rel_error, max_flops_share, max_cost_share)) if x is not None)
+    value = float(given)
+    if not (value >= 0 if mode == ROUTE_RULE_MODES[0] else value > 0):
         raise ValueError(f"measured_routes: {mode}={value} (a bound >= 0; a share > 0)")
     if not ctx.needs_tau:
         raise ValueError("measured_routes: the model was patched with soft-mixture (Train) processors, which run every "
@@ -567,6 +584,22 @@ def measured_precisions_of(model: nn.Module, item: int = 0) -> torch.Tensor:
                            "with hard-routing (Eval) processors")
     entries = [measured.filed[layer][item] for layer in sorted(measured.filed)]
     return torch.stack([e[4]["tier_ids"] if len(e) > 4 else torch.zeros_like(e[0]) for e in entries])
+
+
+def measured_levels_of(model: nn.Module, item: int = 0) -> torch.Tensor:
+    """The (L,) float32 levels of the model's latest MEASURING forward under `measured_routes(model, max_cost_share=...)`, on
+    the device, layers in block order: per layer the error its budget bought (`routes_within_cost_share`'s `level`) -- every
+    head that had a qualifying candidate is within it on the sampled rows.  RuntimeError where the latest measuring forward
+    was routed by another rule: a bound states its own error, and a FLOP budget buys none that is on record."""
+    ctx = context_of(model)
+    measured = ctx.measured_routes if ctx.measured_routes is not None else ctx.latest_measured_routes
+    if measured is None or not measured.filed:
+        raise RuntimeError("measured_levels_of: no forward of this model has measured under measured_routes(model, ...) "
+                           "with hard-routing (Eval) processors")
+    entries = [measured.filed[layer][item] for layer in sorted(measured.filed)]
+    if any(len(e) <= 4 or e[4].get("level") is None for e in entries):
+        raise RuntimeError("measured_levels_of: the latest measuring forward was not routed by max_cost_share")
+    return torch.cat([e[4]["level"].reshape(1) for e in entries])
 
 
 Geometry = Union[Mapping[str, Any], Any]
@@ -720,17 +753,175 @@ def routes_from_fidelity_tiers(fids, max_rel_error: Optional[float] = None, geom
     experts = torch.zeros((N, H), dtype=torch.int64)
     tiers = torch.zeros((N, H), dtype=torch.int64)
     for layer in range(N):
-        for h in range(H):
-            best = None  # (cost, tier index, -expert): the smallest wins
-            for t in range(T):
-                for e in (0, 1, 2):
-                    rel = 0.0 if (e == 0 and t == exact) else rels[t][layer][h][2 if e == 0 else _COLUMN_OF_EXPERT[e]]
-                    if rel <= bound:
-                        key = (float(work[e]) * costs[t], t, -e)
-                        best = key if best is None or key < best else best
-            t, e = (T - 1, 0) if best is None else (best[1], -best[2])
+        for h, (t, e) in enumerate(_pairs_within_bound([rels[t][layer] for t in range(T)], bound, work, costs, exact)):
             experts[layer, h], tiers[layer, h] = e, ids[t]
     return experts.reshape(shape), tiers.reshape(shape)
+
+
+def _pairs_within_bound(rels, bound: float, work, costs, exact: int) -> list:
+    """The selection of `routes_from_fidelity_tiers` on ONE layer: `rels[t][h]` the three float32 rel of tier index t and head h
+    as Python floats (column 0 coreset, 1 sliding tile, 2 full attention in that tier); per head the (tier index, expert) of
+    the cheapest candidate with rel <= bound, (T-1, 0) where none qualifies.  `routes_within_cost_share` calls it too, so the
+    two rules share one selection."""
+    T = len(rels)
+    pairs = []
+    for h in range(len(rels[0])):
+        best = None  # (cost, tier index, -expert): the smallest wins
+        for t in range(T):
+            for e in (0, 1, 2):
+                rel = 0.0 if (e == 0 and t == exact) else rels[t][h][2 if e == 0 else _COLUMN_OF_EXPERT[e]]
+                if rel <= bound:
+                    key = (float(work[e]) * costs[t], t, -e)
+                    best = key if best is None or key < best else best
+        pairs.append((T - 1, 0) if best is None else (best[1], -best[2]))
+    return pairs
+
+
+class CostShareRoutes(NamedTuple):
+    """`routes_within_cost_share`: per layer, on the CPU"""
+    experts: torch.Tensor      # (..., H) int64: 0 full attention, 1 coreset, 2 sliding tile
+    tiers: torch.Tensor        # (..., H) int64: GLOBAL precision tier ids (0 native, 1 fp8pv, 2 i8pv)
+    level: torch.Tensor        # (...,) float32: r*, the error the budget bought
+    cost_share: torch.Tensor   # (...,) float32: the routed layer's cost over all heads on full attention in the last tier
+
+
+def routes_within_cost_share(fids, max_cost_share: float, geometry: Optional[Geometry] = None, text_valid: int = 0, *,
+                             tier_cost: Optional[Mapping] = None) -> CostShareRoutes:
+    """Per head the expert AND the precision tier to launch it in, by a COST budget: spend at most `max_cost_share` of what the
+    layer costs with every head on full attention in the last tier, on any expert in any tier, where it hurts least.  `fids`,
+    `geometry`, `text_valid`, `tier_cost`, the candidates (t, e), their rel (float32) and their cost c[t][e] = work[e] *
+    tier_cost[t] (one rounded double product) are `routes_from_fidelity_tiers`', on which this function is written.
+    Definitions.  state(r), for a float32 r >= 0: the table `routes_from_fidelity_tiers` gives at the bound r -- its own
+    selection (`_pairs_within_bound`, one body for both rules) on rel formed as the device forms it, the divide and the square
+    root each correctly rounded in float32 (`_rel_error_float32`), so that a level and the rel it came from are one number.
+    cost(table) = the sum over (t, e), t-major, of n[t][e] * c[t][e] from the integer counts, every product and sum rounded
+    on its own, an empty list adding nothing.  budget = max_cost_share * (H * c[T-1][0]), two rounded products in that order;
+    a table is within it unless cost > budget (equality is within).  The levels are 0 and every finite rel of a candidate.
+    The rule.  r* is the smallest level whose state is within the budget; where no level is, the candidates ran out: r* is
+    the largest level, the result is state(r*) and `cost_share` > `max_cost_share` shows it.  With r* == 0 the result is
+    state(0).  Else start from state(r-), r- the largest level below r*, and move the heads whose pair in state(r*) is
+    STRICTLY cheaper than their pair in state(r-) to it, in ascending head id, one at a time, until the cost is within the
+    budget: no head's error is raised for nothing, and an equal cost moves no head.  `level` = r*: every head that had a
+    qualifying candidate is within it on the sampled rows (a (T-1, 0) fallback head without a `native` tier is not covered,
+    as in the bound rule).
+    The result minimises the largest per-head rel over all assignments within the budget: an assignment whose largest rel
+    is below r* costs at least cost(state(r-)), which is over the budget.
+    How r* and the partial step are FOUND is part of the definition, so that the device can be held to it with `==` on every
+    record: r* by bisection over the float32 pattern of r (0 .. the pattern of +inf, the midpoint lo + (hi - lo) // 2), the
+    partial step by bisection over the head index m in 0 .. H (the heads below m move).  Both are the searches above wherever
+    the cost of a state does not grow with r, and that is the case whenever no head leaves the (T-1, 0) fallback for a DEARER
+    pair: always with a `native` tier (a head is never without a candidate), and without one whenever full attention in the
+    last tier is the dearest pair of the call -- the order "cheapest tier first" with full attention the dearest expert.  In
+    another order the bisection still ends on a level whose state is within the budget (or reports that the candidates ran
+    out), but a smaller such level may exist.
+    With one tier this is NOT `routes_from_fidelity(max_flops_share=...)`: that rule gives a head ONE candidate, its
+    smaller-rel sparse expert; this one lets a head step down twice (coreset, then sliding tile).  Neither rule changes.
+    ValueError for a share that is zero, negative or NaN, and for what `ops.tier_plan` refuses.
+    This function is the definition: `ops.route_budget_tiers` (vorta_route_budget_tiers) applies it on the device."""
+    import numpy as np
+    from ..ops import DEFAULT_ROUTE_WORK, tier_plan
+    if max_cost_share is None or isinstance(max_cost_share, (bool, str)) or not float(max_cost_share) > 0:
+        raise ValueError(f"routes_within_cost_share: max_cost_share={max_cost_share!r} (a positive share)")
+    share = float(max_cost_share)
+    ids, costs, exact = tier_plan(fids, tier_cost)
+    work = DEFAULT_ROUTE_WORK if geometry is None else expert_work(geometry, text_valid)
+    T = len(ids)
+    c = [[float(work[e]) * costs[t] for e in range(3)] for t in range(T)]
+    records = list(fids.values())
+    shape = tuple(records[0].sq_err.shape[:-1])
+    H = shape[-1]
+    sq_ref = records[0].sq_ref.detach().cpu().float().reshape(-1, H)
+    sq_errs = [f.sq_err.detach().cpu().float().reshape(-1, H, 3) for f in records]
+    N = sq_ref.shape[0]
+    dense = H * c[T - 1][0]
+    budget = share * dense
+
+    def counts(experts, tiers):
+        n = [[0, 0, 0] for _ in range(T)]
+        for e, t in zip(experts, tiers):
+            n[t][e] += 1
+        return n
+
+    def cost(n):  # from the integer counts, t-major: the order of the moves cannot change the bits
+        total = 0.0
+        for t in range(T):
+            for e in range(3):
+                if n[t][e]:
+                    total = total + n[t][e] * c[t][e]
+        return total
+
+    out_e = torch.zeros((N, H), dtype=torch.int64)
+    out_t = torch.zeros((N, H), dtype=torch.int64)
+    level = torch.zeros(N, dtype=torch.float32)
+    cost_share = torch.zeros(N, dtype=torch.float32)
+    for layer in range(N):
+        # rel with BOTH operations correctly rounded in float32, as the device forms it: the levels and the states come from
+        # the same numbers, so a head whose rel IS a level qualifies at it (a math library's square root may be an ulp off)
+        rels = []  # [t][h] = the three columns
+        for t in range(T):
+            cols = [_rel_error_float32(sq_errs[t][layer][:, col], sq_ref[layer]) for col in range(3)]
+            rels.append([[cols[0][h], cols[1][h], cols[2][h]] for h in range(H)])
+
+        def state(r):  # `routes_from_fidelity_tiers`' selection at the bound r: (experts, tier indices)
+            pairs = _pairs_within_bound(rels, r, work, costs, exact)
+            return [e for _, e in pairs], [t for t, _ in pairs]
+
+        found = {0.0}
+        for t in range(T):
+            for col in range(3):
+                if col == 2 and t == exact:
+                    continue  # (the exact tier's full attention is the reference: the level 0)
+                found.update(rels[t][h][col] + 0.0 for h in range(H) if math.isfinite(rels[t][h][col]))
+        levels = sorted(found)
+        states = {}  # level index -> (experts, tiers, within the budget): state(r) is the state of the largest level <= r
+
+        def at(index):
+            if index not in states:
+                experts, tiers = state(levels[index])
+                states[index] = (experts, tiers, not cost(counts(experts, tiers)) > budget)
+            return states[index]
+
+        # r*: bisection over the float32 PATTERN of r (non-negative floats order like their patterns), 0 .. the pattern of
+        # +inf, which stands for "no level is within"
+        lo, hi = 0, _INF_PATTERN
+        while lo < hi:
+            mid = lo + (hi - lo) // 2
+            r = float(np.array(mid, dtype=np.uint32).view(np.float32))
+            if at(bisect.bisect_right(levels, r) - 1)[2]:
+                hi = mid
+            else:
+                lo = mid + 1
+        if hi == _INF_PATTERN:  # the candidates ran out
+            star = len(levels) - 1
+            experts, tiers, _ = at(star)
+        else:
+            star = bisect.bisect_right(levels, float(np.array(hi, dtype=np.uint32).view(np.float32))) - 1
+            experts, tiers, _ = at(max(star - 1, 0))
+            to_e, to_t, _ = at(star)
+            moves = [h for h in range(H) if c[to_t[h]][to_e[h]] < c[tiers[h]][experts[h]]]  # (none at r* == 0)
+
+            def moved(m):  # the heads below m that get strictly cheaper moved to their pair in state(r*)
+                e, t = list(experts), list(tiers)
+                for h in moves:
+                    if h < m:
+                        e[h], t[h] = to_e[h], to_t[h]
+                return e, t
+
+            # the partial step: bisection over the head index, 0 (state(r-), over the budget) .. H (every such head moved)
+            m_lo, m_hi = 0, H
+            while m_hi - m_lo > 1:
+                mid = (m_lo + m_hi) // 2
+                if cost(counts(*moved(mid))) > budget:
+                    m_lo = mid
+                else:
+                    m_hi = mid
+            experts, tiers = moved(m_hi)
+        experts, tiers, r_star = list(experts), list(tiers), levels[star]
+        out_e[layer] = torch.tensor(experts)
+        out_t[layer] = torch.tensor([ids[t] for t in tiers])
+        level[layer] = float(np.float32(r_star))
+        cost_share[layer] = float(np.float32(cost(counts(experts, tiers)) / dense))
+    return CostShareRoutes(out_e.reshape(shape), out_t.reshape(shape), level.reshape(shape[:-1]), cost_share.reshape(shape[:-1]))
 
 
 class RepairedRoutes(NamedTuple):

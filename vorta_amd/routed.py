@@ -680,7 +680,7 @@ def _tier_key_side(precision: str, operands: Optional[AttnOperands], q3, k3, v3,
     return {key: val for key, val in kw.items() if key not in ("q", "scale") and val is not None}
 
 
-ROUTE_RULE_MODES = ("max_rel_error", "max_flops_share")
+ROUTE_RULE_MODES = ("max_rel_error", "max_flops_share", "max_cost_share")
 # the precision tiers a call may launch in, cheapest first, by the process precision (`set_attention_precision`); the last is
 # where a head goes that no candidate serves.  Tier names and global ids: ops.TIER_NAMES (0 native, 1 fp8pv, 2 i8pv)
 TIERS_OF_PRECISION = {"i8pv": ("i8pv", "native"), "fp8pv": ("fp8pv", "native"), "auto8": ("i8pv", "fp8pv", "native"),
@@ -700,12 +700,15 @@ def tiers_of(fp8=None) -> Tuple[str, ...]:
 @dataclass(frozen=True)
 class RouteRule:
     """How the Eval processors route a call by its own measurement (`route_rule=`): `mode` one of ROUTE_RULE_MODES with its
-    `value`, on `n_rows` sampled video rows per head (`sample_rows` with `seed`; every row where the clip has fewer)"""
+    `value`, on `n_rows` sampled video rows per head (`sample_rows` with `seed`; every row where the clip has fewer).
+    "max_cost_share" covers the precision by itself: it routes over the tiers of the process precision with or without
+    `covers_precision`, under "native" over its one tier"""
     mode: str
     value: float
     n_rows: int = 512
     seed: int = 0
-    covers_precision: bool = False       # route over (precision tier, expert) pairs of the process precision: `tiers()`
+    # route over (precision tier, expert) pairs of the process precision: `tiers()` ("max_cost_share" always does)
+    covers_precision: bool = False
     tier_cost: Optional[dict] = None     # tier -> cost of a FLOP there; None: DEFAULT_TIER_COST
     # verify what every call launched on the sampled rows and re-run the heads further than this from dense attention
     # (`routed_attention_repaired`); None: nothing is verified.  The patch layer reads it; `route()` does not
@@ -716,13 +719,16 @@ class RouteRule:
             raise ValueError(f"RouteRule: repair_above={self.repair_above} (a bound >= 0, or None)")
         if self.mode not in ROUTE_RULE_MODES or int(self.n_rows) < 1:
             raise ValueError(f"RouteRule: mode={self.mode!r} (one of {ROUTE_RULE_MODES}), n_rows={self.n_rows} (at least 1)")
-        if self.covers_precision and self.mode != ROUTE_RULE_MODES[0]:
+        if self.covers_precision and self.mode == ROUTE_RULE_MODES[1]:
             raise ValueError("RouteRule: covers_precision goes with max_rel_error: max_flops_share has no form over precision "
-                             "tiers")
+                             "tiers (max_cost_share is the budget that has)")
 
     def tiers(self) -> Optional[Tuple[str, ...]]:
         """the tiers this rule routes over NOW, by the process precision; None where it routes experts alone -- without
-        `covers_precision`, and under "native", whose one tier is the routes of today"""
+        `covers_precision`, and under "native", whose one tier is the routes of today.  "max_cost_share" always routes over
+        tiers: `tiers_of(None)`, ("native",) included"""
+        if self.mode == ROUTE_RULE_MODES[2]:
+            return tiers_of(None)
         if not self.covers_precision:
             return None
         tiers = tiers_of(None)
@@ -741,7 +747,8 @@ class TierRoutes(NamedTuple):
     """`route_by_fidelity(tiers=...)`: per tier, in the caller's order, the HeadRouting of its device lists; the int32 (H,)
     head -> expert and head -> GLOBAL tier id tables; per tier the record it was measured by; per 8-bit tier the operands
     that were prepared for the measurement (`routed_attention_tiers(operands=...)` launches with them); and the kernel's
-    (n_tiers,3,H) lists and (n_tiers,3) counts the routings are views of"""
+    (n_tiers,3,H) lists and (n_tiers,3) counts the routings are views of; under `max_cost_share` also `level`, float32 (1,)
+    on the device: the error the budget bought (None under the bound, which states its own)"""
     routings: Dict[str, "HeadRouting"]
     expert_ids: torch.Tensor
     tier_ids: torch.Tensor
@@ -749,12 +756,14 @@ class TierRoutes(NamedTuple):
     operands: Dict[str, AttnOperands]
     lists: torch.Tensor
     counts: torch.Tensor
+    level: Optional[torch.Tensor] = None
 
 
 def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: RoutedGeometry, *, model: str,
                       text_len: int = 0, text_valid: int = 0, scale: Optional[float] = None, rows=None, seed: int = 0,
                       max_rel_error: Optional[float] = None, max_flops_share: Optional[float] = None,
-                      tiers: Optional[Sequence] = None, tier_cost: Optional[dict] = None):
+                      tiers: Optional[Sequence] = None, tier_cost: Optional[dict] = None,
+                      max_cost_share: Optional[float] = None):
     """Routes of one layer MEASURED on its own q, k, v, by a stated rule and without a router: `max_rel_error` = no sparse head
     may be further than that from dense attention on the sampled rows (per head the cheapest expert within the bound), or
     `max_flops_share` = spend at most that share of the dense layer's FLOPs where it hurts least (exactly one of the two;
@@ -773,11 +782,22 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
     `TierRoutes`; `routed_attention_tiers` launches it.  tier_cost: None = DEFAULT_TIER_COST.  `max_flops_share` with `tiers`
     is a ValueError by name.  What the bound covers: the candidate launches on the sampled rows, in each tier's own
     arithmetic; a full-size launch is that arithmetic with another key cut and, under "i8pv", another grouping of rows
-    into waves."""
+    into waves.
+    max_cost_share: the third rule, a budget that DOES cover the precision: spend at most that share of what the layer costs
+    with every head on full attention in the last tier, on any expert in any tier, so that the largest per-head error is as
+    small as that buys (`vorta.patch.routes_within_cost_share` is the rule; `ops.route_budget_tiers` applies it).  `tiers`
+    None: `tiers_of(None)`, the process precision's -- under "native" its one tier.  The measurement per tier is the one
+    above.  Always a `TierRoutes`, whose `level` is the error the budget bought.  With one tier this is not
+    `max_flops_share`'s rule: that one gives a head one candidate, this one lets a head step down twice."""
     if tiers is not None and max_flops_share is not None:
         raise ValueError("route_by_fidelity: max_flops_share has no form over precision tiers; give max_rel_error")
-    if (max_rel_error is None) == (max_flops_share is None):
-        raise ValueError("route_by_fidelity: exactly one of max_rel_error and max_flops_share")
+    if sum(x is not None for x in (max_rel_error, max_flops_share, max_cost_share)) != 1:
+        raise ValueError("route_by_fidelity: exactly one of max_rel_error and max_flops_share and max_cost_share")
+    if max_cost_share is not None:
+        if isinstance(max_cost_share, (bool, str)) or not float(max_cost_share) > 0:
+            raise ValueError(f"route_by_fidelity: max_cost_share={max_cost_share!r} (a positive share)")
+        if tiers is None:
+            tiers = tiers_of(None)
     if rows is not None and (rows.numel() if torch.is_tensor(rows) else int(rows)) < 1:
         raise ValueError("route_by_fidelity: rows: at least one sampled row (without one every error reads 0 and every head "
                          "would meet any bound)")
@@ -786,14 +806,15 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
                                   seed=seed)
     work = expert_work(geom, text_valid if model == "hunyuan" else 0, q.shape[-1])
     if tiers is not None:
-        return _route_tiers(q, k, v, geom, fid, work, tiers, tier_cost, float(max_rel_error),
+        rule = dict(max_rel_error=float(max_rel_error)) if max_cost_share is None else dict(max_cost_share=float(max_cost_share))
+        return _route_tiers(q, k, v, geom, fid, work, tiers, tier_cost, rule,
                             dict(model=model, text_len=text_len, text_valid=text_valid, scale=scale, rows=rows, seed=seed))
     expert, lists, counts = ops.route_fidelity(fid, max_rel_error=max_rel_error, max_flops_share=max_flops_share, work=work)
     return HeadRouting.from_device(lists, counts), expert, fid
 
 
-def _route_tiers(q, k, v, geom, native_fid, work, tiers, tier_cost, bound: float, measure_kw: dict) -> TierRoutes:
-    """`route_by_fidelity(tiers=...)` after the native measurement"""
+def _route_tiers(q, k, v, geom, native_fid, work, tiers, tier_cost, rule: dict, measure_kw: dict) -> TierRoutes:
+    """`route_by_fidelity(tiers=...)` after the native measurement; `rule`: max_rel_error or max_cost_share with its value"""
     names = [ops.TIER_NAMES[ops.tier_id(t)] for t in tiers]
     q3, k3, v3 = _fold(q), _fold(k), _fold(v)
     operands: Dict[str, AttnOperands] = {}
@@ -805,21 +826,25 @@ def _route_tiers(q, k, v, geom, native_fid, work, tiers, tier_cost, bound: float
                              else AttnOperands("fp8pv", q3, k3, i8.v, i8.v_descale))
     fids = {name: native_fid if name == "native" else
             sampled_expert_fidelity(q, k, v, geom, precision=name, operands=operands[name], **measure_kw) for name in names}
-    expert, tier, lists, counts = ops.route_fidelity_tiers(fids, max_rel_error=bound, work=work, tier_cost=tier_cost)
+    level = None
+    if "max_cost_share" in rule:
+        expert, tier, lists, counts, level = ops.route_budget_tiers(fids, work=work, tier_cost=tier_cost, **rule)
+    else:
+        expert, tier, lists, counts = ops.route_fidelity_tiers(fids, work=work, tier_cost=tier_cost, **rule)
     tier_ids = torch.zeros_like(tier)
     for i, name in enumerate(names):  # the caller's index -> the global id, on the device
         tier_ids = torch.where(tier == i, ops.TIER_NAMES.index(name), tier_ids)
     routings = {name: HeadRouting.from_device(lists[i], counts[i]) for i, name in enumerate(names)}
-    return TierRoutes(routings, expert, tier_ids, fids, operands, lists, counts)
+    return TierRoutes(routings, expert, tier_ids, fids, operands, lists, counts, level)
 
 
 def tier_sink_entry(routes: TierRoutes) -> tuple:
     """what a processor's `route_sink` receives for a call routed over tiers: the four entries of a call routed over experts
     -- expert_ids, lists (n_tiers,3,H), counts (n_tiers,3), a record (`native`'s, the method's error, where that tier is one of
-    them; else the first tier's) -- and the tier data"""
+    them; else the first tier's) -- and the tier data, `level` included (None under the bound)"""
     fid = routes.fids.get("native", next(iter(routes.fids.values())))
     return (routes.expert_ids, routes.lists, routes.counts, fid,
-            dict(tiers=tuple(routes.routings), tier_ids=routes.tier_ids, fids=routes.fids))
+            dict(tiers=tuple(routes.routings), tier_ids=routes.tier_ids, fids=routes.fids, level=routes.level))
 
 
 def _merge_sampled(records) -> "ops.SampledFidelity":

@@ -18,6 +18,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
                                                       -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
     vorta::route_fidelity_tiers(sq_ref, sq_err, tiers, max_rel_error, work, tier_cost)
                                                       -> (expert_of_head, tier_of_head, head_lists, head_counts, cost_share)   vorta_route_fidelity_tiers
+    vorta::route_budget_tiers(sq_ref, sq_err, tiers, max_cost_share, work, tier_cost)
+                                                      -> (expert_of_head, tier_of_head, head_lists, head_counts, level, cost_share)   vorta_route_budget_tiers
     vorta::route_repair(sq_ref, sq_err, expert_of_head, tier_of_head, head_lists, head_counts, exact_tier, repair_above)
                                                       -> (repair_list, repair_count, state_of_head, rel)   mutates the four tables   vorta_route_repair
     vorta::router_route(temb, weight, bias, heads, tau) -> (scores, expert_of_head, head_lists, head_counts)
@@ -156,6 +158,31 @@ def _(sq_ref, sq_err, tiers, max_rel_error, work=None, tier_cost=None):
     i32 = dict(dtype=torch.int32)
     return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((H,), **i32), sq_ref.new_empty((T, 3, H), **i32),
             sq_ref.new_empty((T, 3), **i32), sq_ref.new_empty((1,), dtype=torch.float32))
+
+
+@torch.library.custom_op("vorta::route_budget_tiers", mutates_args=(), device_types="cuda")
+def route_budget_tiers(sq_ref: torch.Tensor, sq_err: torch.Tensor, tiers: List[int], max_cost_share: float,
+                       work: Optional[List[float]] = None, tier_cost: Optional[List[float]] = None
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.route_budget_tiers on the statistics of one layer: the arguments of `route_fidelity_tiers` with the share of the
+    all-dense cost in the bound's place: int32 (H,), (H,), (n_tiers,3,H), (n_tiers,3), the level float32 (1,) and the routed
+    layer's cost share, float32 (1,)"""
+    if sq_err.dim() != 3 or sq_err.shape[0] != len(tiers) or (tier_cost is not None and len(tier_cost) != len(tiers)):
+        raise ValueError("route_budget_tiers: sq_err (n_tiers, H, 3) with one tier id, and one cost where given, per tier")
+    fids = {t: ops.ExpertFidelity(sq_ref, sq_ref, sq_err[i], sq_err[i]) for i, t in enumerate(tiers)}
+    if len(fids) != len(tiers):
+        raise ValueError(f"route_budget_tiers: distinct tiers, got {list(tiers)}")
+    cost = None if tier_cost is None else dict(zip(tiers, tier_cost))
+    return ops.route_budget_tiers(fids, max_cost_share=max_cost_share, work=work, tier_cost=cost, cost_share=True)
+
+
+@route_budget_tiers.register_fake
+def _(sq_ref, sq_err, tiers, max_cost_share, work=None, tier_cost=None):
+    H, T = sq_ref.shape[0], len(tiers)
+    i32 = dict(dtype=torch.int32)
+    return (sq_ref.new_empty((H,), **i32), sq_ref.new_empty((H,), **i32), sq_ref.new_empty((T, 3, H), **i32),
+            sq_ref.new_empty((T, 3), **i32), sq_ref.new_empty((1,), dtype=torch.float32),
+            sq_ref.new_empty((1,), dtype=torch.float32))
 
 
 @torch.library.custom_op("vorta::route_repair", mutates_args=("expert_of_head", "tier_of_head", "head_lists", "head_counts"),
