@@ -65,7 +65,10 @@ extern "C" {
                                    and the verification and repair of launched routes, vorta_route_repair (a pure addition:
                                    the symbol and vorta_route_repair_args_size())
                                    and routing over (precision tier, expert) pairs by a cost budget, vorta_route_budget_tiers (a
-                                   pure addition: the symbol and vorta_route_budget_tiers_args_size()) */
+                                   pure addition: the symbol and vorta_route_budget_tiers_args_size())
+                                   and the sliding-tile expert's key tiles chosen by content, vorta_sta_select_tiles (a pure
+                                   addition: the symbol, vorta_sta_select_tiles_args_size() and
+                                   vorta_sta_select_tiles_ws_floats()) */
 
 typedef enum vorta_dtype {
   VORTA_BF16 = 0,
@@ -604,6 +607,59 @@ int vorta_sta_build_tables(const vorta_sta_args* args, void* hip_stream);
 int vorta_sta_partial_sizes(const vorta_sta_args* args, int32_t* n_tiles, int32_t* n_lists, int32_t* list_stride,
                             int32_t* list_n_kv, int32_t list_n_kv_cap);
 int vorta_sta_build_tables_partial(const vorta_sta_args* args, void* hip_stream);
+
+/*
+ * vorta_sta_select_tiles -- the sliding-tile expert's key tiles chosen by CONTENT (ABI 9, a pure addition; no reference
+ * counterpart: the reference's mask_mod picks tiles by position alone).
+ *
+ * On a dividing geometry, with n_tiles, tok and cnt_d = min(nt_d, 2*(window_d/2)+1) as in vorta_sta_build_tables and
+ * n_sel = cnt_0*cnt_1*cnt_2 (the window expert's key-tile count), for every head slot y (head_list / n_heads /
+ * n_heads_dev as in vorta_attn_fwd; slots at or past *n_heads_dev are not touched) and every query tile i:
+ *   qbar[y][i][d]  = fp32 mean over the tok rows q_rows[i*tok .. i*tok+tok-1] of q (q_rows: the tile-major table of
+ *                    vorta_sta_build_tables, a row_map already applied); kbar the same for k
+ *   score[i][j]    = sum_d qbar[i][d] * kbar[j][d]   (fp32, d ascending, no scale: only the order is used)
+ *   selected       : tile i itself, and the n_sel-1 tiles j != i of highest score, equal scores to the lower j
+ *                    (-0 and +0 are equal; a NaN score orders by its bits, so exactly n_sel tiles are selected whatever
+ *                    the data holds)
+ * Writes, all caller-owned:
+ *   sel_tiles[y][i][n_sel]   the selected tiles in ascending tile index (dense int32)
+ *   kv_rows[y*kv_rows_stride_h + i*kv_rows_stride_g + j], j < n_kv = n_sel*tok + t_eff:
+ *                            j < n_sel*tok: q_rows[sel_tiles[y][i][j/tok]*tok + j%tok]; then the t_eff text rows
+ *                            S..S+t_eff-1 (through row_map when one is given).  This is the key list vorta_attn_fwd and
+ *                            the backward entry points read with q_group_len = tok and the same two strides.  The
+ *                            lists are written with 16-byte stores: kv_rows is 16-byte aligned, both strides are
+ *                            multiples of 4 entries, kv_rows_stride_g >= n_kv, kv_rows_stride_h >= n_tiles *
+ *                            kv_rows_stride_g; the entries between n_kv and the next multiple of 4 repeat entry 0.
+ *   ws                       fp32, vorta_sta_select_tiles_ws_floats(args) = n_heads*2*n_tiles*128 floats, 16-byte aligned:
+ *                            [y][q|k][tile][d], the tile means
+ * phases: 0 = both launches; 1 = the tile means only (sel_tiles / kv_rows are not read); 2 = the selection only, from the
+ * means an earlier call left in ws (q / k are not read).
+ * Two launches on the stream (sta_select.hip), no host read, no allocation: graph-capturable.  The sums have a fixed
+ * order: the same inputs give the same lists bit for bit.
+ * VORTA_EINVAL: struct size, null or misaligned pointers or strides, a tile that does not divide the latent grid;
+ * VORTA_EUNSUPPORTED: a dtype other than bf16 / fp16, head_dim != 128, more than 1024 tiles; VORTA_OK with nothing launched
+ * for n_heads == 0.  vorta_sta_select_tiles_ws_floats is host-only and returns VORTA_EINVAL (negative) for bad arguments.
+ */
+typedef struct vorta_sta_select_args {
+  uint32_t struct_size;
+  int32_t dtype, head_dim, n_heads;
+  vorta_tensor q, k; /* (H,S[+T],D) */
+  const int32_t* head_list;
+  const int32_t* n_heads_dev;
+  int32_t latent[3], tile[3], window[3];
+  int32_t t_eff;
+  int32_t phases, reserved;
+  const int32_t* row_map; /* text rows only: the video rows come through q_rows */
+  const int32_t* q_rows;  /* [S] of vorta_sta_build_tables (built with the same row_map) */
+  int32_t* sel_tiles;
+  int32_t* kv_rows;
+  int64_t kv_rows_stride_h, kv_rows_stride_g;
+  float* ws;
+} vorta_sta_select_args;
+
+int vorta_sta_select_tiles(const vorta_sta_select_args* args, void* hip_stream);
+int vorta_sta_select_tiles_args_size(void);
+int64_t vorta_sta_select_tiles_ws_floats(const vorta_sta_select_args* args);
 
 /*
  * vorta_router_route -- vorta/patch/router.py:33-43 (Router.forward) + the top-1 / tau rule of

@@ -60,6 +60,16 @@ class StaArgs(C.Structure):
     ]
 
 
+class StaSelectArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("n_heads", _i32),
+        ("q", Tensor), ("k", Tensor), ("head_list", _vp), ("n_heads_dev", _vp),
+        ("latent", _i32 * 3), ("tile", _i32 * 3), ("window", _i32 * 3), ("t_eff", _i32), ("phases", _i32), ("reserved", _i32),
+        ("row_map", _vp), ("q_rows", _vp), ("sel_tiles", _vp), ("kv_rows", _vp),
+        ("kv_rows_stride_h", _i64), ("kv_rows_stride_g", _i64), ("ws", _vp),
+    ]
+
+
 class RouterArgs(C.Structure):
     _fields_ = [
         ("struct_size", _u32), ("dtype", _i32),
@@ -276,6 +286,9 @@ SYMBOLS = {
     "vorta_sta_partial_sizes": (C.c_int, [C.POINTER(StaArgs), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
                                           C.POINTER(_i32), _i32]),
     "vorta_sta_build_tables_partial": (C.c_int, [C.POINTER(StaArgs), _vp]),
+    "vorta_sta_select_tiles": (C.c_int, [C.POINTER(StaSelectArgs), _vp]),
+    "vorta_sta_select_tiles_args_size": (C.c_int, []),
+    "vorta_sta_select_tiles_ws_floats": (_i64, [C.POINTER(StaSelectArgs)]),
     "vorta_router_route": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
@@ -380,6 +393,9 @@ def lib():
     if h.vorta_route_repair_args_size() != C.sizeof(RouteRepairArgs):
         raise VortaHipError(f"struct layout mismatch for RouteRepairArgs: C {h.vorta_route_repair_args_size()} "
                             f"vs ctypes {C.sizeof(RouteRepairArgs)}")
+    if h.vorta_sta_select_tiles_args_size() != C.sizeof(StaSelectArgs):
+        raise VortaHipError(f"struct layout mismatch for StaSelectArgs: C {h.vorta_sta_select_tiles_args_size()} "
+                            f"vs ctypes {C.sizeof(StaSelectArgs)}")
     _lib = h
     return h
 

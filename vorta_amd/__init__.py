@@ -22,6 +22,16 @@ def set_attention_backward(name: str) -> None:
     _set(name)
 
 
+def set_sliding_keys(name: str) -> None:
+    """Which key tiles the sliding-tile expert attends: "window" (the default: the clamped window of tiles around the query
+    tile, the reference's mask) or "content" (as many tiles, chosen per head and query tile on the device by the product of
+    the tiles' mean q and mean k).  Also: VORTA_SLIDING_KEYS=window|content; read when a geometry is built.
+    "content" is refused by name on a partial geometry, under sequence parallelism and in the per-expert sampled measurement
+    (`sampled_expert_fidelity`, `route_by_fidelity`, `measured_routes`)."""
+    from .routed import set_sliding_keys as _set
+    _set(name)
+
+
 def set_partial_geometry(on: bool) -> None:
     """Accept tile and coreset windows that do not divide the latent grid (off by default; also VORTA_PARTIAL_GEOMETRY=0|1):
     thin last tiles for the sliding-tile expert, the reference's cropped windows plus full-resolution remainder tokens for the

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libvorta_hip.so")
 SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_bwd_dq.hip", "attn_bwd_dkv.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
-           "sta_tables.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "expert_fidelity.hip", "sampled_fidelity.hip",
+           "sta_tables.hip", "sta_select.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "expert_fidelity.hip", "sampled_fidelity.hip",
            "sampled_experts.hip", "route_fidelity.hip", "route_fidelity_tiers.hip", "route_budget_tiers.hip", "route_repair.hip", "permute.hip"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent fp32 adds of the softmax row sum into v_pk_add_f32 plus the
 # v_mov pairs to feed them -- more instructions on the VALU issue port that bounds the attention loop (+2 % without)
@@ -26,7 +26,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # register) does not allow -- it spills 227 registers without this option and none with it
 # (attn_bwd_dkv.hip is that sweep without its dQ half: the same 256 accumulator registers, the same option)
 SOURCE_FLAGS = {"attn_bwd_kmajor.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-                "attn_bwd_dkv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+                "attn_bwd_dkv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                # the tile means are eight independent fp32 sums per lane: kept on the scalar-per-lane fp32 instructions (no
+                # packed fp32 adds), so the order of every sum is the one the source states
+                "sta_select.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(src, dst):

@@ -1,0 +1,284 @@
+// Sliding-tile key tiles chosen by CONTENT for gfx950: include/vorta_hip.h vorta_sta_select_tiles.
+//
+// The window expert of sta_tables.hip gives query tile i the clamped window of tiles around it: a choice by position.  Here
+// the same NUMBER of key tiles (n_sel = cnt_0 cnt_1 cnt_2) is chosen per head and per query tile from the data: tile i
+// itself and the n_sel - 1 tiles j != i with the largest <mean q of tile i, mean k of tile j>, ties to the lower j, emitted
+// in ascending j and expanded through the tile-major q_rows table into the key list the gather attention kernels read
+// (kv_rows[y][i][n_kv], text rows last).  Two launches:
+//   sta_tile_means_kernel     HBM bound: q and k of the selected heads are read once.  One workgroup per (tile, slot, q|k);
+//                             16 lanes hold one 256-byte row as 16-byte loads, so the 256 threads hold 16 rows a pass; row
+//                             ids are fetched a pass ahead of the rows they address; fp32 sums in registers, then ONE
+//                             reduction over the 16 row lanes through LDS in a fixed order (the result repeats bit for bit)
+//   sta_select_expand_kernel  one workgroup per (slot, 4 query tiles), a wave per query tile: the slot's k means pass through
+//                             LDS in chunks of 64 tiles (a lane per key tile, rows padded to 129 floats against bank
+//                             conflicts), scores in fp32 on the vector units, kept as order-preserving integer keys; rank
+//                             by counting, ascending list by ballot + prefix count, then the wave writes its tile's key
+//                             list with 16-byte stores
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vorta_hip.h"
+#include "common.h"
+
+namespace {
+
+constexpr int D = 128;          // head_dim: 16 lanes x 8 elements
+constexpr int ROW_LANES = 16;   // rows of a tile in flight per pass (256 threads / 16 lanes a row)
+constexpr int UNR = 4;          // passes requested before the first is summed
+constexpr int QB = 4;           // query tiles per selection workgroup: one per wave
+constexpr int KT = 64;          // key tiles staged per chunk: one per lane
+constexpr int KPAD = D + 1;     // floats per staged row
+constexpr int MAX_TILES = 1024; // keys and lists of a wave live in LDS: QB x MAX_TILES x (4 + 4) bytes
+
+struct MParams {
+  const char* x[2]; int64_t sh[2], ss[2];  // q, k: byte strides
+  const int32_t* head_list; const int32_t* n_heads_dev; int n_heads;
+  const int32_t* q_rows;
+  int tok, n_tiles;
+  float* ws;  // [n_heads][2][n_tiles][D]
+};
+
+struct EParams {
+  const int32_t* n_heads_dev; int n_heads;
+  const int32_t* q_rows; const int32_t* row_map;
+  int tok, n_tiles, n_sel, S, t_eff, n_kv;
+  const float* ws;
+  int32_t* sel_tiles;
+  int32_t* kv_rows; int64_t kv_sh, kv_sg;
+};
+
+template <typename T> __device__ __forceinline__ float to_f(T v) { return (float)v; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void sta_tile_means_kernel(const MParams p) {
+  typedef __attribute__((ext_vector_type(8))) T V8;
+  __shared__ float part[ROW_LANES][D];
+  const int tile = blockIdx.x, y = blockIdx.y, which = blockIdx.z;
+  if (y >= p.n_heads || (p.n_heads_dev && y >= *p.n_heads_dev)) return;  // (uniform: before any barrier)
+  const int head = p.head_list ? p.head_list[y] : y;
+  const int rl = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  const char* xb = p.x[which] + (int64_t)head * p.sh[which] + sub * 16;
+  const int64_t ss = p.ss[which];
+  const int32_t* rows = p.q_rows + (int64_t)tile * p.tok;
+
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  int ids[UNR];
+#pragma unroll
+  for (int u = 0; u < UNR; ++u) {
+    const int i = rl + ROW_LANES * u;
+    ids[u] = i < p.tok ? rows[i] : 0;
+  }
+  for (int base = rl; base < p.tok; base += ROW_LANES * UNR) {
+    V8 v[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (base + ROW_LANES * u < p.tok) v[u] = *(const V8*)(xb + (int64_t)ids[u] * ss);
+    // the ids of the NEXT passes leave before this pass's rows are summed
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int i = base + ROW_LANES * (UNR + u);
+      ids[u] = i < p.tok ? rows[i] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (base + ROW_LANES * u < p.tok) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += to_f<T>(v[u][j]);
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[rl][sub * 8 + j] = acc[j];
+  __syncthreads();
+  if (threadIdx.x < D) {
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < ROW_LANES; ++r) s += part[r][threadIdx.x];  // fixed order
+    p.ws[(((int64_t)y * 2 + which) * p.n_tiles + tile) * D + threadIdx.x] = s / (float)p.tok;
+  }
+}
+
+// a float as an unsigned key of the same order (-0 first made +0: the two compare equal, so they must tie); a total order,
+// NaNs included, so every query tile selects EXACTLY n_sel tiles whatever the data holds
+__device__ __forceinline__ uint32_t order_key(float s) {
+  const uint32_t b = __float_as_uint(s + 0.f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void sta_select_expand_kernel(const EParams p) {
+  __shared__ float ks[KT][KPAD];
+  __shared__ __attribute__((aligned(16))) float qs[QB][D];
+  __shared__ uint32_t keys[QB][MAX_TILES];
+  __shared__ int32_t sel[QB][MAX_TILES];
+  const int y = blockIdx.y;
+  if (y >= p.n_heads || (p.n_heads_dev && y >= *p.n_heads_dev)) return;  // (uniform: before any barrier)
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * QB + w;
+  const bool active = i < p.n_tiles;  // wave-uniform; an idle wave of the last workgroup still stages and meets the barriers
+  const float* qbar = p.ws + ((int64_t)y * 2 + 0) * p.n_tiles * D;
+  const float* kbar = p.ws + ((int64_t)y * 2 + 1) * p.n_tiles * D;
+  for (int d = lane; d < D; d += 64) qs[w][d] = active ? qbar[(int64_t)i * D + d] : 0.f;
+
+  // ---- scores: lane = key tile of the staged chunk, d ascending ----
+  for (int c0 = 0; c0 < p.n_tiles; c0 += KT) {
+    __syncthreads();  // (the previous chunk is consumed; qs is written)
+    const int n_c = min(KT, p.n_tiles - c0);
+    for (int e = threadIdx.x; e < n_c * (D / 4); e += 256) {
+      const int r = e / (D / 4), d4 = e % (D / 4);
+      const f32x4 v = *(const f32x4*)(kbar + (int64_t)(c0 + r) * D + d4 * 4);
+      ks[r][d4 * 4 + 0] = v[0]; ks[r][d4 * 4 + 1] = v[1]; ks[r][d4 * 4 + 2] = v[2]; ks[r][d4 * 4 + 3] = v[3];
+    }
+    __syncthreads();
+    if (lane < n_c) {
+      float s = 0.f;
+#pragma unroll 8
+      for (int d4 = 0; d4 < D / 4; ++d4) {
+        const f32x4 qv = *(const f32x4*)&qs[w][d4 * 4];  // one address per wave: a broadcast
+        s = fmaf(qv[0], ks[lane][d4 * 4 + 0], s);
+        s = fmaf(qv[1], ks[lane][d4 * 4 + 1], s);
+        s = fmaf(qv[2], ks[lane][d4 * 4 + 2], s);
+        s = fmaf(qv[3], ks[lane][d4 * 4 + 3], s);
+      }
+      keys[w][c0 + lane] = order_key(s);
+    }
+  }
+  if (!active) return;  // (no barrier below: every wave works on rows of its own)
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // ---- selection: rank among j != i by counting, ascending list by ballot + prefix count ----
+  int32_t* sel_out = p.sel_tiles + ((int64_t)y * p.n_tiles + i) * p.n_sel;
+  int n_out = 0;
+  for (int j0 = 0; j0 < p.n_tiles; j0 += 64) {
+    const int j = j0 + lane;
+    bool take = false;
+    if (j < p.n_tiles) {
+      const uint32_t mine = keys[w][j];
+      int rank = 0;
+      for (int o = 0; o < p.n_tiles; ++o) {
+        const uint32_t other = keys[w][o];  // a broadcast
+        rank += (o != i && (other > mine || (other == mine && o < j))) ? 1 : 0;
+      }
+      take = j == i || rank < p.n_sel - 1;
+    }
+    const uint64_t m = __ballot(take);
+    if (take) {
+      const int pos = n_out + __popcll(m & ((1ull << lane) - 1));
+      if (pos < p.n_sel) {  // (always: the order is total, so exactly n_sel tiles are taken)
+        sel[w][pos] = j;
+        sel_out[pos] = j;
+      }
+    }
+    n_out += __popcll(m);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // ---- expansion: entry e < n_sel tok is q_rows[sel[e / tok] tok + e % tok], then the text rows; 4 entries a lane, one
+  // 16-byte store (the strides are multiples of 4 entries).  Entries between n_kv and the next multiple of 4 repeat entry 0
+  int32_t* dst = p.kv_rows + (int64_t)y * p.kv_sh + (int64_t)i * p.kv_sg;
+  const int n_vid = p.n_sel * p.tok;
+  const int first = n_vid ? p.q_rows[(int64_t)sel[w][0] * p.tok] : 0;
+  for (int e0 = lane * 4; e0 < p.n_kv; e0 += 64 * 4) {
+    int t = e0 / p.tok, within = e0 - t * p.tok;
+    int32_t r[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + u;
+      if (e < n_vid) {
+        r[u] = p.q_rows[(int64_t)sel[w][t] * p.tok + within];
+      } else if (e < p.n_kv) {
+        const int x = p.S + (e - n_vid);
+        r[u] = p.row_map ? p.row_map[x] : x;
+      } else {
+        r[u] = first;
+      }
+      if (++within == p.tok) { within = 0; ++t; }
+    }
+    u32x4 out;
+    out[0] = (uint32_t)r[0]; out[1] = (uint32_t)r[1]; out[2] = (uint32_t)r[2]; out[3] = (uint32_t)r[3];
+    *(u32x4*)(dst + e0) = out;
+  }
+}
+
+struct Geometry { int S, tok, n_tiles, n_sel; };
+
+int geometry(const vorta_sta_select_args* a, Geometry& g) {
+  int64_t S = 1, tok = 1, n_tiles = 1, n_sel = 1;
+  for (int d = 0; d < 3; ++d) {
+    if (a->latent[d] <= 0 || a->tile[d] <= 0 || a->window[d] <= 0) return VORTA_EINVAL;
+    if (a->latent[d] % a->tile[d]) return VORTA_EINVAL;  // a dividing geometry, as vorta_sta_build_tables
+    const int nt = a->latent[d] / a->tile[d];
+    S *= a->latent[d]; tok *= a->tile[d]; n_tiles *= nt;
+    n_sel *= min(nt, 2 * (a->window[d] / 2) + 1);
+  }
+  if (a->t_eff < 0 || S + a->t_eff > 0x7fffffff || n_sel * tok + a->t_eff > 0x7fffffff) return VORTA_EINVAL;
+  g.S = (int)S; g.tok = (int)tok; g.n_tiles = (int)n_tiles; g.n_sel = (int)n_sel;
+  return VORTA_OK;
+}
+
+}  // namespace
+
+extern "C" int vorta_sta_select_tiles_args_size(void) { return (int)sizeof(vorta_sta_select_args); }
+
+extern "C" int64_t vorta_sta_select_tiles_ws_floats(const vorta_sta_select_args* a) {
+  Geometry g{};
+  if (!a || a->struct_size != sizeof(vorta_sta_select_args) || a->n_heads < 0 || geometry(a, g) != VORTA_OK) return VORTA_EINVAL;
+  return (int64_t)a->n_heads * 2 * g.n_tiles * D;
+}
+
+extern "C" int vorta_sta_select_tiles(const vorta_sta_select_args* a, void* hip_stream) {
+  if (!a || a->struct_size != sizeof(vorta_sta_select_args)) return VORTA_EINVAL;
+  Geometry g{};
+  int rc = geometry(a, g);
+  if (rc != VORTA_OK) return rc;
+  if (a->dtype != VORTA_BF16 && a->dtype != VORTA_FP16) return VORTA_EUNSUPPORTED;
+  if (a->head_dim != D) return VORTA_EUNSUPPORTED;
+  if (g.n_tiles > MAX_TILES) return VORTA_EUNSUPPORTED;
+  if (a->n_heads < 0 || a->n_heads > 65535 || a->phases < 0 || a->phases > 2) return VORTA_EINVAL;
+  if (a->n_heads == 0) return VORTA_OK;
+  const int n_kv = g.n_sel * g.tok + a->t_eff;
+  const bool means = a->phases != 2, select = a->phases != 1;
+  if (!a->q_rows || !a->ws || ((uintptr_t)a->ws & 15)) return VORTA_EINVAL;
+  if (means) {
+    const vorta_tensor* xs[2] = {&a->q, &a->k};
+    for (const vorta_tensor* x : xs)
+      if (!x->ptr || ((uintptr_t)x->ptr & 15) || (x->stride_s % 8) || (x->stride_h % 8) || x->stride_s < D) return VORTA_EINVAL;
+  }
+  if (select) {
+    if (!a->sel_tiles || !a->kv_rows || ((uintptr_t)a->kv_rows & 15)) return VORTA_EINVAL;
+    // 16-byte stores: both strides in whole groups of 4 entries, a tile's row long enough for its list rounded up to 4
+    if ((a->kv_rows_stride_g % 4) || (a->kv_rows_stride_h % 4) || a->kv_rows_stride_g < n_kv ||
+        a->kv_rows_stride_h < (int64_t)g.n_tiles * a->kv_rows_stride_g)
+      return VORTA_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (means) {
+    MParams m{};
+    const int64_t esz = 2;
+    m.x[0] = (const char*)a->q.ptr; m.sh[0] = a->q.stride_h * esz; m.ss[0] = a->q.stride_s * esz;
+    m.x[1] = (const char*)a->k.ptr; m.sh[1] = a->k.stride_h * esz; m.ss[1] = a->k.stride_s * esz;
+    m.head_list = a->head_list; m.n_heads_dev = a->n_heads_dev; m.n_heads = a->n_heads;
+    m.q_rows = a->q_rows; m.tok = g.tok; m.n_tiles = g.n_tiles; m.ws = a->ws;
+    const dim3 grid((unsigned)g.n_tiles, (unsigned)a->n_heads, 2);
+    if (a->dtype == VORTA_BF16)
+      hipLaunchKernelGGL(sta_tile_means_kernel<__bf16>, grid, dim3(256), 0, st, m);
+    else
+      hipLaunchKernelGGL(sta_tile_means_kernel<_Float16>, grid, dim3(256), 0, st, m);
+  }
+  if (select) {
+    EParams e{};
+    e.n_heads_dev = a->n_heads_dev; e.n_heads = a->n_heads;
+    e.q_rows = a->q_rows; e.row_map = a->row_map;
+    e.tok = g.tok; e.n_tiles = g.n_tiles; e.n_sel = g.n_sel; e.S = g.S; e.t_eff = a->t_eff; e.n_kv = n_kv;
+    e.ws = a->ws; e.sel_tiles = a->sel_tiles;
+    e.kv_rows = a->kv_rows; e.kv_sh = a->kv_rows_stride_h; e.kv_sg = a->kv_rows_stride_g;
+    hipLaunchKernelGGL(sta_select_expand_kernel, dim3((unsigned)((g.n_tiles + QB - 1) / QB), (unsigned)a->n_heads), dim3(256),
+                       0, st, e);
+  }
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? VORTA_OK : vorta_set_hip_error(err);
+}

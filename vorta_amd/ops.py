@@ -199,7 +199,15 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     if q_rows is not None and (q_rows.dim() not in (1, 2) or q_rows.shape[-1] < n_q
                                or (q_rows.dim() == 2 and q_rows.shape[0] < n_heads)):
         raise ValueError(f"q_rows {tuple(q_rows.shape)} does not cover n_q = {n_q} rows for {n_heads} head slots")
-    if kv_rows is not None:
+    kv_per_slot_groups = kv_rows is not None and kv_rows.dim() == 3
+    if kv_per_slot_groups:
+        # (slots, groups, n_kv): a key list per head slot AND query group (ops.sta_select_tiles); the group axis may be padded
+        if kv_rows.dtype != torch.int32 or kv_rows.stride(2) != 1 or kv_rows_stride_g != kv_rows.stride(1) or kv_rows_stride_g <= 0 \
+                or kv_rows.shape[0] < n_heads or kv_rows.shape[1] < n_groups or kv_rows.shape[2] < n_kv \
+                or kv_rows.stride(0) < kv_rows.shape[1] * kv_rows_stride_g:
+            raise ValueError(f"kv_rows {tuple(kv_rows.shape)} (strides {kv_rows.stride()}) does not cover {n_heads} head slots x "
+                             f"{n_groups} groups x {n_kv} keys with kv_rows_stride_g = {kv_rows_stride_g} its group stride")
+    elif kv_rows is not None:
         if kv_rows_stride_g > 0:
             need = (n_groups - 1) * kv_rows_stride_g + n_kv
             if kv_rows.numel() < need or kv_rows_stride_g < 0:
@@ -216,8 +224,10 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     a.q_rows = _ptr(q_rows)
     a.q_rows_stride_h = q_rows.stride(0) if (q_rows is not None and q_rows.dim() == 2) else 0
     a.n_kv, a.kv_row_offset = n_kv, kv_row_offset
-    a.kv_rows = _ptr(kv_rows)
-    if kv_rows is not None and kv_rows_stride_g == 0 and kv_rows.dim() == 2:
+    a.kv_rows = kv_rows.data_ptr() if kv_per_slot_groups else _ptr(kv_rows)
+    if kv_per_slot_groups:
+        a.kv_rows_stride_h = kv_rows.stride(0)
+    elif kv_rows is not None and kv_rows_stride_g == 0 and kv_rows.dim() == 2:
         a.kv_rows_stride_h = kv_rows.stride(0)  # (slots, n_kv): per head slot, one group
     a.kv_rows_stride_g = kv_rows_stride_g
     a.dup_rows = _ptr(dup_rows)
@@ -731,6 +741,60 @@ def sta_build_tables(latent, tile, window, t_eff: int, device, row_map: Optional
     with torch.cuda.device(dev):
         _C.check(_C.lib().vorta_sta_build_tables(C.byref(a), _stream()), "vorta_sta_build_tables")
     return q_rows, kv_rows
+
+
+def sta_select_buffers(n_slots: int, n_tiles: int, n_sel: int, n_kv: int, device):
+    """the caller-owned tables of `sta_select_tiles` for `n_slots` head slots: (kv_rows (slots, n_tiles, n_kv) int32 -- a view
+    whose tile stride is n_kv rounded up to 4 entries, the kernel stores 16 bytes at a time --, sel_tiles (slots, n_tiles,
+    n_sel) int32, ws float32)"""
+    stride = (n_kv + 3) // 4 * 4
+    kv = torch.empty((n_slots, n_tiles, stride), dtype=torch.int32, device=device)[:, :, :n_kv]
+    return (kv, torch.empty((n_slots, n_tiles, n_sel), dtype=torch.int32, device=device),
+            torch.empty(max(n_slots, 1) * 2 * n_tiles * 128, dtype=torch.float32, device=device))
+
+
+def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_eff: int, q_rows: torch.Tensor, *,
+                     head_list: Optional[torch.Tensor] = None, n_heads: Optional[int] = None,
+                     n_heads_dev: Optional[torch.Tensor] = None, row_map: Optional[torch.Tensor] = None,
+                     out=None, phases: int = 0) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """vorta_sta_select_tiles: the sliding-tile expert's key tiles chosen by content.  q, k: (H,N,D) 16-bit, D = 128; `q_rows`
+    the tile-major table of `sta_build_tables` (built with the same `row_map`).  Per head slot and query tile, the tile itself
+    and the n_sel - 1 other tiles of highest <mean q, mean k> (fp32, ties to the lower tile), n_sel the window expert's tile
+    count.  Returns (kv_rows (slots, n_tiles, n_kv) int32 -- the key lists, `kv_rows.stride(1)` the group stride of the launch
+    --, sel_tiles (slots, n_tiles, n_sel) int32 ascending, n_kv).  Slots at or past `n_heads_dev` are not written.
+    out: the (kv_rows, sel_tiles, ws) of `sta_select_buffers` to write into (no allocation then); phases: 0 both launches, 1 the
+    tile means only, 2 the selection from the means `out`'s ws holds.  No host read."""
+    _require_gpu(q, k, q_rows)
+    if q.dtype not in _DT or q.dtype != k.dtype:
+        raise _C.VortaHipError("sta_select_tiles failed: VORTA_EUNSUPPORTED (q, k of one dtype, bf16 or fp16)")
+    n_tiles, tok, n_kv = sta_table_sizes(latent, tile, window, t_eff)
+    n_sel = (n_kv - t_eff) // tok
+    if n_heads is None:
+        n_heads = head_list.numel() if head_list is not None else q.shape[0]
+    if head_list is not None and head_list.numel() < n_heads:
+        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
+    if q_rows.numel() < n_tiles * tok:
+        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
+    if row_map is not None and row_map.numel() < n_tiles * tok + t_eff:
+        raise ValueError(f"row_map holds {row_map.numel()} rows, video and text {n_tiles * tok + t_eff}")
+    kv, sel, ws = out if out is not None else sta_select_buffers(n_heads, n_tiles, n_sel, n_kv, q.device)
+    if kv.dtype != torch.int32 or sel.dtype != torch.int32 or tuple(kv.shape) != (kv.shape[0], n_tiles, n_kv) \
+            or kv.shape[0] < n_heads or kv.stride(2) != 1 or tuple(sel.shape) != (kv.shape[0], n_tiles, n_sel) \
+            or not sel.is_contiguous() or ws.dtype != torch.float32 or ws.numel() < n_heads * 2 * n_tiles * 128:
+        raise ValueError("sta_select_tiles: out= the buffers of sta_select_buffers for at least n_heads slots of this geometry")
+    a = _C.StaSelectArgs()
+    a.struct_size = C.sizeof(_C.StaSelectArgs)
+    a.dtype, a.head_dim, a.n_heads = _DT[q.dtype], q.shape[-1], n_heads
+    a.q, a.k = _tensor(q), _tensor(k)
+    a.head_list, a.n_heads_dev = _ptr(head_list), _ptr(n_heads_dev)
+    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
+    a.t_eff, a.phases = t_eff, phases
+    a.row_map, a.q_rows = _ptr(row_map), _ptr(q_rows)
+    a.sel_tiles, a.kv_rows = sel.data_ptr(), kv.data_ptr()
+    a.kv_rows_stride_h, a.kv_rows_stride_g = kv.stride(0), kv.stride(1)
+    a.ws = ws.data_ptr()
+    _C.check(_C.lib().vorta_sta_select_tiles(C.byref(a), _stream()), "vorta_sta_select_tiles")
+    return kv, sel, n_kv
 
 
 def _sta_args(latent, tile, window, t_eff: int):

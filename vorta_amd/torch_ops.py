@@ -13,6 +13,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::attn_fwd(q,k,v,out, n_q,n_kv, ...)         -> ()    mutates out        vorta_attn_fwd
     vorta::coreset_select(x, latent, group, n_keep, ...) -> (keep_rows, drop_rows)  vorta_coreset_select
     vorta::sta_build_tables(like, latent, tile, window, t_eff, row_map) -> (q_rows, kv_rows)
+    vorta::sta_select_tiles(q, k, q_rows, kv_rows, sel_tiles, ws, latent, tile, window, t_eff, ...)
+                                                      -> ()    mutates kv_rows, sel_tiles, ws   vorta_sta_select_tiles
     vorta::route_scores(scores, tau)                  -> (expert_of_head, head_lists, head_counts)
     vorta::route_fidelity(sq_ref, sq_err, max_rel_error, max_flops_share, work)
                                                       -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
@@ -104,6 +106,24 @@ def _(like, latent, tile, window, t_eff=0, row_map=None):
     n_tiles, _, n_kv = ops.sta_table_sizes(latent, tile, window, t_eff)  # host-only geometry query
     S = latent[0] * latent[1] * latent[2]
     return like.new_empty((S,), dtype=torch.int32), like.new_empty((n_tiles, n_kv), dtype=torch.int32)
+
+
+@torch.library.custom_op("vorta::sta_select_tiles", mutates_args=("kv_rows", "sel_tiles", "ws"), device_types="cuda")
+def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, q_rows: torch.Tensor, kv_rows: torch.Tensor, sel_tiles: torch.Tensor,
+                     ws: torch.Tensor, latent: List[int], tile: List[int], window: List[int], t_eff: int = 0,
+                     head_list: Optional[torch.Tensor] = None, n_heads: int = -1, n_heads_dev: Optional[torch.Tensor] = None,
+                     row_map: Optional[torch.Tensor] = None) -> None:
+    """ops.sta_select_tiles into the caller's tables (`ops.sta_select_buffers`): the key lists `kv_rows` and the chosen tiles
+    `sel_tiles` are written in place, `ws` holds the tile means"""
+    ops.sta_select_tiles(q, k, latent, tile, window, t_eff, q_rows, head_list=head_list,
+                         n_heads=None if n_heads < 0 else n_heads, n_heads_dev=n_heads_dev, row_map=row_map,
+                         out=(kv_rows, sel_tiles, ws))
+
+
+@sta_select_tiles.register_fake
+def _(q, k, q_rows, kv_rows, sel_tiles, ws, latent, tile, window, t_eff=0, head_list=None, n_heads=-1, n_heads_dev=None,
+      row_map=None) -> None:
+    return None
 
 
 @torch.library.custom_op("vorta::route_scores", mutates_args=(), device_types="cuda")
