@@ -633,7 +633,8 @@ int vorta_sta_build_tables_partial(const vorta_sta_args* args, void* hip_stream)
  *   ws                       fp32, vorta_sta_select_tiles_ws_floats(args) = n_heads*2*n_tiles*128 floats, 16-byte aligned:
  *                            [y][q|k][tile][d], the tile means
  * phases: 0 = both launches; 1 = the tile means only (sel_tiles / kv_rows are not read); 2 = the selection only, from the
- * means an earlier call left in ws (q / k are not read).
+ * means an earlier call left in ws (q / k are not read); 3 = the selection only, from a score matrix [y][i][j] (n_tiles x
+ * n_tiles fp32 per slot, dense) that an earlier call -- vorta_sta_tile_mass -- left at the start of ws (q / k are not read).
  * Two launches on the stream (sta_select.hip), no host read, no allocation: graph-capturable.  The sums have a fixed
  * order: the same inputs give the same lists bit for bit.
  * VORTA_EINVAL: struct size, null or misaligned pointers or strides, a tile that does not divide the latent grid;
@@ -660,6 +661,49 @@ typedef struct vorta_sta_select_args {
 int vorta_sta_select_tiles(const vorta_sta_select_args* args, void* hip_stream);
 int vorta_sta_select_tiles_args_size(void);
 int64_t vorta_sta_select_tiles_ws_floats(const vorta_sta_select_args* args);
+
+/*
+ * vorta_sta_tile_mass -- the score matrix of the key-tile selection from SAMPLED ATTENTION MASS (a pure addition: the symbol,
+ * vorta_sta_tile_mass_args_size() and vorta_sta_tile_mass_ws_floats(); no reference counterpart).
+ *
+ * Geometry, q_rows and head slots as vorta_sta_select_tiles.  With r = rows_per_tile (8, 16 or 32, at most tok):
+ *   sampled rows   query tile i is represented by its tile-major positions i*tok + floor((2s+1)*tok / (2r)), s < r, each read
+ *                  through q_rows
+ *   logits         l = scale * sum_d q[x][d] k[p][d] for a sampled row x and EVERY video key position p (through q_rows);
+ *                  16-bit inputs, fp32 accumulation.  Text keys take no part (every list ends with them anyway)
+ *   mass           p_x(j) = sum_{p in tile j} exp(l) / sum_{all video p} exp(l)
+ *   score[y][i][j] = sum over the sampled rows x of tile i, s ascending, of p_x(j)                       (fp32)
+ * Writes ws (fp32, 16-byte aligned, vorta_sta_tile_mass_ws_floats(args) floats): the dense matrix score[y][i][j] at its start
+ * -- where vorta_sta_select_tiles(phases = 3) on the same ws, geometry and slots ranks it by its own rule (tile i itself, then
+ * the n_sel-1 tiles j != i of highest score, ties to the lower j) and writes sel_tiles / kv_rows -- and, behind it, the
+ * per-(sampled row, key tile) partial (max, sum) pairs.  sel_tiles, kv_rows and row_map are carried for that second call and
+ * not read here.
+ * Two launches on the stream (sta_mass.hip: a Q K^T-only MFMA loop, then a reduction), no host read, no allocation, no
+ * atomics: graph-capturable, and the same inputs give the same scores bit for bit.
+ * Error codes as vorta_sta_select_tiles; VORTA_EINVAL also for rows_per_tile outside {8, 16, 32} or above tok, and for a
+ * scale that is not positive and finite.
+ */
+typedef struct vorta_sta_mass_args {
+  uint32_t struct_size;
+  int32_t dtype, head_dim, n_heads;
+  vorta_tensor q, k; /* (H,S[+T],D) */
+  const int32_t* head_list;
+  const int32_t* n_heads_dev;
+  int32_t latent[3], tile[3], window[3];
+  int32_t t_eff;
+  int32_t rows_per_tile;
+  float scale;
+  const int32_t* row_map;
+  const int32_t* q_rows;
+  int32_t* sel_tiles;
+  int32_t* kv_rows;
+  int64_t kv_rows_stride_h, kv_rows_stride_g;
+  float* ws;
+} vorta_sta_mass_args;
+
+int vorta_sta_tile_mass(const vorta_sta_mass_args* args, void* hip_stream);
+int vorta_sta_tile_mass_args_size(void);
+int64_t vorta_sta_tile_mass_ws_floats(const vorta_sta_mass_args* args);
 
 /*
  * vorta_router_route -- vorta/patch/router.py:33-43 (Router.forward) + the top-1 / tau rule of

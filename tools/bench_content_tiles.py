@@ -10,12 +10,16 @@
 #                                  workgroups (+ Hunyuan's text-query launch, in every arm)
 #   content_br256 / content_br128  the same heads with content lists: selection + the un-merged launch (a tile is a group)
 #   content_launch_br256 / _br128  that launch alone, over lists already selected
-# and the ratios of the content arms to window_merged.
+#   mass_scores / mass_select      the mass statistic alone (ops.sta_tile_mass: the MFMA scoring launch + the reduction), and
+#                                  the whole mass selection (those two + the rank and expansion from its matrix)
+#   mass_br256 / mass_br128        the same heads under sliding_keys="mass": mass selection + the un-merged launch
+# and the ratios of the content and mass arms to window_merged.
 # accuracy: the structured families of tests/_structured_inputs.py (local, redundant, white), every head on the sliding
-# expert: per head rel_error = |out - dense| / |dense| over the video rows, for window and for content lists.
+# expert: per head rel_error = |out - dense| / |dense| over the video rows, for window, content and mass lists.
 #
 # usage: python tools/bench_content_tiles.py timing --config hunyuan-129f --config wan14b-81f --out profiles/content_tiles_timing.json
 #        python tools/bench_content_tiles.py accuracy --config hunyuan-129f --config wan14b-81f --out profiles/content_tiles_accuracy.txt
+#        (with the mass arms: profiles/mass_tiles_timing.json, profiles/mass_tiles_accuracy.txt)
 import argparse
 import json
 import os
@@ -50,6 +54,11 @@ def timing_of(a, config):
     bufs = content.content_buffers(te, n)
     select = lambda phases: ops.sta_select_tiles(q[0], k[0], cfg["latent"], cfg["tile"], cfg["window"], te, q_rows, out=bufs,  # noqa: E731
                                                  phases=phases, **slots)
+    from vorta_amd.routed import MASS_ROWS_PER_TILE
+    mass = RoutedGeometry(cfg["latent"], cfg["tile"], cfg["window"], cfg["group"], cfg["rate"], dev, sliding_keys="mass")
+    mass.prebuild(te, content_slots=n)
+    mbufs = mass.content_buffers(te, n)
+    mass_kw = dict(scale=kw.get("scale"), rows_per_tile=MASS_ROWS_PER_TILE)
     launches = {}
     for br in (256, 128):
         rec = []
@@ -57,7 +66,13 @@ def timing_of(a, config):
         launches[br] = rec  # (a recorded call keeps lists of its own)
     arms = {"select_both": lambda: select(0), "tile_means": lambda: select(1), "select_expand": lambda: select(2),
             "window_merged": lambda: routed_attention(q, k, v, routing, window, out=out, fp8=False, **kw)}
+    arms["mass_scores"] = lambda: ops.sta_tile_mass(q[0], k[0], cfg["latent"], cfg["tile"], cfg["window"], te, q_rows, mbufs[2],
+                                                    **mass_kw, **slots)
+    arms["mass_select"] = lambda: ops.sta_select_tiles(q[0], k[0], cfg["latent"], cfg["tile"], cfg["window"], te, q_rows, out=mbufs,
+                                                       scores="mass", **mass_kw, **slots)
     for br in (256, 128):
+        arms[f"mass_br{br}"] = lambda br=br: routed_attention(q, k, v, routing, mass, out=out, fp8=False,
+                                                              sliding_block_rows=br, **kw)
         arms[f"content_br{br}"] = lambda br=br: routed_attention(q, k, v, routing, content, out=out, fp8=False,
                                                                  sliding_block_rows=br, **kw)
         arms[f"content_launch_br{br}"] = lambda br=br: ops.attn_fwd_batch([dict(c) for c in launches[br]])
@@ -66,8 +81,11 @@ def timing_of(a, config):
     n_tiles, tok, _ = ops.sta_table_sizes(cfg["latent"], cfg["tile"], cfg["window"], te)
     return {"config": config, "dtype": str(dt), "S": S, "heads": H, "sliding_heads": n, "n_tiles": n_tiles, "tok": tok, "n_kv": n_kv,
             "inputs": "white noise", "rounds": a.rounds, "device": torch.cuda.get_device_name(0), "arms": res,
-            "bytes": {"tile_means_read": 2 * n * S * 128 * q.element_size(), "key_lists_written": n * n_tiles * n_kv * 4},
-            "ratio_to_window_merged": {name: round(res[name]["median_ms"] / base, 4) for name in res if name.startswith("content")}}
+            "bytes": {"tile_means_read": 2 * n * S * 128 * q.element_size(), "key_lists_written": n * n_tiles * n_kv * 4,
+                      "mass_pairs_written": n * n_tiles * MASS_ROWS_PER_TILE * n_tiles * 8},
+            "mass_rows_per_tile": MASS_ROWS_PER_TILE, "mass_score_flop": 2.0 * n * n_tiles * MASS_ROWS_PER_TILE * S * 128,
+            "ratio_to_window_merged": {name: round(res[name]["median_ms"] / base, 4) for name in res
+                                       if name.startswith(("content", "mass_br"))}}
 
 
 def accuracy_of(a, config, lines):
@@ -77,7 +95,7 @@ def accuracy_of(a, config, lines):
     dev, dt = torch.device("cuda:0"), torch.float16 if cfg["dtype"] == "fp16" else torch.bfloat16
     latent, S = cfg["latent"], cfg["latent"][0] * cfg["latent"][1] * cfg["latent"][2]
     geoms = {name: RoutedGeometry(latent, cfg["tile"], cfg["window"], cfg["group"], cfg["rate"], dev, sliding_keys=name)
-             for name in ("window", "content")}
+             for name in ("window", "content", "mass")}
     lines.append(f"\n==== {config}: S = {S}, {dt}, every head on the sliding-tile expert, {torch.cuda.get_device_name(0)}")
     for noise in a.noise:
         gen = torch.Generator(device=dev).manual_seed(11)
@@ -89,9 +107,10 @@ def accuracy_of(a, config, lines):
             out = routed_attention(q, k, v, HeadRouting.from_expert_ids([2, 2, 2], dev), geom, **kw).float()
             rel[name] = ((out - dense)[0].flatten(1).norm(dim=1) / dense[0].flatten(1).norm(dim=1)).tolist()
         for h, fam in enumerate(FAMILIES):
-            w, c = rel["window"][h], rel["content"][h]
-            lines.append(f"noise {noise}: {fam:9s} head: rel_error window {w:.5f} content {c:.5f}  "
-                         f"({'content better' if c < w else 'content worse' if c > w else 'equal'})")
+            w, c, m = rel["window"][h], rel["content"][h], rel["mass"][h]
+            lines.append(f"noise {noise}: {fam:9s} head: rel_error window {w:.5f} content {c:.5f} mass {m:.5f}  "
+                         f"({'content better' if c < w else 'content worse' if c > w else 'equal'}; "
+                         f"{'mass better' if m < w else 'mass worse' if m > w else 'mass equal'})")
 
 
 def main():
@@ -110,7 +129,8 @@ def main():
         text = json.dumps({"tool": "tools/bench_content_tiles.py timing", "runs": [timing_of(a, c) for c in configs]}, indent=1)
     else:
         lines = ["tools/bench_content_tiles.py accuracy: per-head rel_error of the sliding-tile expert against dense attention "
-                 "(|out - dense| / |dense| over the video rows), window key tiles and content-chosen key tiles"]
+                 "(|out - dense| / |dense| over the video rows), window key tiles, content-chosen key tiles (tile means) and "
+                 "mass-chosen key tiles (sampled attention mass)"]
         for c in configs:
             accuracy_of(a, c, lines)
         text = "\n".join(lines)

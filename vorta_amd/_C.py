@@ -70,6 +70,17 @@ class StaSelectArgs(C.Structure):
     ]
 
 
+class StaMassArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("dtype", _i32), ("head_dim", _i32), ("n_heads", _i32),
+        ("q", Tensor), ("k", Tensor), ("head_list", _vp), ("n_heads_dev", _vp),
+        ("latent", _i32 * 3), ("tile", _i32 * 3), ("window", _i32 * 3), ("t_eff", _i32), ("rows_per_tile", _i32),
+        ("scale", C.c_float),
+        ("row_map", _vp), ("q_rows", _vp), ("sel_tiles", _vp), ("kv_rows", _vp),
+        ("kv_rows_stride_h", _i64), ("kv_rows_stride_g", _i64), ("ws", _vp),
+    ]
+
+
 class RouterArgs(C.Structure):
     _fields_ = [
         ("struct_size", _u32), ("dtype", _i32),
@@ -289,6 +300,9 @@ SYMBOLS = {
     "vorta_sta_select_tiles": (C.c_int, [C.POINTER(StaSelectArgs), _vp]),
     "vorta_sta_select_tiles_args_size": (C.c_int, []),
     "vorta_sta_select_tiles_ws_floats": (_i64, [C.POINTER(StaSelectArgs)]),
+    "vorta_sta_tile_mass": (C.c_int, [C.POINTER(StaMassArgs), _vp]),
+    "vorta_sta_tile_mass_args_size": (C.c_int, []),
+    "vorta_sta_tile_mass_ws_floats": (_i64, [C.POINTER(StaMassArgs)]),
     "vorta_router_route": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
@@ -396,6 +410,9 @@ def lib():
     if h.vorta_sta_select_tiles_args_size() != C.sizeof(StaSelectArgs):
         raise VortaHipError(f"struct layout mismatch for StaSelectArgs: C {h.vorta_sta_select_tiles_args_size()} "
                             f"vs ctypes {C.sizeof(StaSelectArgs)}")
+    if h.vorta_sta_tile_mass_args_size() != C.sizeof(StaMassArgs):
+        raise VortaHipError(f"struct layout mismatch for StaMassArgs: C {h.vorta_sta_tile_mass_args_size()} "
+                            f"vs ctypes {C.sizeof(StaMassArgs)}")
     _lib = h
     return h
 

@@ -24,9 +24,11 @@ def set_attention_backward(name: str) -> None:
 
 def set_sliding_keys(name: str) -> None:
     """Which key tiles the sliding-tile expert attends: "window" (the default: the clamped window of tiles around the query
-    tile, the reference's mask) or "content" (as many tiles, chosen per head and query tile on the device by the product of
-    the tiles' mean q and mean k).  Also: VORTA_SLIDING_KEYS=window|content; read when a geometry is built.
-    "content" is refused by name on a partial geometry, under sequence parallelism and in the per-expert sampled measurement
+    tile, the reference's mask), "content" (as many tiles, chosen per head and query tile on the device by the product of
+    the tiles' mean q and mean k) or "mass" (as many tiles, chosen by the share of softmax mass that 16
+    sampled query rows of the tile put on each key tile, scored on the matrix pipe).  Also:
+    VORTA_SLIDING_KEYS=window|content|mass; read when a geometry is built.
+    "content" and "mass" are refused by name on a partial geometry, under sequence parallelism and in the per-expert sampled measurement
     (`sampled_expert_fidelity`, `route_by_fidelity`, `measured_routes`)."""
     from .routed import set_sliding_keys as _set
     _set(name)

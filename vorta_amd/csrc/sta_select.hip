@@ -14,13 +14,18 @@
 //                             conflicts), scores in fp32 on the vector units, kept as order-preserving integer keys; rank
 //                             by counting, ascending list by ballot + prefix count, then the wave writes its tile's key
 //                             list with 16-byte stores
+// phases = 3 ranks a score matrix another statistic left in ws (sta_mass.hip) with the same rank, ballot and stores: the
+// wave's keys come from its row of the matrix in place of the staged means.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vorta_hip.h"
 #include "common.h"
+#include "sta_geometry.h"
 
 namespace {
+using vorta_sta::Geometry;
+using vorta_sta::MAX_TILES;
 
 constexpr int D = 128;          // head_dim: 16 lanes x 8 elements
 constexpr int ROW_LANES = 16;   // rows of a tile in flight per pass (256 threads / 16 lanes a row)
@@ -28,7 +33,7 @@ constexpr int UNR = 4;          // passes requested before the first is summed
 constexpr int QB = 4;           // query tiles per selection workgroup: one per wave
 constexpr int KT = 64;          // key tiles staged per chunk: one per lane
 constexpr int KPAD = D + 1;     // floats per staged row
-constexpr int MAX_TILES = 1024; // keys and lists of a wave live in LDS: QB x MAX_TILES x (4 + 4) bytes
+// (vorta_sta::MAX_TILES: keys and lists of a wave live in LDS: QB x MAX_TILES x (4 + 4) bytes)
 
 struct MParams {
   const char* x[2]; int64_t sh[2], ss[2];  // q, k: byte strides
@@ -43,6 +48,7 @@ struct EParams {
   const int32_t* q_rows; const int32_t* row_map;
   int tok, n_tiles, n_sel, S, t_eff, n_kv;
   const float* ws;
+  const float* scores;  // phases 3: score[y][i][j] of another statistic (sta_mass.hip), ranked in place of <mean q, mean k>
   int32_t* sel_tiles;
   int32_t* kv_rows; int64_t kv_sh, kv_sg;
 };
@@ -118,10 +124,16 @@ __global__ __launch_bounds__(256) void sta_select_expand_kernel(const EParams p)
   const bool active = i < p.n_tiles;  // wave-uniform; an idle wave of the last workgroup still stages and meets the barriers
   const float* qbar = p.ws + ((int64_t)y * 2 + 0) * p.n_tiles * D;
   const float* kbar = p.ws + ((int64_t)y * 2 + 1) * p.n_tiles * D;
-  for (int d = lane; d < D; d += 64) qs[w][d] = active ? qbar[(int64_t)i * D + d] : 0.f;
+  if (p.scores) {
+    // ---- scores given: the wave's row of the matrix becomes its keys (no barrier on this path) ----
+    if (active)
+      for (int j = lane; j < p.n_tiles; j += 64) keys[w][j] = order_key(p.scores[((int64_t)y * p.n_tiles + i) * p.n_tiles + j]);
+  } else {
+    for (int d = lane; d < D; d += 64) qs[w][d] = active ? qbar[(int64_t)i * D + d] : 0.f;
+  }
 
   // ---- scores: lane = key tile of the staged chunk, d ascending ----
-  for (int c0 = 0; c0 < p.n_tiles; c0 += KT) {
+  for (int c0 = 0; !p.scores && c0 < p.n_tiles; c0 += KT) {
     __syncthreads();  // (the previous chunk is consumed; qs is written)
     const int n_c = min(KT, p.n_tiles - c0);
     for (int e = threadIdx.x; e < n_c * (D / 4); e += 256) {
@@ -204,21 +216,7 @@ __global__ __launch_bounds__(256) void sta_select_expand_kernel(const EParams p)
   }
 }
 
-struct Geometry { int S, tok, n_tiles, n_sel; };
-
-int geometry(const vorta_sta_select_args* a, Geometry& g) {
-  int64_t S = 1, tok = 1, n_tiles = 1, n_sel = 1;
-  for (int d = 0; d < 3; ++d) {
-    if (a->latent[d] <= 0 || a->tile[d] <= 0 || a->window[d] <= 0) return VORTA_EINVAL;
-    if (a->latent[d] % a->tile[d]) return VORTA_EINVAL;  // a dividing geometry, as vorta_sta_build_tables
-    const int nt = a->latent[d] / a->tile[d];
-    S *= a->latent[d]; tok *= a->tile[d]; n_tiles *= nt;
-    n_sel *= min(nt, 2 * (a->window[d] / 2) + 1);
-  }
-  if (a->t_eff < 0 || S + a->t_eff > 0x7fffffff || n_sel * tok + a->t_eff > 0x7fffffff) return VORTA_EINVAL;
-  g.S = (int)S; g.tok = (int)tok; g.n_tiles = (int)n_tiles; g.n_sel = (int)n_sel;
-  return VORTA_OK;
-}
+int geometry(const vorta_sta_select_args* a, Geometry& g) { return vorta_sta::geometry(a->latent, a->tile, a->window, a->t_eff, g); }
 
 }  // namespace
 
@@ -238,10 +236,10 @@ extern "C" int vorta_sta_select_tiles(const vorta_sta_select_args* a, void* hip_
   if (a->dtype != VORTA_BF16 && a->dtype != VORTA_FP16) return VORTA_EUNSUPPORTED;
   if (a->head_dim != D) return VORTA_EUNSUPPORTED;
   if (g.n_tiles > MAX_TILES) return VORTA_EUNSUPPORTED;
-  if (a->n_heads < 0 || a->n_heads > 65535 || a->phases < 0 || a->phases > 2) return VORTA_EINVAL;
+  if (a->n_heads < 0 || a->n_heads > 65535 || a->phases < 0 || a->phases > 3) return VORTA_EINVAL;
   if (a->n_heads == 0) return VORTA_OK;
   const int n_kv = g.n_sel * g.tok + a->t_eff;
-  const bool means = a->phases != 2, select = a->phases != 1;
+  const bool means = a->phases < 2, select = a->phases != 1;
   if (!a->q_rows || !a->ws || ((uintptr_t)a->ws & 15)) return VORTA_EINVAL;
   if (means) {
     const vorta_tensor* xs[2] = {&a->q, &a->k};
@@ -274,7 +272,7 @@ extern "C" int vorta_sta_select_tiles(const vorta_sta_select_args* a, void* hip_
     e.n_heads_dev = a->n_heads_dev; e.n_heads = a->n_heads;
     e.q_rows = a->q_rows; e.row_map = a->row_map;
     e.tok = g.tok; e.n_tiles = g.n_tiles; e.n_sel = g.n_sel; e.S = g.S; e.t_eff = a->t_eff; e.n_kv = n_kv;
-    e.ws = a->ws; e.sel_tiles = a->sel_tiles;
+    e.ws = a->ws; e.scores = a->phases == 3 ? a->ws : nullptr; e.sel_tiles = a->sel_tiles;
     e.kv_rows = a->kv_rows; e.kv_sh = a->kv_rows_stride_h; e.kv_sg = a->kv_rows_stride_g;
     hipLaunchKernelGGL(sta_select_expand_kernel, dim3((unsigned)((g.n_tiles + QB - 1) / QB), (unsigned)a->n_heads), dim3(256),
                        0, st, e);

@@ -743,28 +743,86 @@ def sta_build_tables(latent, tile, window, t_eff: int, device, row_map: Optional
     return q_rows, kv_rows
 
 
-def sta_select_buffers(n_slots: int, n_tiles: int, n_sel: int, n_kv: int, device):
+SELECT_SCORES = ("mean", "mass")  # the statistic `sta_select_tiles` ranks key tiles by
+
+
+def sta_mass_ws_floats(n_slots: int, n_tiles: int, rows_per_tile: int) -> int:
+    """vorta_sta_tile_mass_ws_floats: the score matrices (rounded up to 4 floats), then a (max, sum) pair per (sampled row, key
+    tile)"""
+    return (n_slots * n_tiles * n_tiles + 3) // 4 * 4 + n_slots * n_tiles * rows_per_tile * n_tiles * 2
+
+
+def sta_select_buffers(n_slots: int, n_tiles: int, n_sel: int, n_kv: int, device, scores: str = "mean", rows_per_tile: int = 16):
     """the caller-owned tables of `sta_select_tiles` for `n_slots` head slots: (kv_rows (slots, n_tiles, n_kv) int32 -- a view
     whose tile stride is n_kv rounded up to 4 entries, the kernel stores 16 bytes at a time --, sel_tiles (slots, n_tiles,
-    n_sel) int32, ws float32)"""
+    n_sel) int32, ws float32 -- sized for the statistic `scores`: the tile means, or the mass statistic's score matrix and
+    pairs at `rows_per_tile`)"""
+    if scores not in SELECT_SCORES:
+        raise ValueError(f"sta_select_buffers: unknown scores {scores!r} (one of {', '.join(SELECT_SCORES)})")
     stride = (n_kv + 3) // 4 * 4
     kv = torch.empty((n_slots, n_tiles, stride), dtype=torch.int32, device=device)[:, :, :n_kv]
+    slots = max(n_slots, 1)
+    ws_floats = slots * 2 * n_tiles * 128 if scores == "mean" else sta_mass_ws_floats(slots, n_tiles, rows_per_tile)
     return (kv, torch.empty((n_slots, n_tiles, n_sel), dtype=torch.int32, device=device),
-            torch.empty(max(n_slots, 1) * 2 * n_tiles * 128, dtype=torch.float32, device=device))
+            torch.empty(ws_floats, dtype=torch.float32, device=device))
+
+
+def sta_tile_mass(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_eff: int, q_rows: torch.Tensor, ws: torch.Tensor, *,
+                  scale: Optional[float] = None, rows_per_tile: int = 16, head_list: Optional[torch.Tensor] = None,
+                  n_heads: Optional[int] = None, n_heads_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vorta_sta_tile_mass: the key-tile score matrix from sampled attention mass.  q, k: (H,N,D) 16-bit, D = 128; `q_rows` the
+    tile-major table of `sta_build_tables`.  Per head slot, `rows_per_tile` evenly spaced rows of every query tile are scored
+    against every video key (MFMA, no V); score[y][i][j] is the sum over tile i's sampled rows of the share of the row's
+    softmax mass (at `scale`, default D^-0.5) on key tile j.  Written to the start of `ws` (float32, at least
+    `sta_mass_ws_floats` floats), where `sta_select_tiles(phases=3)` ranks it; returns that (slots, n_tiles, n_tiles) view.
+    Two launches, no host read, no allocation."""
+    _require_gpu(q, k, q_rows, ws)
+    if q.dtype not in _DT or q.dtype != k.dtype:
+        raise _C.VortaHipError("sta_tile_mass failed: VORTA_EUNSUPPORTED (q, k of one dtype, bf16 or fp16)")
+    n_tiles, tok, _ = sta_table_sizes(latent, tile, window, t_eff)
+    if n_heads is None:
+        n_heads = head_list.numel() if head_list is not None else q.shape[0]
+    if head_list is not None and head_list.numel() < n_heads:
+        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
+    if q_rows.numel() < n_tiles * tok:
+        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
+    a = _C.StaMassArgs()
+    a.struct_size = C.sizeof(_C.StaMassArgs)
+    a.dtype, a.head_dim, a.n_heads = _DT[q.dtype], q.shape[-1], n_heads
+    a.q, a.k = _tensor(q), _tensor(k)
+    a.head_list, a.n_heads_dev = _ptr(head_list), _ptr(n_heads_dev)
+    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
+    a.t_eff, a.rows_per_tile = t_eff, rows_per_tile
+    a.scale = float(q.shape[-1]) ** -0.5 if scale is None else float(scale)
+    a.q_rows, a.ws = _ptr(q_rows), ws.data_ptr()
+    need = _C.lib().vorta_sta_tile_mass_ws_floats(C.byref(a))
+    _C.check(min(need, 0), "vorta_sta_tile_mass_ws_floats")
+    if ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"sta_tile_mass: ws holds {ws.numel()} float32, the statistic needs {need} (sta_select_buffers(scores='mass'))")
+    _C.check(_C.lib().vorta_sta_tile_mass(C.byref(a), _stream()), "vorta_sta_tile_mass")
+    return ws[:n_heads * n_tiles * n_tiles].view(n_heads, n_tiles, n_tiles)
 
 
 def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_eff: int, q_rows: torch.Tensor, *,
                      head_list: Optional[torch.Tensor] = None, n_heads: Optional[int] = None,
                      n_heads_dev: Optional[torch.Tensor] = None, row_map: Optional[torch.Tensor] = None,
-                     out=None, phases: int = 0) -> Tuple[torch.Tensor, torch.Tensor, int]:
+                     out=None, phases: int = 0, scores: str = "mean", scale: Optional[float] = None,
+                     rows_per_tile: int = 16) -> Tuple[torch.Tensor, torch.Tensor, int]:
     """vorta_sta_select_tiles: the sliding-tile expert's key tiles chosen by content.  q, k: (H,N,D) 16-bit, D = 128; `q_rows`
     the tile-major table of `sta_build_tables` (built with the same `row_map`).  Per head slot and query tile, the tile itself
     and the n_sel - 1 other tiles of highest <mean q, mean k> (fp32, ties to the lower tile), n_sel the window expert's tile
     count.  Returns (kv_rows (slots, n_tiles, n_kv) int32 -- the key lists, `kv_rows.stride(1)` the group stride of the launch
     --, sel_tiles (slots, n_tiles, n_sel) int32 ascending, n_kv).  Slots at or past `n_heads_dev` are not written.
     out: the (kv_rows, sel_tiles, ws) of `sta_select_buffers` to write into (no allocation then); phases: 0 both launches, 1 the
-    tile means only, 2 the selection from the means `out`'s ws holds.  No host read."""
+    tile means only, 2 the selection from the means `out`'s ws holds, 3 the selection from a score matrix there.  No host read.
+    scores="mass" (phases 0 only): the tiles are ranked by sampled attention mass, not by the means -- `sta_tile_mass` at
+    `scale` and `rows_per_tile`, then the selection from its matrix: three launches; `out` from
+    `sta_select_buffers(..., scores="mass", rows_per_tile=)`."""
     _require_gpu(q, k, q_rows)
+    if scores not in SELECT_SCORES:
+        raise ValueError(f"sta_select_tiles: unknown scores {scores!r} (one of {', '.join(SELECT_SCORES)})")
+    if scores == "mass" and phases != 0:
+        raise ValueError("sta_select_tiles: scores='mass' is the whole selection (phases=0); sta_tile_mass is its first part")
     if q.dtype not in _DT or q.dtype != k.dtype:
         raise _C.VortaHipError("sta_select_tiles failed: VORTA_EUNSUPPORTED (q, k of one dtype, bf16 or fp16)")
     n_tiles, tok, n_kv = sta_table_sizes(latent, tile, window, t_eff)
@@ -777,10 +835,11 @@ def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_e
         raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
     if row_map is not None and row_map.numel() < n_tiles * tok + t_eff:
         raise ValueError(f"row_map holds {row_map.numel()} rows, video and text {n_tiles * tok + t_eff}")
-    kv, sel, ws = out if out is not None else sta_select_buffers(n_heads, n_tiles, n_sel, n_kv, q.device)
+    kv, sel, ws = out if out is not None else sta_select_buffers(n_heads, n_tiles, n_sel, n_kv, q.device, scores, rows_per_tile)
+    ws_floats = n_heads * n_tiles * n_tiles if phases == 3 else n_heads * 2 * n_tiles * 128
     if kv.dtype != torch.int32 or sel.dtype != torch.int32 or tuple(kv.shape) != (kv.shape[0], n_tiles, n_kv) \
             or kv.shape[0] < n_heads or kv.stride(2) != 1 or tuple(sel.shape) != (kv.shape[0], n_tiles, n_sel) \
-            or not sel.is_contiguous() or ws.dtype != torch.float32 or ws.numel() < n_heads * 2 * n_tiles * 128:
+            or not sel.is_contiguous() or ws.dtype != torch.float32 or (scores == "mean" and ws.numel() < ws_floats):
         raise ValueError("sta_select_tiles: out= the buffers of sta_select_buffers for at least n_heads slots of this geometry")
     a = _C.StaSelectArgs()
     a.struct_size = C.sizeof(_C.StaSelectArgs)
@@ -788,6 +847,10 @@ def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_e
     a.q, a.k = _tensor(q), _tensor(k)
     a.head_list, a.n_heads_dev = _ptr(head_list), _ptr(n_heads_dev)
     a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
+    if scores == "mass":  # (checks ws against the statistic's own size)
+        sta_tile_mass(q, k, latent, tile, window, t_eff, q_rows, ws, scale=scale, rows_per_tile=rows_per_tile,
+                      head_list=head_list, n_heads=n_heads, n_heads_dev=n_heads_dev)
+        phases = 3
     a.t_eff, a.phases = t_eff, phases
     a.row_map, a.q_rows = _ptr(row_map), _ptr(q_rows)
     a.sel_tiles, a.kv_rows = sel.data_ptr(), kv.data_ptr()

@@ -512,8 +512,8 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     if SP_STATE.enabled:
         raise NotImplementedError("measured_routes: routing by a measurement does not run under sequence parallelism")
     from .. import routed as _routed
-    if _routed.sliding_keys_of(None) == "content":  # (the processors' geometries follow the process-wide switch)
-        raise ValueError("measured_routes: " + _routed._NO_SAMPLED_CONTENT)
+    if _routed.sliding_keys_of(None) != "window":  # (the processors' geometries follow the process-wide switch)
+        raise ValueError("measured_routes: " + _routed.no_sampled_measurement(_routed.sliding_keys_of(None)))
     bound = _check_repair_above("measured_routes", repair_above)
     if bound is not None:
         from ..routed import precision_of

@@ -21,11 +21,18 @@ from ._partial import partial_geometry, set_partial_geometry  # noqa: F401  (the
 Triple = Tuple[int, int, int]
 
 
-SLIDING_KEYS = ("window", "content")
+SLIDING_KEYS = ("window", "content", "mass")
+_SELECT_SCORES = {"content": "mean", "mass": "mass"}  # the statistic ops.sta_select_tiles ranks by, per selecting choice
+MASS_ROWS_PER_TILE = 16  # sampled query rows that stand for a query tile under "mass" 
 _sliding_keys: Optional[str] = None  # the process-wide default; None = not set: VORTA_SLIDING_KEYS, else "window"
 _NO_SAMPLED_CONTENT = ("sliding_keys='content': the sampled sliding candidate is built from the key lists every head of a "
                        "length class shares (RoutedGeometry.sample_tables); the per-head sampled form of content-chosen "
                        "lists is missing -- measure under 'window', or verify what was launched (fidelity=, repair_above=)")
+
+
+def no_sampled_measurement(keys: str) -> str:
+    """the refusal of the per-expert sampled measurement under a selecting choice of key tiles, by its name"""
+    return _NO_SAMPLED_CONTENT.replace("'content'", repr(keys), 1)
 
 
 def _check_sliding_keys(name, where: str) -> str:
@@ -36,8 +43,9 @@ def _check_sliding_keys(name, where: str) -> str:
 
 def set_sliding_keys(name: str) -> None:
     """the process-wide choice of the sliding-tile expert's key tiles: "window" (the clamped window of tiles around the query
-    tile: the reference's mask) or "content" (as many tiles, chosen per head and query tile by <mean q, mean k>:
-    ops.sta_select_tiles).  Overrides the environment switch VORTA_SLIDING_KEYS; read when a geometry is built."""
+    tile: the reference's mask), "content" (as many tiles, chosen per head and query tile by <mean q, mean k>:
+    ops.sta_select_tiles) or "mass" (as many tiles, chosen by the attention mass that sampled query rows of the
+    tile put on every key tile: ops.sta_tile_mass).  Overrides the environment switch VORTA_SLIDING_KEYS; read when a geometry is built."""
     global _sliding_keys
     _sliding_keys = _check_sliding_keys(name, "set_sliding_keys")
 
@@ -185,8 +193,8 @@ class RoutedGeometry:
     # accept a tile / coreset window that does not divide the latent grid (DESIGN.md "Partial geometry"); None = the
     # process-wide switch (set_partial_geometry / VORTA_PARTIAL_GEOMETRY).  A geometry that divides is built as ever.
     partial: Optional[bool] = None
-    # which key tiles the sliding-tile expert attends: "window" (by position) or "content" (ops.sta_select_tiles, per call and
-    # head); None = the process-wide switch (set_sliding_keys / VORTA_SLIDING_KEYS).  "window" builds and launches what it always did
+    # which key tiles the sliding-tile expert attends: "window" (by position), "content" or "mass" (ops.sta_select_tiles, per
+    # call and head, ranked by tile means or by sampled attention mass); None = the process-wide switch (set_sliding_keys / VORTA_SLIDING_KEYS).  "window" builds and launches what it always did
     sliding_keys: Optional[str] = None
 
     def __post_init__(self):
@@ -198,12 +206,12 @@ class RoutedGeometry:
         # is_partial: the tables, launches and lists below differ from the dividing ones only then
         self.is_partial = self.partial and not _partial.divides(self.latent, self.tile, self.group)
         self.sliding_keys = sliding_keys_of(self.sliding_keys)
-        if self.sliding_keys == "content":
+        if self.sliding_keys in _SELECT_SCORES:
             if self.is_partial:
-                raise ValueError("sliding_keys='content' on a partial geometry: the selection ranks tiles of one size (a mean over "
-                                 "`tok` rows, lists of one length); tiles of different thickness are missing from it")
+                raise ValueError(f"sliding_keys={self.sliding_keys!r} on a partial geometry: the selection ranks tiles of one size "
+                                 "(a mean over `tok` rows, lists of one length); tiles of different thickness are missing from it")
             if self.row_map is not None:
-                raise ValueError("sliding_keys='content' under sequence parallelism (a geometry with a row_map): the selection is "
+                raise ValueError(f"sliding_keys={self.sliding_keys!r} under sequence parallelism (a geometry with a row_map): the selection is "
                                  "not wired into the sequence-parallel engine's slot groups and their per-rank geometries")
         self.n_keep = int(self.g * (1 - self.rate)) - 1  # coreset_select.py:54
         # the distinct VIDEO key counts of the sliding expert's key lists, longest first (one where the tile divides)
@@ -279,30 +287,32 @@ class RoutedGeometry:
         return self._sta[t_eff]
 
     def content_buffers(self, t_eff: int, n_slots: int, own: bool = False):
-        """the (kv_rows, sel_tiles, ws) a content-keyed sliding call of `n_slots` head slots selects into
+        """the (kv_rows, sel_tiles, ws) a content- or mass-keyed sliding call of `n_slots` head slots selects into
         (`ops.sta_select_buffers`): allocated once per (text length, slot count) and kept with the other lazily built tables,
         so a call allocates nothing after its first (a captured graph's replay writes the buffers its capture wrote).  Every
         call overwrites them, in stream order.  own=True: buffers of the caller's own -- for a call whose recorded launches a
         backward reads later, after other calls have selected."""
         n_tiles, tok, n_kv = ops.sta_table_sizes(self.latent, self.tile, self.window, t_eff)
+        scores = _SELECT_SCORES[self.sliding_keys]
         if own:
-            return ops.sta_select_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device)
+            return ops.sta_select_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device, scores, MASS_ROWS_PER_TILE)
         key = ("content", t_eff, n_slots)
         if key not in self._sta:
-            self._sta[key] = ops.sta_select_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device)
+            self._sta[key] = ops.sta_select_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device, scores,
+                                                    MASS_ROWS_PER_TILE)
         return self._sta[key]
 
     def prebuild(self, t_eff: int, block_rows: int = 256, content_slots: int = 0) -> None:
         """Build (on the CURRENT stream) every lazily cached device table a routed call with this text length may touch.
         Callers that enqueue routed_attention on several streams call this before they fork: a table built inside one
         stream's call is not ordered against another stream's first use of the cached object.
-        content_slots: under sliding_keys="content", the head slots of the sliding expert's launch (H with device counts, the
+        content_slots: under sliding_keys="content" or "mass", the head slots of the sliding expert's launch (H with device counts, the
         host count otherwise), whose selection buffers are allocated here too."""
         if self.is_partial:
             self.sta_partial_launches(t_eff, block_rows if block_rows in (128, 256) else 256)
             return
         self.sta_tables(t_eff)
-        if self.sliding_keys == "content":
+        if self.sliding_keys in _SELECT_SCORES:
             if content_slots > 0:
                 self.content_buffers(t_eff, content_slots)
             return
@@ -674,8 +684,8 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     another key cut (`fidelity_ref_splits` against the routed call's own) and, under "i8pv", another grouping of rows into
     waves (the int8 query scale is a wave's, over its 32 rows: DESIGN.md 6.8)."""
     hy = model == "hunyuan"
-    if geom.sliding_keys == "content":
-        raise ValueError("sampled_expert_fidelity: " + _NO_SAMPLED_CONTENT)
+    if geom.sliding_keys in _SELECT_SCORES:
+        raise ValueError("sampled_expert_fidelity: " + no_sampled_measurement(geom.sliding_keys))
     if precision is not None:
         if precision not in ("fp8pv", "i8pv"):
             raise ValueError(f"sampled_expert_fidelity: precision={precision!r} (None, 'fp8pv' or 'i8pv')")
@@ -866,8 +876,8 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
     if rows is not None and (rows.numel() if torch.is_tensor(rows) else int(rows)) < 1:
         raise ValueError("route_by_fidelity: rows: at least one sampled row (without one every error reads 0 and every head "
                          "would meet any bound)")
-    if geom.sliding_keys == "content":
-        raise ValueError("route_by_fidelity: " + _NO_SAMPLED_CONTENT)
+    if geom.sliding_keys in _SELECT_SCORES:
+        raise ValueError("route_by_fidelity: " + no_sampled_measurement(geom.sliding_keys))
     from .patch.fidelity import expert_work
     fid = sampled_expert_fidelity(q, k, v, geom, model=model, text_len=text_len, text_valid=text_valid, scale=scale, rows=rows,
                                   seed=seed)
@@ -1080,13 +1090,16 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                           kv_rows_stride_g=stride, q_block_table=table, n_key_lists=n_lists, tag="sliding",
                           flops=nheads(2) * 4.0 * D * q_rows.numel() * n_kv, block_rows=br, **sl)
                      for q_rows, kv_rows, stride, n_kv, table, n_lists in geom.sta_partial_launches(te, br)]
-        elif geom.sliding_keys == "content":
-            # key tiles chosen per head and query tile from this call's 16-bit q, k (ops.sta_select_tiles, two launches on
-            # this stream), then the un-merged form: a tile is a group, a (slot, tile) has its own key list.  A recorded call
+        elif geom.sliding_keys in _SELECT_SCORES:
+            # key tiles chosen per head and query tile from this call's 16-bit q, k (ops.sta_select_tiles: two launches on
+            # this stream by the tile means, three by the sampled attention mass at the call's softmax scale), then the
+            # un-merged form: a tile is a group, a (slot, tile) has its own key list.  A recorded call
             # keeps lists of its own (its backward reads them after later calls have selected into the shared buffers)
             q_rows, _, n_kv = geom.sta_tables(te)
             kv_rows, _, _ = ops.sta_select_tiles(q3, k3, geom.latent, geom.tile, geom.window, te, q_rows,
-                                                 out=geom.content_buffers(te, sl["n_heads"], own=record is not None), **sl)
+                                                 out=geom.content_buffers(te, sl["n_heads"], own=record is not None),
+                                                 scores=_SELECT_SCORES[geom.sliding_keys], scale=scale,
+                                                 rows_per_tile=MASS_ROWS_PER_TILE, **sl)
             calls = [dict(base, out=o_e[2], n_q=S, q_group_len=geom.tok, n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows,
                           kv_rows_stride_g=kv_rows.stride(1), tag="sliding", flops=nheads(2) * 4.0 * D * S * n_kv,
                           block_rows=sliding_block_rows, **sl)]

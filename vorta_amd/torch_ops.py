@@ -15,6 +15,8 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
     vorta::sta_build_tables(like, latent, tile, window, t_eff, row_map) -> (q_rows, kv_rows)
     vorta::sta_select_tiles(q, k, q_rows, kv_rows, sel_tiles, ws, latent, tile, window, t_eff, ...)
                                                       -> ()    mutates kv_rows, sel_tiles, ws   vorta_sta_select_tiles
+    vorta::sta_tile_mass(q, k, q_rows, ws, latent, tile, window, t_eff, scale, rows_per_tile, ...)
+                                                      -> ()    mutates ws         vorta_sta_tile_mass
     vorta::route_scores(scores, tau)                  -> (expert_of_head, head_lists, head_counts)
     vorta::route_fidelity(sq_ref, sq_err, max_rel_error, max_flops_share, work)
                                                       -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
@@ -112,17 +114,37 @@ def _(like, latent, tile, window, t_eff=0, row_map=None):
 def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, q_rows: torch.Tensor, kv_rows: torch.Tensor, sel_tiles: torch.Tensor,
                      ws: torch.Tensor, latent: List[int], tile: List[int], window: List[int], t_eff: int = 0,
                      head_list: Optional[torch.Tensor] = None, n_heads: int = -1, n_heads_dev: Optional[torch.Tensor] = None,
-                     row_map: Optional[torch.Tensor] = None) -> None:
+                     row_map: Optional[torch.Tensor] = None, phases: int = 0, scores: str = "mean", scale: float = 0.0,
+                     rows_per_tile: int = 16) -> None:
     """ops.sta_select_tiles into the caller's tables (`ops.sta_select_buffers`): the key lists `kv_rows` and the chosen tiles
-    `sel_tiles` are written in place, `ws` holds the tile means"""
+    `sel_tiles` are written in place, `ws` holds the tile means (scores="mass": the mass statistic's matrix and pairs)"""
     ops.sta_select_tiles(q, k, latent, tile, window, t_eff, q_rows, head_list=head_list,
                          n_heads=None if n_heads < 0 else n_heads, n_heads_dev=n_heads_dev, row_map=row_map,
-                         out=(kv_rows, sel_tiles, ws))
+                         out=(kv_rows, sel_tiles, ws), phases=phases, scores=scores, scale=None if scale <= 0.0 else scale,
+                         rows_per_tile=rows_per_tile)
 
 
 @sta_select_tiles.register_fake
 def _(q, k, q_rows, kv_rows, sel_tiles, ws, latent, tile, window, t_eff=0, head_list=None, n_heads=-1, n_heads_dev=None,
-      row_map=None) -> None:
+      row_map=None, phases=0, scores="mean", scale=0.0, rows_per_tile=16) -> None:
+    return None
+
+
+@torch.library.custom_op("vorta::sta_tile_mass", mutates_args=("ws",), device_types="cuda")
+def sta_tile_mass(q: torch.Tensor, k: torch.Tensor, q_rows: torch.Tensor, ws: torch.Tensor, latent: List[int], tile: List[int],
+                  window: List[int], t_eff: int = 0, scale: float = 0.0, rows_per_tile: int = 16,
+                  head_list: Optional[torch.Tensor] = None, n_heads: int = -1,
+                  n_heads_dev: Optional[torch.Tensor] = None) -> None:
+    """ops.sta_tile_mass into the caller's `ws` (`ops.sta_select_buffers(scores="mass")`): the score matrix
+    (slots, n_tiles, n_tiles) at its start, for `sta_select_tiles(phases=3)`"""
+    ops.sta_tile_mass(q, k, latent, tile, window, t_eff, q_rows, ws, scale=None if scale <= 0.0 else scale,
+                      rows_per_tile=rows_per_tile, head_list=head_list, n_heads=None if n_heads < 0 else n_heads,
+                      n_heads_dev=n_heads_dev)
+
+
+@sta_tile_mass.register_fake
+def _(q, k, q_rows, ws, latent, tile, window, t_eff=0, scale=0.0, rows_per_tile=16, head_list=None, n_heads=-1,
+      n_heads_dev=None) -> None:
     return None
 
 
