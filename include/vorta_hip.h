@@ -706,6 +706,89 @@ int vorta_sta_tile_mass_args_size(void);
 int64_t vorta_sta_tile_mass_ws_floats(const vorta_sta_mass_args* args);
 
 /*
+ * vorta_sta_select_tiles_share -- the FEWEST key tiles that hold a stated share of the sampled attention mass (a pure addition:
+ * the symbol, vorta_sta_select_tiles_share_args_size() and vorta_sta_select_tiles_share_ws_floats(); no reference counterpart).
+ *
+ * Geometry, q_rows, row_map and head slots as vorta_sta_select_tiles (n_heads / n_heads_dev: the selection reads no tensor, so
+ * it takes no head_list).  Reads the score matrix score[y][i][j] that vorta_sta_tile_mass left at the start of ws -- the
+ * contract of vorta_sta_select_tiles(phases = 3); a row of it sums to rows_per_tile.  For every head slot y and query tile i:
+ *   rank        as vorta_sta_select_tiles: tile i first, then the tiles j != i by descending score, equal scores to the lower j,
+ *               a NaN by its bits
+ *   count       the length of the shortest prefix of that order whose scores, summed in fp32 in rank order, reach
+ *               mass_share * rows_per_tile (one fp32 product); at least 1, at most n_sel (a prefix that never reaches it, or a
+ *               NaN sum: n_sel)
+ * Writes, all caller-owned:
+ *   sel_count[y][i]          the count (dense int32 [n_heads][n_tiles])
+ *   sel_tiles[y][i][n_sel]   the kept tiles in ascending tile index, the entries from `count` on -1
+ *   kv_rows                  layout and alignment rules of vorta_sta_select_tiles, the strides sized for the LONGEST list
+ *                            n_kv = n_sel*tok + t_eff: the kept tiles' rows, then the t_eff text rows; the entries between the
+ *                            list's length and the next multiple of 4 repeat entry 0; nothing is written behind that
+ *   kv_len[y][i]             = count*tok + t_eff (dense int32 [n_heads][n_tiles]): the table of vorta_attn_fwd_varlen with
+ *                            kv_len_stride_h = n_tiles and q_group_len = tok
+ *   order                    optional, int32 [n_heads*n_tiles*blocks_per_group]: the logical workgroups (y*n_tiles + i) *
+ *                            blocks_per_group + b of that launch -- blocks_per_group = ceil(tok / block_rows) -- by tile count,
+ *                            descending, equal counts in index order (a counting sort); a slot at or past *n_heads_dev counts 0,
+ *                            so the table is a permutation whatever the device count holds
+ * Slots at or past *n_heads_dev are not written (order apart).  Two launches on the stream (sta_share.hip), no host read, no
+ * allocation, no atomics: graph-capturable, and the same scores give the same tables bit for bit.
+ * Error codes as vorta_sta_select_tiles; VORTA_EINVAL also for a mass_share outside (0, 1] or NaN, rows_per_tile outside
+ * {8, 16, 32} or above tok, blocks_per_group < 1.
+ */
+typedef struct vorta_sta_share_args {
+  uint32_t struct_size;
+  int32_t n_heads;
+  const int32_t* n_heads_dev;
+  int32_t latent[3], tile[3], window[3];
+  int32_t t_eff;
+  int32_t rows_per_tile;
+  float mass_share;
+  int32_t blocks_per_group;
+  int32_t reserved;
+  const int32_t* row_map; /* text rows only */
+  const int32_t* q_rows;
+  int32_t* sel_count;
+  int32_t* sel_tiles;
+  int32_t* kv_rows;
+  int64_t kv_rows_stride_h, kv_rows_stride_g;
+  int32_t* kv_len;
+  int32_t* order;
+  const float* ws;
+} vorta_sta_share_args;
+
+int vorta_sta_select_tiles_share(const vorta_sta_share_args* args, void* hip_stream);
+int vorta_sta_select_tiles_share_args_size(void);
+int64_t vorta_sta_select_tiles_share_ws_floats(const vorta_sta_share_args* args);
+
+/*
+ * vorta_attn_fwd_varlen -- vorta_attn_fwd for query groups whose key lists have DIFFERENT lengths (a pure addition: the symbol
+ * and vorta_attn_varlen_ext_size(); vorta_attn_args keeps its size and meaning).
+ *
+ * 16 bits (bf16 / fp16), head_dim 128, kv_rows required; query groups by q_group_len or q_block_table, head slots by head_list /
+ * n_heads / n_heads_dev, q_rows, q_valid and the device-resident lengths as vorta_attn_fwd.  args->n_kv is the LONGEST list.
+ *   kv_len[y*kv_len_stride_h + g]  device int32: the key positions group g of slot y attends, clamped into [1, n_kv] by the
+ *                                  kernel.  The group reads kv_rows[y*kv_rows_stride_h + g*kv_rows_stride_g + j] for
+ *                                  j < kv_len and no entry behind that
+ *   order                          optional device int32, one entry per workgroup of the launch (n_heads * query blocks):
+ *                                  physical block b computes logical workgroup order[b] = slot * (query blocks) + query
+ *                                  block.  A permutation (vorta_sta_select_tiles_share writes one, longest key loops first);
+ *                                  an entry outside the grid is clamped into it.  NULL: index order
+ * One launch (attn_fwd_varlen.hip), 256- or 128-row workgroups (block_rows; 0 = the choice of vorta_attn_fwd).
+ * VORTA_EUNSUPPORTED: split keys (n_splits != 1), duplicates (dup_rows), variant 1, a dtype other than bf16 / fp16;
+ * VORTA_EINVAL: no kv_rows, no kv_len, misaligned tables, kv_len_stride_h below the number of groups, and what vorta_attn_fwd
+ * refuses.  vorta_attn_fwd_batch* take no such entry: the launch runs on its own.
+ */
+typedef struct vorta_attn_varlen_ext {
+  uint32_t struct_size;
+  int32_t reserved;
+  const int32_t* kv_len;
+  int64_t kv_len_stride_h;
+  const int32_t* order;
+} vorta_attn_varlen_ext;
+
+int vorta_attn_fwd_varlen(const vorta_attn_args* args, const vorta_attn_varlen_ext* ext, void* hip_stream);
+int vorta_attn_varlen_ext_size(void);
+
+/*
  * vorta_router_route -- vorta/patch/router.py:33-43 (Router.forward) + the top-1 / tau rule of
  * `_get_routed_qkv` (hunyuan.py:620-624, wan.py:396-400), without the host sync of torch.nonzero.
  *

@@ -81,6 +81,20 @@ class StaMassArgs(C.Structure):
     ]
 
 
+class StaShareArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("n_heads", _i32), ("n_heads_dev", _vp),
+        ("latent", _i32 * 3), ("tile", _i32 * 3), ("window", _i32 * 3), ("t_eff", _i32), ("rows_per_tile", _i32),
+        ("mass_share", C.c_float), ("blocks_per_group", _i32), ("reserved", _i32),
+        ("row_map", _vp), ("q_rows", _vp), ("sel_count", _vp), ("sel_tiles", _vp), ("kv_rows", _vp),
+        ("kv_rows_stride_h", _i64), ("kv_rows_stride_g", _i64), ("kv_len", _vp), ("order", _vp), ("ws", _vp),
+    ]
+
+
+class AttnVarlenExt(C.Structure):
+    _fields_ = [("struct_size", _u32), ("reserved", _i32), ("kv_len", _vp), ("kv_len_stride_h", _i64), ("order", _vp)]
+
+
 class RouterArgs(C.Structure):
     _fields_ = [
         ("struct_size", _u32), ("dtype", _i32),
@@ -303,6 +317,11 @@ SYMBOLS = {
     "vorta_sta_tile_mass": (C.c_int, [C.POINTER(StaMassArgs), _vp]),
     "vorta_sta_tile_mass_args_size": (C.c_int, []),
     "vorta_sta_tile_mass_ws_floats": (_i64, [C.POINTER(StaMassArgs)]),
+    "vorta_sta_select_tiles_share": (C.c_int, [C.POINTER(StaShareArgs), _vp]),
+    "vorta_sta_select_tiles_share_args_size": (C.c_int, []),
+    "vorta_sta_select_tiles_share_ws_floats": (_i64, [C.POINTER(StaShareArgs)]),
+    "vorta_attn_fwd_varlen": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnVarlenExt), _vp]),
+    "vorta_attn_varlen_ext_size": (C.c_int, []),
     "vorta_router_route": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
@@ -413,6 +432,12 @@ def lib():
     if h.vorta_sta_tile_mass_args_size() != C.sizeof(StaMassArgs):
         raise VortaHipError(f"struct layout mismatch for StaMassArgs: C {h.vorta_sta_tile_mass_args_size()} "
                             f"vs ctypes {C.sizeof(StaMassArgs)}")
+    if h.vorta_sta_select_tiles_share_args_size() != C.sizeof(StaShareArgs):
+        raise VortaHipError(f"struct layout mismatch for StaShareArgs: C {h.vorta_sta_select_tiles_share_args_size()} "
+                            f"vs ctypes {C.sizeof(StaShareArgs)}")
+    if h.vorta_attn_varlen_ext_size() != C.sizeof(AttnVarlenExt):
+        raise VortaHipError(f"struct layout mismatch for AttnVarlenExt: C {h.vorta_attn_varlen_ext_size()} "
+                            f"vs ctypes {C.sizeof(AttnVarlenExt)}")
     _lib = h
     return h
 

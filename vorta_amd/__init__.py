@@ -22,16 +22,19 @@ def set_attention_backward(name: str) -> None:
     _set(name)
 
 
-def set_sliding_keys(name: str) -> None:
+def set_sliding_keys(name: str, mass_share=None) -> None:
     """Which key tiles the sliding-tile expert attends: "window" (the default: the clamped window of tiles around the query
     tile, the reference's mask), "content" (as many tiles, chosen per head and query tile on the device by the product of
     the tiles' mean q and mean k) or "mass" (as many tiles, chosen by the share of softmax mass that 16
     sampled query rows of the tile put on each key tile, scored on the matrix pipe).  Also:
-    VORTA_SLIDING_KEYS=window|content|mass; read when a geometry is built.
-    "content" and "mass" are refused by name on a partial geometry, under sequence parallelism and in the per-expert sampled measurement
-    (`sampled_expert_fidelity`, `route_by_fidelity`, `measured_routes`)."""
+    VORTA_SLIDING_KEYS=window|content|mass|share; read when a geometry is built.
+    "share" keeps the FEWEST tiles, in the ranking of "mass", that hold the share `mass_share` (in (0, 1]) of the tile's sampled
+    mass, at most the window's count, and runs the sliding expert as a launch whose key lists differ in length.
+    It has no default share: give `mass_share=` here, to the geometry, or VORTA_SLIDING_MASS_SHARE.  Inference only, 16 bits.
+    "content", "mass" and "share" are refused by name on a partial geometry, under sequence parallelism and in the per-expert sampled measurement
+    (`sampled_expert_fidelity`, `route_by_fidelity`, `measured_routes`); "share" also in grad mode."""
     from .routed import set_sliding_keys as _set
-    _set(name)
+    _set(name, mass_share)
 
 
 def set_partial_geometry(on: bool) -> None:

@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libvorta_hip.so")
-SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_bwd_dq.hip", "attn_bwd_dkv.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
-           "sta_tables.hip", "sta_select.hip", "sta_mass.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "expert_fidelity.hip", "sampled_fidelity.hip",
+SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_bwd_dq.hip", "attn_bwd_dkv.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "attn_fwd_varlen.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
+           "sta_tables.hip", "sta_select.hip", "sta_mass.hip", "sta_share.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "expert_fidelity.hip", "sampled_fidelity.hip",
            "sampled_experts.hip", "route_fidelity.hip", "route_fidelity_tiers.hip", "route_budget_tiers.hip", "route_repair.hip", "permute.hip"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent fp32 adds of the softmax row sum into v_pk_add_f32 plus the
 # v_mov pairs to feed them -- more instructions on the VALU issue port that bounds the attention loop (+2 % without)

@@ -113,8 +113,11 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
                variant: int = 0, tag: str = "", flops: float = 0.0,
                v_descale: Optional[torch.Tensor] = None, fp8_opts: Optional[dict] = None,
                q_block_table: Optional[torch.Tensor] = None, n_key_lists: int = 0,
-               i8: Optional["I8Operands"] = None):
+               i8: Optional["I8Operands"] = None,
+               kv_len: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
     """Fill a vorta_attn_args; returns (args, workspace tensors to keep alive until the launch is enqueued).
+    kv_len (slots, groups) int32 = key lists of different lengths (`attn_fwd_varlen`): the args carry the vorta_attn_varlen_ext
+    of vorta_attn_fwd_varlen as `_ext`, `n_kv` is the longest list and `order` the optional workgroup order.
     q,k,v of dtype uint8 = e4m3 operands from `fp8_quantize_qkv` (then `v_descale` is required and `out` is 16-bit):
     the args carry `_ext`, the vorta_attn_fp8_ext of the fp8 entry points.
     k of dtype int8 = the rows of `i8_quantize_k` (then `i8` = its I8Operands, or views of them with k's geometry, is
@@ -253,6 +256,23 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     a.reserved = NO_XCD_REMAP
     if q_block_table is not None:
         a.q_block_table, a.n_q_blocks = _ptr(q_block_table), q_block_table.shape[0]
+    if kv_len is not None or order is not None:
+        if fp8 or mixed or i8:
+            raise ValueError("key lists of different lengths (kv_len=) run in 16 bits only: there is no 8-bit variable-length body")
+        if kv_len is None or kv_rows is None or kv_len.dtype != torch.int32 or kv_len.dim() != 2 or kv_len.stride(1) != 1 \
+                or kv_len.shape[0] < n_heads or kv_len.shape[1] < n_groups:
+            raise ValueError(f"kv_len must be int32 (slots, groups) covering {n_heads} head slots x {n_groups} key lists of kv_rows")
+        ext = _C.AttnVarlenExt()
+        ext.struct_size = C.sizeof(_C.AttnVarlenExt)
+        ext.kv_len, ext.kv_len_stride_h = kv_len.data_ptr(), kv_len.stride(0)
+        if order is not None:
+            n_blocks = q_block_table.shape[0] if q_block_table is not None else n_groups * -(-(q_group_len or n_q) // max(block_rows, 1))
+            if block_rows not in (128, 256) or order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous() \
+                    or order.numel() != n_heads * n_blocks:
+                raise ValueError(f"order must be int32 ({n_heads} head slots x {n_blocks} query blocks,) with an explicit block_rows "
+                                 "(128 / 256): one logical workgroup per physical block")
+            ext.order = order.data_ptr()
+        a._ext, a._family = ext, _FAMILIES["varlen"]
     ws = None
     if n_splits > 1:
         so, sm = C.c_uint64(), C.c_uint64()
@@ -277,6 +297,8 @@ _FAMILIES = {
     "fp8": _Family("vorta_attn_fwd_fp8", "vorta_attn_fwd_batch_fp8", "attn8_kernel<{t},{nw},{tab},{lmfma}>", "attn8_multi_kernel<{t}>"),
     "mx": _Family("vorta_attn_fwd_fp8", "vorta_attn_fwd_batch_fp8", "attn_mx_kernel<{t},{nw},{tab}>", "attn_mx_multi_kernel<{t}>"),
     "i8": _Family("vorta_attn_fwd_i8", "vorta_attn_fwd_batch_i8", "attn_i8_kernel<{t},{nw},{tab}>", "attn_i8_multi_kernel<{t}>"),
+    # key lists of different lengths (csrc/attn_fwd_varlen.hip): a launch of its own, no fused grid takes it
+    "varlen": _Family("vorta_attn_fwd_varlen", None, "attn_varlen_kernel<{t},{nw}>", None),
 }
 
 
@@ -294,7 +316,7 @@ def _plan(a) -> Tuple[int, int, str]:
     _C.check(_C.lib().vorta_attn_plan(C.byref(a), C.byref(br), C.byref(nwg), C.byref(kid)), "vorta_attn_plan")
     nw, kk = kid.value // 16, kid.value % 16
     fmt = a._family.kernel if kk & 1 else "attn_fwd_kernel<{t},{nw}>"  # (not pipelined: the 16-bit variant 1)
-    lmfma = "false" if a._ext is not None and a._ext.flags & 1 else "true"
+    lmfma = "false" if getattr(a._ext, "flags", 0) & 1 else "true"
     return br.value, nwg.value, fmt.format(t=a._out_type, nw=nw, tab="true" if kk & 2 else "false", lmfma=lmfma)
 
 
@@ -319,6 +341,16 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tenso
     a, ws = _attn_args(q, k, v, out, **kw)
     _timed(lambda: _launch_one(a), tag, flops, [a])
     # `ws` may be released now: the caching allocator is stream ordered and the launch is on this stream
+
+
+def attn_fwd_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, kv_len: torch.Tensor,
+                    order: Optional[torch.Tensor] = None, tag: str = "", flops: float = 0.0, **kw) -> None:
+    """vorta_attn_fwd_varlen: `attn_fwd` for query groups whose key lists have different lengths.  16-bit q, k, v, out, D = 128,
+    `kv_rows` required; `n_kv` is the longest list.  kv_len: int32 (slots, groups), the key positions group g of slot y attends
+    (the kernel clamps it into [1, n_kv] and reads no list entry behind it).  order: optional int32 (slots * query blocks,), the
+    logical workgroup (slot * query blocks + query block) physical block b computes -- a permutation, `sta_select_tiles_share`
+    writes one with the longest key loops first; needs an explicit `block_rows`.  No split keys, no duplicate rows."""
+    attn_fwd(q, k, v, out, tag=tag, flops=flops, kv_len=kv_len, order=order, **kw)
 
 
 MAX_FUSED = 6  # include/vorta_hip.h VORTA_MAX_FUSED_LAUNCHES (the library refuses more with VORTA_EINVAL)
@@ -354,7 +386,8 @@ def attn_fwd_batch(calls) -> None:
         return
 
     def fusable_one(a):
-        return _plan(a)[0] == 256 and a.variant != 1 and not (isinstance(a._ext, _C.AttnFp8Ext) and a._ext.flags & 1)
+        return _plan(a)[0] == 256 and a.variant != 1 and a._family.batch is not None \
+            and not (isinstance(a._ext, _C.AttnFp8Ext) and a._ext.flags & 1)
 
     ok = [fusable_one(a) for a, _, _, _ in built]
     fuse_all = 1 < len(built) <= MAX_FUSED and all(ok)
@@ -858,6 +891,68 @@ def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_e
     a.ws = ws.data_ptr()
     _C.check(_C.lib().vorta_sta_select_tiles(C.byref(a), _stream()), "vorta_sta_select_tiles")
     return kv, sel, n_kv
+
+
+class ShareTiles(NamedTuple):
+    """the tables of `sta_select_tiles_share`, all int32 on the device"""
+    kv_rows: torch.Tensor    # (slots, n_tiles, n_kv): the key lists, n_kv the longest; entries behind a list's length are not written
+    sel_tiles: torch.Tensor  # (slots, n_tiles, n_sel): the kept tiles ascending, then -1
+    sel_count: torch.Tensor  # (slots, n_tiles): kept tiles
+    kv_len: torch.Tensor     # (slots, n_tiles): sel_count * tok + t_eff
+    order: torch.Tensor      # (slots * n_tiles * blocks_per_group,): the launch's workgroups, longest key loops first
+    ws: torch.Tensor         # float32: the mass statistic's score matrix and pairs (`sta_select_buffers(scores="mass")`)
+
+
+def sta_share_buffers(n_slots: int, n_tiles: int, n_sel: int, n_kv: int, device, rows_per_tile: int = 16,
+                      blocks_per_group: int = 1) -> ShareTiles:
+    """the caller-owned tables of `sta_select_tiles_share` for `n_slots` head slots (`sta_select_buffers(scores="mass")` and the
+    three tables of the variable-length launch)"""
+    kv, sel, ws = sta_select_buffers(n_slots, n_tiles, n_sel, n_kv, device, "mass", rows_per_tile)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)  # noqa: E731
+    return ShareTiles(kv, sel, i32(n_slots, n_tiles), i32(n_slots, n_tiles), i32(n_slots * n_tiles * blocks_per_group), ws)
+
+
+def sta_select_tiles_share(latent, tile, window, t_eff: int, q_rows: torch.Tensor, out: ShareTiles, *, mass_share: float,
+                           n_heads: int, rows_per_tile: int = 16, block_rows: int = 256,
+                           n_heads_dev: Optional[torch.Tensor] = None, row_map: Optional[torch.Tensor] = None) -> ShareTiles:
+    """vorta_sta_select_tiles_share: per head slot and query tile, the FEWEST key tiles -- in the rank order of
+    `sta_select_tiles` -- whose scores reach `mass_share` of the sampled mass, at least 1 and at most the window's count.  Reads
+    the score matrix `sta_tile_mass` left at the start of `out.ws` (at `rows_per_tile`) and writes the other tables of `out`
+    (`sta_share_buffers`): the key lists, their lengths `kv_len` and the workgroup `order` of `attn_fwd_varlen` with
+    q_group_len = tok and `block_rows` (128 / 256) rows per workgroup.  Two launches, no host read, no allocation."""
+    _require_gpu(q_rows, *out)
+    n_tiles, tok, n_kv = sta_table_sizes(latent, tile, window, t_eff)
+    n_sel = (n_kv - t_eff) // tok
+    if block_rows not in (128, 256):
+        raise ValueError("sta_select_tiles_share: block_rows is the variable-length launch's, 128 or 256")
+    bpg = -(-tok // block_rows)
+    kv, sel, cnt, kv_len, order, ws = out
+    if any(t.dtype != torch.int32 for t in (kv, sel, cnt, kv_len, order)) or tuple(kv.shape) != (kv.shape[0], n_tiles, n_kv) \
+            or kv.shape[0] < n_heads or kv.stride(2) != 1 or tuple(sel.shape) != (kv.shape[0], n_tiles, n_sel) \
+            or not (sel.is_contiguous() and cnt.is_contiguous() and kv_len.is_contiguous() and order.is_contiguous()) \
+            or tuple(cnt.shape) != (n_heads, n_tiles) or tuple(kv_len.shape) != (n_heads, n_tiles) \
+            or order.numel() != n_heads * n_tiles * bpg or ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("sta_select_tiles_share: out= the tables of sta_share_buffers for exactly n_heads slots of this geometry "
+                         "and ceil(tok / block_rows) blocks a tile")
+    if q_rows.numel() < n_tiles * tok:
+        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
+    if row_map is not None and row_map.numel() < n_tiles * tok + t_eff:
+        raise ValueError(f"row_map holds {row_map.numel()} rows, video and text {n_tiles * tok + t_eff}")
+    a = _C.StaShareArgs()
+    a.struct_size = C.sizeof(_C.StaShareArgs)
+    a.n_heads, a.n_heads_dev = n_heads, _ptr(n_heads_dev)
+    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
+    a.t_eff, a.rows_per_tile, a.mass_share, a.blocks_per_group = t_eff, rows_per_tile, float(mass_share), bpg
+    a.row_map, a.q_rows = _ptr(row_map), _ptr(q_rows)
+    a.sel_count, a.sel_tiles, a.kv_rows = cnt.data_ptr(), sel.data_ptr(), kv.data_ptr()
+    a.kv_rows_stride_h, a.kv_rows_stride_g = kv.stride(0), kv.stride(1)
+    a.kv_len, a.order, a.ws = kv_len.data_ptr(), order.data_ptr(), ws.data_ptr()
+    need = _C.lib().vorta_sta_select_tiles_share_ws_floats(C.byref(a))
+    _C.check(min(need, 0), "vorta_sta_select_tiles_share_ws_floats")
+    if ws.numel() < need:
+        raise ValueError(f"sta_select_tiles_share: ws holds {ws.numel()} float32, the score matrices {need}")
+    _C.check(_C.lib().vorta_sta_select_tiles_share(C.byref(a), _stream()), "vorta_sta_select_tiles_share")
+    return out
 
 
 def _sta_args(latent, tile, window, t_eff: int):

@@ -21,10 +21,12 @@ from ._partial import partial_geometry, set_partial_geometry  # noqa: F401  (the
 Triple = Tuple[int, int, int]
 
 
-SLIDING_KEYS = ("window", "content", "mass")
-_SELECT_SCORES = {"content": "mean", "mass": "mass"}  # the statistic ops.sta_select_tiles ranks by, per selecting choice
+SLIDING_KEYS = ("window", "content", "mass", "share")
+# the statistic the tiles are ranked by, per selecting choice ("share": the mass statistic, ranked by ops.sta_select_tiles_share)
+_SELECT_SCORES = {"content": "mean", "mass": "mass", "share": "mass"}
 MASS_ROWS_PER_TILE = 16  # sampled query rows that stand for a query tile under "mass" 
 _sliding_keys: Optional[str] = None  # the process-wide default; None = not set: VORTA_SLIDING_KEYS, else "window"
+_mass_share: Optional[float] = None  # the process-wide share of "share"; None = not set: VORTA_SLIDING_MASS_SHARE, else an error
 _NO_SAMPLED_CONTENT = ("sliding_keys='content': the sampled sliding candidate is built from the key lists every head of a "
                        "length class shares (RoutedGeometry.sample_tables); the per-head sampled form of content-chosen "
                        "lists is missing -- measure under 'window', or verify what was launched (fidelity=, repair_above=)")
@@ -41,13 +43,47 @@ def _check_sliding_keys(name, where: str) -> str:
     return name
 
 
-def set_sliding_keys(name: str) -> None:
+def _check_mass_share(p, where: str) -> float:
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: mass_share {p!r} is not a number") from None
+    if not 0.0 < p <= 1.0:  # (a NaN fails both)
+        raise ValueError(f"{where}: mass_share {p!r} outside (0, 1]: the share of a query tile's sampled attention mass its kept "
+                         "key tiles must hold")
+    return p
+
+
+def mass_share_of(p: Optional[float] = None) -> float:
+    """the share a geometry built with sliding_keys="share" and `mass_share=p` keeps: its own, else set_sliding_keys', else the
+    environment's VORTA_SLIDING_MASS_SHARE.  There is no default: the share is the user's bound on the mass a head may lose."""
+    if p is not None:
+        return _check_mass_share(p, "mass_share")
+    if _mass_share is not None:
+        return _mass_share
+    import os
+    env = os.environ.get("VORTA_SLIDING_MASS_SHARE")
+    if not env:
+        raise ValueError("sliding_keys='share' has no default share: give mass_share=p, p in (0, 1] (RoutedGeometry(..., "
+                         "mass_share=p), set_sliding_keys('share', mass_share=p) or VORTA_SLIDING_MASS_SHARE=p)")
+    return _check_mass_share(env, "VORTA_SLIDING_MASS_SHARE")
+
+
+def set_sliding_keys(name: str, mass_share: Optional[float] = None) -> None:
     """the process-wide choice of the sliding-tile expert's key tiles: "window" (the clamped window of tiles around the query
     tile: the reference's mask), "content" (as many tiles, chosen per head and query tile by <mean q, mean k>:
     ops.sta_select_tiles) or "mass" (as many tiles, chosen by the attention mass that sampled query rows of the
-    tile put on every key tile: ops.sta_tile_mass).  Overrides the environment switch VORTA_SLIDING_KEYS; read when a geometry is built."""
-    global _sliding_keys
-    _sliding_keys = _check_sliding_keys(name, "set_sliding_keys")
+    tile put on every key tile: ops.sta_tile_mass).  Overrides the environment switch VORTA_SLIDING_KEYS; read when a geometry is built.
+    "share" (the FEWEST tiles, in that mass ranking, that hold `mass_share` of the tile's sampled mass, at most the window's
+    count: ops.sta_select_tiles_share and the variable-length launch ops.attn_fwd_varlen) takes its share here,
+    from a geometry's own `mass_share=` or from VORTA_SLIDING_MASS_SHARE; there is no default share."""
+    global _sliding_keys, _mass_share
+    name = _check_sliding_keys(name, "set_sliding_keys")
+    if mass_share is not None:
+        if name != "share":
+            raise ValueError(f"set_sliding_keys: mass_share= goes with 'share', not with {name!r}")
+        _mass_share = _check_mass_share(mass_share, "set_sliding_keys")
+    _sliding_keys = name
 
 
 def sliding_keys_of(name: Optional[str] = None) -> str:
@@ -196,6 +232,9 @@ class RoutedGeometry:
     # which key tiles the sliding-tile expert attends: "window" (by position), "content" or "mass" (ops.sta_select_tiles, per
     # call and head, ranked by tile means or by sampled attention mass); None = the process-wide switch (set_sliding_keys / VORTA_SLIDING_KEYS).  "window" builds and launches what it always did
     sliding_keys: Optional[str] = None
+    # under sliding_keys="share": the share of a query tile's sampled attention mass its kept key tiles hold, in (0, 1]; None =
+    # set_sliding_keys' / VORTA_SLIDING_MASS_SHARE (no default: an error without one).  Not read under the other choices
+    mass_share: Optional[float] = None
 
     def __post_init__(self):
         self.latent, self.tile, self.window, self.group = (tuple(int(v) for v in x) for x in
@@ -206,6 +245,7 @@ class RoutedGeometry:
         # is_partial: the tables, launches and lists below differ from the dividing ones only then
         self.is_partial = self.partial and not _partial.divides(self.latent, self.tile, self.group)
         self.sliding_keys = sliding_keys_of(self.sliding_keys)
+        self.mass_share = mass_share_of(self.mass_share) if self.sliding_keys == "share" else None
         if self.sliding_keys in _SELECT_SCORES:
             if self.is_partial:
                 raise ValueError(f"sliding_keys={self.sliding_keys!r} on a partial geometry: the selection ranks tiles of one size "
@@ -302,6 +342,16 @@ class RoutedGeometry:
                                                     MASS_ROWS_PER_TILE)
         return self._sta[key]
 
+    def share_buffers(self, t_eff: int, n_slots: int, block_rows: int) -> "ops.ShareTiles":
+        """the tables a share-keyed sliding call of `n_slots` head slots and `block_rows` rows a workgroup selects into
+        (`ops.sta_share_buffers`), allocated once and kept as `content_buffers` keeps its own"""
+        key = ("share", t_eff, n_slots, block_rows)
+        if key not in self._sta:
+            n_tiles, tok, n_kv = ops.sta_table_sizes(self.latent, self.tile, self.window, t_eff)
+            self._sta[key] = ops.sta_share_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device, MASS_ROWS_PER_TILE,
+                                                   -(-tok // block_rows))
+        return self._sta[key]
+
     def prebuild(self, t_eff: int, block_rows: int = 256, content_slots: int = 0) -> None:
         """Build (on the CURRENT stream) every lazily cached device table a routed call with this text length may touch.
         Callers that enqueue routed_attention on several streams call this before they fork: a table built inside one
@@ -313,7 +363,9 @@ class RoutedGeometry:
             return
         self.sta_tables(t_eff)
         if self.sliding_keys in _SELECT_SCORES:
-            if content_slots > 0:
+            if content_slots > 0 and self.sliding_keys == "share":
+                self.share_buffers(t_eff, content_slots, block_rows if block_rows in (128, 256) else 256)
+            elif content_slots > 0:
                 self.content_buffers(t_eff, content_slots)
             return
         if STA_MERGE and block_rows in (128, 256):
@@ -1041,6 +1093,13 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     def nheads(e):  # for the algorithmic-work tags only
         return routing.counts_host[e] if routing.counts_host is not None else 0
 
+    if geom.sliding_keys == "share" and live(2):
+        if record is not None or (torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v))):
+            raise ValueError("sliding_keys='share' in grad mode: the backward replays key lists of one length per launch; a "
+                             "variable-length backward is missing -- train under 'window', 'content' or 'mass'")
+        if (operands.precision if operands is not None else precision_of(fp8)) != "native":
+            raise ValueError("sliding_keys='share' under an 8-bit precision: the variable-length launch (ops.attn_fwd_varlen) has a "
+                             "16-bit body only -- run it with fp8=False")
     if operands is None:
         # (video_tokens: the sample is summed in eighths of the video tokens + the text, as the sequence-parallel send side sums it)
         operands = prepare_operands(precision_of(fp8), q3, k3, v3, scale, fp8_operands,
@@ -1090,6 +1149,22 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                           kv_rows_stride_g=stride, q_block_table=table, n_key_lists=n_lists, tag="sliding",
                           flops=nheads(2) * 4.0 * D * q_rows.numel() * n_kv, block_rows=br, **sl)
                      for q_rows, kv_rows, stride, n_kv, table, n_lists in geom.sta_partial_launches(te, br)]
+        elif geom.sliding_keys == "share":
+            # the fewest key tiles that hold geom.mass_share of the sampled mass: the tile-mass launches at the call's softmax
+            # scale, the share selection, then ONE launch whose groups (a tile each) walk key lists of their own lengths, its
+            # workgroups ordered longest first.  No fused grid takes it: ops.attn_fwd_batch runs it behind the other experts'
+            br = sliding_block_rows if sliding_block_rows in (128, 256) else 256
+            q_rows, _, n_kv = geom.sta_tables(te)
+            tabs = geom.share_buffers(te, sl["n_heads"], br)
+            ops.sta_tile_mass(q3, k3, geom.latent, geom.tile, geom.window, te, q_rows, tabs.ws, scale=scale,
+                              rows_per_tile=MASS_ROWS_PER_TILE, **sl)
+            ops.sta_select_tiles_share(geom.latent, geom.tile, geom.window, te, q_rows, tabs, mass_share=geom.mass_share,
+                                       n_heads=sl["n_heads"], rows_per_tile=MASS_ROWS_PER_TILE, block_rows=br,
+                                       n_heads_dev=sl.get("n_heads_dev"))
+            # (flops: the window's count, an upper bound -- the kept counts live on the device)
+            calls = [dict(base, out=o_e[2], n_q=S, q_group_len=geom.tok, n_kv=n_kv, q_rows=q_rows, kv_rows=tabs.kv_rows,
+                          kv_rows_stride_g=tabs.kv_rows.stride(1), kv_len=tabs.kv_len, order=tabs.order, tag="sliding",
+                          flops=nheads(2) * 4.0 * D * S * n_kv, block_rows=br, **sl)]
         elif geom.sliding_keys in _SELECT_SCORES:
             # key tiles chosen per head and query tile from this call's 16-bit q, k (ops.sta_select_tiles: two launches on
             # this stream by the tile means, three by the sampled attention mass at the call's softmax scale), then the
@@ -1587,17 +1662,19 @@ _GEOMETRY_CACHE_MAX = 48
 
 
 def geometry_for(latent, tile, window, group, rate, device, row_map: Optional[torch.Tensor] = None,
-                 partial: Optional[bool] = None, sliding_keys: Optional[str] = None) -> RoutedGeometry:
+                 partial: Optional[bool] = None, sliding_keys: Optional[str] = None,
+                 mass_share: Optional[float] = None) -> RoutedGeometry:
     """Process-wide cache: the tables are built once per geometry, not once per layer call.
-    `partial`, `sliding_keys`: as RoutedGeometry's (None = the process-wide switch, read here)."""
+    `partial`, `sliding_keys`, `mass_share`: as RoutedGeometry's (None = the process-wide switch, read here)."""
     partial = partial_geometry() if partial is None else bool(partial)
     keys = sliding_keys_of(sliding_keys)
+    share = mass_share_of(mass_share) if keys == "share" else None
     key = (tuple(latent), tuple(tile), tuple(window), tuple(group), float(rate), str(device),
-           None if row_map is None else (row_map.data_ptr(), row_map.numel()), partial, keys)
+           None if row_map is None else (row_map.data_ptr(), row_map.numel()), partial, keys, share)
     g = _GEOMETRY_CACHE.pop(key, None)
     if g is None:
         g = RoutedGeometry(latent, tile, window, group, rate, torch.device(device), row_map=row_map, partial=partial,
-                           sliding_keys=keys)
+                           sliding_keys=keys, mass_share=share)
         # bounded: a geometry holds its sliding-tile tables (13 MB at Hunyuan-129f) and, under sequence parallelism, there is one
         # per distinct slot count of a rank (slot groups and uneven placements: up to ~2 H / P of them per resolution); the least
         # recently used one goes when a process has seen more than this many (the row maps they are keyed on are never freed)

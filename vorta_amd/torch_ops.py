@@ -17,6 +17,9 @@ Registered (tensors are (H,S,D) views as in ops.py; optional tensors may be None
                                                       -> ()    mutates kv_rows, sel_tiles, ws   vorta_sta_select_tiles
     vorta::sta_tile_mass(q, k, q_rows, ws, latent, tile, window, t_eff, scale, rows_per_tile, ...)
                                                       -> ()    mutates ws         vorta_sta_tile_mass
+    vorta::sta_select_tiles_share(q_rows, kv_rows, sel_tiles, sel_count, kv_len, order, ws, latent, tile, window, t_eff,
+                                  mass_share, n_heads, ...) -> ()    mutates the five tables   vorta_sta_select_tiles_share
+    vorta::attn_fwd_varlen(q,k,v,out, kv_rows, kv_len, n_q, n_kv, ...) -> ()    mutates out   vorta_attn_fwd_varlen
     vorta::route_scores(scores, tau)                  -> (expert_of_head, head_lists, head_counts)
     vorta::route_fidelity(sq_ref, sq_err, max_rel_error, max_flops_share, work)
                                                       -> (expert_of_head, head_lists, head_counts, flops_share)   vorta_route_fidelity
@@ -145,6 +148,45 @@ def sta_tile_mass(q: torch.Tensor, k: torch.Tensor, q_rows: torch.Tensor, ws: to
 @sta_tile_mass.register_fake
 def _(q, k, q_rows, ws, latent, tile, window, t_eff=0, scale=0.0, rows_per_tile=16, head_list=None, n_heads=-1,
       n_heads_dev=None) -> None:
+    return None
+
+
+@torch.library.custom_op("vorta::sta_select_tiles_share", mutates_args=("kv_rows", "sel_tiles", "sel_count", "kv_len", "order"),
+                         device_types="cuda")
+def sta_select_tiles_share(q_rows: torch.Tensor, kv_rows: torch.Tensor, sel_tiles: torch.Tensor, sel_count: torch.Tensor,
+                           kv_len: torch.Tensor, order: torch.Tensor, ws: torch.Tensor, latent: List[int], tile: List[int],
+                           window: List[int], t_eff: int, mass_share: float, n_heads: int, rows_per_tile: int = 16,
+                           block_rows: int = 256, n_heads_dev: Optional[torch.Tensor] = None,
+                           row_map: Optional[torch.Tensor] = None) -> None:
+    """ops.sta_select_tiles_share into the caller's tables (`ops.sta_share_buffers`), from the score matrix `sta_tile_mass` left
+    in `ws`"""
+    ops.sta_select_tiles_share(latent, tile, window, t_eff, q_rows, ops.ShareTiles(kv_rows, sel_tiles, sel_count, kv_len, order, ws),
+                               mass_share=mass_share, n_heads=n_heads, rows_per_tile=rows_per_tile, block_rows=block_rows,
+                               n_heads_dev=n_heads_dev, row_map=row_map)
+
+
+@sta_select_tiles_share.register_fake
+def _(q_rows, kv_rows, sel_tiles, sel_count, kv_len, order, ws, latent, tile, window, t_eff, mass_share, n_heads,
+      rows_per_tile=16, block_rows=256, n_heads_dev=None, row_map=None) -> None:
+    return None
+
+
+@torch.library.custom_op("vorta::attn_fwd_varlen", mutates_args=("out",), device_types="cuda")
+def attn_fwd_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, kv_rows: torch.Tensor,
+                    kv_len: torch.Tensor, n_q: int, n_kv: int, order: Optional[torch.Tensor] = None,
+                    head_list: Optional[torch.Tensor] = None, n_heads: int = -1, n_heads_dev: Optional[torch.Tensor] = None,
+                    q_group_len: int = 0, q_valid: int = -1, q_rows: Optional[torch.Tensor] = None, kv_rows_stride_g: int = 0,
+                    scale: float = 0.0, block_rows: int = 0) -> None:
+    """ops.attn_fwd_varlen: group g of slot y attends the first kv_len[y][g] entries of its key list"""
+    ops.attn_fwd_varlen(q, k, v, out, kv_len=kv_len, order=order, n_q=n_q, n_kv=n_kv, head_list=head_list,
+                        n_heads=None if n_heads < 0 else n_heads, n_heads_dev=n_heads_dev, q_group_len=q_group_len,
+                        q_valid=None if q_valid < 0 else q_valid, q_rows=q_rows, kv_rows=kv_rows,
+                        kv_rows_stride_g=kv_rows_stride_g, scale=None if scale <= 0.0 else scale, block_rows=block_rows)
+
+
+@attn_fwd_varlen.register_fake
+def _(q, k, v, out, kv_rows, kv_len, n_q, n_kv, order=None, head_list=None, n_heads=-1, n_heads_dev=None, q_group_len=0,
+      q_valid=-1, q_rows=None, kv_rows_stride_g=0, scale=0.0, block_rows=0) -> None:
     return None
 
 
