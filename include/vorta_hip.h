@@ -789,6 +789,20 @@ int vorta_attn_fwd_varlen(const vorta_attn_args* args, const vorta_attn_varlen_e
 int vorta_attn_varlen_ext_size(void);
 
 /*
+ * vorta_attn_fwd_varlen_i8 -- vorta_attn_fwd_varlen with INT8 SCORES and e4m3 P V (a pure addition: the symbol; no struct
+ * changes size or meaning).  Operands and `i8` as vorta_attn_fwd_i8 (16-bit q and out, int8 k, e4m3 v, k_bias, q_prep,
+ * k_head_scale, v_descale, p_bias, defer), tables and `ext` as vorta_attn_fwd_varlen (kv_rows required, kv_len clamped into
+ * [1, n_kv], optional order clamped into the grid).  head_dim 128, 256- or 128-row workgroups, bf16 / fp16 outputs.
+ * The body is the int8-score kernel's (attn_i8_body.h), block after block: group g of slot y gets the bits vorta_attn_fwd_i8
+ * writes for its rows over kv_rows[..][0 .. kv_len) with n_kv = kv_len.  Tiles behind a list's last block are not requested;
+ * no list entry behind kv_len is read (attn_fwd_i8_varlen.hip).
+ * VORTA_EUNSUPPORTED: split keys, dup_rows, variant 1, and what vorta_attn_fwd_i8 does not support; VORTA_EINVAL: a bad `i8`
+ * as vorta_attn_fwd_i8 decides it, a bad `ext` or table as vorta_attn_fwd_varlen decides it.  No fused grid takes it.
+ */
+int vorta_attn_fwd_varlen_i8(const vorta_attn_args* args, const vorta_attn_i8_ext* i8, const vorta_attn_varlen_ext* ext,
+                             void* hip_stream);
+
+/*
  * vorta_router_route -- vorta/patch/router.py:33-43 (Router.forward) + the top-1 / tau rule of
  * `_get_routed_qkv` (hunyuan.py:620-624, wan.py:396-400), without the host sync of torch.nonzero.
  *

@@ -13,11 +13,14 @@
 #                          over the SAME mass-chosen lists, every length n_kv (no order table); the margin is the run's own
 #                          min-max spread
 # with the mean and largest kept tile count per p, and the ratios to window_merged.
+# --precision i8pv: every arm under the int8-score precision (the selection arms are unchanged code: they read the 16-bit q, k);
+# table_full / varlen_full are then vorta_attn_fwd_i8 and vorta_attn_fwd_varlen_i8 over the operands of prepare_operands.
 # accuracy: the structured families (local, redundant, white), every head on the sliding expert: per head rel_error =
 # |out - dense| / |dense| over the video rows, for the window and for share at every p, with the mean kept tile count.
 #
 # usage: python tools/bench_sliding_share.py timing --config hunyuan-129f --config wan14b-81f --out profiles/share_tiles_timing.json
 #        python tools/bench_sliding_share.py accuracy --config hunyuan-129f --config wan14b-81f --out profiles/share_tiles_accuracy.txt
+#        ... --precision i8pv --out profiles/share_tiles_i8_timing.json / profiles/share_tiles_i8_accuracy.txt
 import argparse
 import json
 import os
@@ -45,8 +48,9 @@ def _geom(cfg, dev, **kw):
 def timing_of(a, config, inputs):
     import _structured_inputs as SI
     from vorta_amd import ops
-    from vorta_amd.routed import MASS_ROWS_PER_TILE, HeadRouting, routed_attention
+    from vorta_amd.routed import MASS_ROWS_PER_TILE, HeadRouting, prepare_operands, routed_attention
     cfg, dev, dt, S, H, q, k, v, window, kw = _layer(config)
+    fp8 = False if a.precision == "native" else a.precision
     n = SLIDING_HEADS.get(config, max(1, H // 3))
     te = kw["text_valid"]
     if inputs == "local":  # the video rows of the sliding heads become local heads; the text rows stay white
@@ -60,7 +64,7 @@ def timing_of(a, config, inputs):
     geoms = {p: _geom(cfg, dev, sliding_keys="share", mass_share=p) for p in SHARES}
     q_rows, _, n_kv = geoms[SHARES[0]].sta_tables(te)
     n_tiles, tok, _ = ops.sta_table_sizes(cfg["latent"], cfg["tile"], cfg["window"], te)
-    arms = {"window_merged": lambda: routed_attention(q, k, v, routing, window, out=out, fp8=False, **kw)}
+    arms = {"window_merged": lambda: routed_attention(q, k, v, routing, window, out=out, fp8=fp8, **kw)}
     tabs = {}
     for p, g in geoms.items():
         g.prebuild(te, content_slots=n)
@@ -72,21 +76,22 @@ def timing_of(a, config, inputs):
             ops.sta_select_tiles_share(g.latent, g.tile, g.window, te, q_rows, tabs[p], mass_share=p, n_heads=slots["n_heads"],
                                        rows_per_tile=MASS_ROWS_PER_TILE, n_heads_dev=slots.get("n_heads_dev"))
         arms[f"share_select_{p}"] = select
-        arms[f"share_{p}"] = lambda g=g: routed_attention(q, k, v, routing, g, out=out, fp8=False, **kw)
+        arms[f"share_{p}"] = lambda g=g: routed_attention(q, k, v, routing, g, out=out, fp8=fp8, **kw)
     # the body alone: the same full-length lists through the existing table launch and through the variable-length one
     mass = _geom(cfg, dev, sliding_keys="mass")
     kv_rows, _, _ = ops.sta_select_tiles(q[0], k[0], mass.latent, mass.tile, mass.window, te, q_rows, scores="mass",
                                          scale=kw.get("scale"), rows_per_tile=MASS_ROWS_PER_TILE, **slots)
     full = torch.full((n, n_tiles), n_kv, dtype=torch.int32, device=dev)
     launch = dict(n_q=S, q_group_len=tok, n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=kv_rows.stride(1),
-                  block_rows=256, scale=kw.get("scale"), **slots)
-    arms["table_full"] = lambda: ops.attn_fwd(q[0], k[0], v[0], out[0], **launch)
-    arms["varlen_full"] = lambda: ops.attn_fwd_varlen(q[0], k[0], v[0], out[0], kv_len=full, **launch)
+                  block_rows=256, **slots)
+    operands = prepare_operands(a.precision, q[0], k[0], v[0], kw.get("scale")).kwargs(kw.get("scale"))
+    arms["table_full"] = lambda: ops.attn_fwd(out=out[0], **operands, **launch)
+    arms["varlen_full"] = lambda: ops.attn_fwd_varlen(out=out[0], kv_len=full, **operands, **launch)
     res = _alternate(arms, a.rounds)
     torch.cuda.synchronize()
     counts = {str(p): {"mean": round(float(tabs[p].sel_count.float().mean()), 3), "max": int(tabs[p].sel_count.max())} for p in SHARES}
     base, tab = res["window_merged"]["median_ms"], res["table_full"]
-    return {"config": config, "inputs": inputs, "dtype": str(dt), "S": S, "heads": H, "sliding_heads": n, "n_tiles": n_tiles,
+    return {"config": config, "inputs": inputs, "precision": a.precision, "dtype": str(dt), "S": S, "heads": H, "sliding_heads": n, "n_tiles": n_tiles,
             "tok": tok, "n_kv": n_kv, "n_sel": (n_kv - te) // tok, "rounds": a.rounds, "device": torch.cuda.get_device_name(0),
             "arms": res, "kept_tiles": counts,
             "ratio_to_window_merged": {name: round(res[name]["median_ms"] / base, 4) for name in res if name.startswith("share_0")},
@@ -108,6 +113,7 @@ def accuracy_of(a, config, lines):
         q, k, v = (x.to(dt) for x in SI.structured_layer(latent, [2, 1, 0], cfg["tile"], cfg["group"], noise, gen, dev))
         kw = dict(model="wan", fp8=False)  # (video tokens alone: the families have no text part)
         dense = routed_attention(q, k, v, HeadRouting.from_expert_ids([0, 0, 0], dev), geoms["window"], **kw).float()
+        kw["fp8"] = False if a.precision == "native" else a.precision  # (the dense reference stays in the input dtype)
         rel, kept = {}, {}
         for name, geom in geoms.items():
             o = routed_attention(q, k, v, HeadRouting.from_expert_ids([2, 2, 2], dev), geom, **kw).float()
@@ -116,7 +122,7 @@ def accuracy_of(a, config, lines):
                 kept[name] = geom.share_buffers(0, 3, 256).sel_count.float().mean(1).tolist()
         n_sel = geoms[SHARES[0]].share_buffers(0, 3, 256).sel_tiles.shape[2]
         for h, fam in enumerate(FAMILIES):
-            lines.append(f"noise {noise}: {fam:9s} head: rel_error window {rel['window'][h]:.5f} ({n_sel} tiles)  " +
+            lines.append(f"noise {noise}: {a.precision} {fam:9s} head: rel_error window {rel['window'][h]:.5f} ({n_sel} tiles)  " +
                          "  ".join(f"share {p}: {rel[p][h]:.5f} ({kept[p][h]:.2f} tiles)" for p in SHARES))
 
 
@@ -125,6 +131,7 @@ def main():
     ap.add_argument("what", choices=["timing", "accuracy"])
     ap.add_argument("--config", action="append", choices=sorted(bench.CONFIGS), help="repeatable; default: hunyuan-129f")
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--precision", choices=["native", "i8pv"], default="native", help="the precision of every attention launch")
     ap.add_argument("--noise", type=float, action="append", help="accuracy: white-noise share of the structured heads; repeatable")
     ap.add_argument("--out", default="")
     a = ap.parse_args()

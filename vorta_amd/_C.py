@@ -321,6 +321,7 @@ SYMBOLS = {
     "vorta_sta_select_tiles_share_args_size": (C.c_int, []),
     "vorta_sta_select_tiles_share_ws_floats": (_i64, [C.POINTER(StaShareArgs)]),
     "vorta_attn_fwd_varlen": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnVarlenExt), _vp]),
+    "vorta_attn_fwd_varlen_i8": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnI8Ext), C.POINTER(AttnVarlenExt), _vp]),
     "vorta_attn_varlen_ext_size": (C.c_int, []),
     "vorta_router_route": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),

@@ -1,4 +1,4 @@
-// Diagnostic variants of the int8-score attention loop (attn_fwd_i8.hip includes this inside attn_i8_body when the build
+// Diagnostic variants of the int8-score attention loop (attn_i8_body.h includes this inside attn_i8_body when the build
 // defines VORTA_I8_DIAG -- suffixed libraries only, vorta_amd/build.py refuses extra flags for the product library).
 // Everything here RE-DEFINES a macro of the product loop; nothing here is compiled into libvorta_hip.so.
   // Timing ablations (suffixed diagnostic libraries only; each removes one ingredient of the step and gives WRONG RESULTS;
@@ -20,7 +20,7 @@
 #define DMA_V(slot_)
 #undef REQ_TAIL
 #undef ROWS_UPDATE
-#define REQ_TAIL(bw_)
+#define REQ_TAIL(bw_, jabs_)
 #endif
 #ifdef VORTA_I8_DIAG_NOSEED
 #undef MAKE_SEEDS

@@ -154,7 +154,7 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     a = _C.AttnArgs()
     a.struct_size = C.sizeof(_C.AttnArgs)
     a.dtype = _C.VORTA_FP8E4M3 if fp8 else _DT[q.dtype]
-    a._ext = None
+    a._ext = a._ext2 = None
     a._family = _FAMILIES["i8" if i8 else "fp8" if fp8 else "mx" if mixed else "16"]
     a._out_type = "_Float16" if out.dtype == torch.float16 else "__bf16"  # T of the kernel symbols
     a._device = out.device
@@ -257,8 +257,9 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     if q_block_table is not None:
         a.q_block_table, a.n_q_blocks = _ptr(q_block_table), q_block_table.shape[0]
     if kv_len is not None or order is not None:
-        if fp8 or mixed or i8:
-            raise ValueError("key lists of different lengths (kv_len=) run in 16 bits only: there is no 8-bit variable-length body")
+        if fp8 or mixed:
+            raise ValueError("key lists of different lengths (kv_len=) run in 16 bits and with int8 scores (int8 k, e4m3 v): there is no "
+                             + ("all-e4m3 (e4m3 q, k)" if fp8 else "mixed-precision (16-bit k, e4m3 v)") + " variable-length body")
         if kv_len is None or kv_rows is None or kv_len.dtype != torch.int32 or kv_len.dim() != 2 or kv_len.stride(1) != 1 \
                 or kv_len.shape[0] < n_heads or kv_len.shape[1] < n_groups:
             raise ValueError(f"kv_len must be int32 (slots, groups) covering {n_heads} head slots x {n_groups} key lists of kv_rows")
@@ -272,7 +273,10 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
                 raise ValueError(f"order must be int32 ({n_heads} head slots x {n_blocks} query blocks,) with an explicit block_rows "
                                  "(128 / 256): one logical workgroup per physical block")
             ext.order = order.data_ptr()
-        a._ext, a._family = ext, _FAMILIES["varlen"]
+        if i8:  # csrc/attn_fwd_i8_varlen.hip: the int8 ext first, then the tables
+            a._ext2, a._family = ext, _FAMILIES["varlen_i8"]
+        else:
+            a._ext, a._family = ext, _FAMILIES["varlen"]
     ws = None
     if n_splits > 1:
         so, sm = C.c_uint64(), C.c_uint64()
@@ -299,11 +303,13 @@ _FAMILIES = {
     "i8": _Family("vorta_attn_fwd_i8", "vorta_attn_fwd_batch_i8", "attn_i8_kernel<{t},{nw},{tab}>", "attn_i8_multi_kernel<{t}>"),
     # key lists of different lengths (csrc/attn_fwd_varlen.hip): a launch of its own, no fused grid takes it
     "varlen": _Family("vorta_attn_fwd_varlen", None, "attn_varlen_kernel<{t},{nw}>", None),
+    # ... with int8 scores (csrc/attn_fwd_i8_varlen.hip): the same, behind the int8 operands' ext
+    "varlen_i8": _Family("vorta_attn_fwd_varlen_i8", None, "attn_i8_varlen_kernel<{t},{nw}>", None),
 }
 
 
 def _ext(a) -> tuple:
-    return () if a._ext is None else (C.byref(a._ext),)
+    return tuple(C.byref(e) for e in (a._ext, a._ext2) if e is not None)
 
 
 def _launch_one(a):
@@ -346,7 +352,9 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tenso
 def attn_fwd_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, kv_len: torch.Tensor,
                     order: Optional[torch.Tensor] = None, tag: str = "", flops: float = 0.0, **kw) -> None:
     """vorta_attn_fwd_varlen: `attn_fwd` for query groups whose key lists have different lengths.  16-bit q, k, v, out, D = 128,
-    `kv_rows` required; `n_kv` is the longest list.  kv_len: int32 (slots, groups), the key positions group g of slot y attends
+    `kv_rows` required; `n_kv` is the longest list.  With int8 k and e4m3 v (`i8=` the I8Operands of `i8_quantize_k`, `v_descale=`
+    of `fp8_quantize_v`, as `attn_fwd` takes them) it is vorta_attn_fwd_varlen_i8: per group the bits of the int8-score launch
+    over that group's list alone; all-e4m3 and mixed-precision operands are refused by name.  kv_len: int32 (slots, groups), the key positions group g of slot y attends
     (the kernel clamps it into [1, n_kv] and reads no list entry behind it).  order: optional int32 (slots * query blocks,), the
     logical workgroup (slot * query blocks + query block) physical block b computes -- a permutation, `sta_select_tiles_share`
     writes one with the longest key loops first; needs an explicit `block_rows`.  No split keys, no duplicate rows."""

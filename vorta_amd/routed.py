@@ -75,7 +75,8 @@ def set_sliding_keys(name: str, mass_share: Optional[float] = None) -> None:
     ops.sta_select_tiles) or "mass" (as many tiles, chosen by the attention mass that sampled query rows of the
     tile put on every key tile: ops.sta_tile_mass).  Overrides the environment switch VORTA_SLIDING_KEYS; read when a geometry is built.
     "share" (the FEWEST tiles, in that mass ranking, that hold `mass_share` of the tile's sampled mass, at most the window's
-    count: ops.sta_select_tiles_share and the variable-length launch ops.attn_fwd_varlen) takes its share here,
+    count: ops.sta_select_tiles_share and the variable-length launch ops.attn_fwd_varlen, in 16 bits or under "i8pv"; DESIGN.md
+    6.12) takes its share here,
     from a geometry's own `mass_share=` or from VORTA_SLIDING_MASS_SHARE; there is no default share."""
     global _sliding_keys, _mass_share
     name = _check_sliding_keys(name, "set_sliding_keys")
@@ -1097,9 +1098,14 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
         if record is not None or (torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v))):
             raise ValueError("sliding_keys='share' in grad mode: the backward replays key lists of one length per launch; a "
                              "variable-length backward is missing -- train under 'window', 'content' or 'mass'")
-        if (operands.precision if operands is not None else precision_of(fp8)) != "native":
-            raise ValueError("sliding_keys='share' under an 8-bit precision: the variable-length launch (ops.attn_fwd_varlen) has a "
-                             "16-bit body only -- run it with fp8=False")
+        prec = operands.precision if operands is not None else precision_of(fp8)
+        if prec not in ("native", "i8pv"):
+            # (the selection reads the 16-bit q, k whatever the precision; what is missing is an attention body)
+            raise ValueError(f"sliding_keys='share' under precision {prec!r}: the variable-length launch (ops.attn_fwd_varlen) has a "
+                             "16-bit and an int8-score body, no "
+                             + {"fp8pv": "mixed-precision one (16-bit k, e4m3 v)",
+                                "auto8": "mixed-precision one (16-bit k, e4m3 v), which 'auto8' needs for its heavy-tailed heads"
+                                }.get(prec, "all-e4m3 one") + " -- run it under 'native' or 'i8pv'")
     if operands is None:
         # (video_tokens: the sample is summed in eighths of the video tokens + the text, as the sequence-parallel send side sums it)
         operands = prepare_operands(precision_of(fp8), q3, k3, v3, scale, fp8_operands,
