@@ -71,6 +71,49 @@ def test_groups_of_different_key_counts_in_one_launch(case, dtype, block_rows, r
     assert err <= ATOL_SAME[dtype]
 
 
+@pytest.mark.parametrize("family", ["16", "i8"])
+def test_refusals_keep_their_code_and_precedence(case, family, monkeypatch):
+    """vorta_attn_fwd_varlen and vorta_attn_fwd_varlen_i8 share one entry frame (csrc/attn_common.h fill_var_tables): a wrong
+    ext size is VORTA_EINVAL before anything else, split keys are VORTA_EUNSUPPORTED before the tables are looked at, a kv_len
+    stride below the groups and a missing kv_rows are VORTA_EINVAL.  Nothing is launched."""
+    import ctypes as C
+    from vorta_amd import _C, ops
+    q, k, v, q_rows, kv_rows, kv_len = case
+    t = lambda a: torch.as_tensor(a, device=dev())  # noqa: E731
+    qd, kd, vd = (to_dev(np.nan_to_num(x), torch.bfloat16) for x in (q, k, v))
+    kv, name, ops_kw = t(kv_rows), "vorta_attn_fwd_varlen", {}
+    if family == "i8":
+        i8 = ops.i8_quantize_k(qd, kd)
+        vd, descale, _ = ops.fp8_quantize_v(vd)
+        kd, name, ops_kw = i8.k8, "vorta_attn_fwd_varlen_i8", dict(i8=i8, v_descale=descale)
+    kw = dict(kv_len=t(kv_len), n_q=N_Q, q_group_len=GLEN, n_kv=N_KV, q_rows=t(q_rows), kv_rows=kv, kv_rows_stride_g=kv.stride(1),
+              **ops_kw)
+    out = torch.empty_like(qd)
+    einval, eunsupported = f"^{name} failed: VORTA_EINVAL \\(bad argument\\)$", f"^{name} failed: VORTA_EUNSUPPORTED$"
+    one_row = dict(kw, kv_len=t(kv_len[:1]).expand(H, -1))  # (slots, groups) with a slot stride of 0 < 5 groups
+    with pytest.raises(_C.VortaHipError, match=eunsupported):
+        ops.attn_fwd_varlen(qd, kd, vd, out, **kw, n_splits=2)
+    with pytest.raises(_C.VortaHipError, match=eunsupported):  # ... before the table checks
+        ops.attn_fwd_varlen(qd, kd, vd, out, **one_row, n_splits=2)
+    with pytest.raises(ValueError, match=einval):
+        ops.attn_fwd_varlen(qd, kd, vd, out, **one_row)
+    # a missing kv_rows: the wrapper refuses it by name; behind the wrapper the library answers VORTA_EINVAL
+    with pytest.raises(ValueError, match="^kv_len must be int32 \\(slots, groups\\)"):
+        ops.attn_fwd_varlen(qd, kd, vd, out, **dict(kw, kv_rows=None))
+    a, _ = ops._attn_args(qd, kd, vd, out, **kw)
+    a.kv_rows = None
+    with pytest.raises(ValueError, match=einval):
+        ops._launch_one(a)
+
+    class LongerExt(_C.AttnVarlenExt):  # an ext of another size, as a caller built against another header would pass
+        _fields_ = [("more", C.c_int64)]
+
+    monkeypatch.setattr(_C, "AttnVarlenExt", LongerExt)
+    for more in ({}, dict(n_splits=2)):  # (... before the parent's checks and the unsupported forms)
+        with pytest.raises(ValueError, match=einval):
+            ops.attn_fwd_varlen(qd, kd, vd, out, **kw, **more)
+
+
 def test_split_keys_and_duplicates_are_refused(case):
     from vorta_amd import _C, ops
     q, k, v, q_rows, kv_rows, kv_len = case

@@ -76,6 +76,25 @@ def test_selection_equals_the_restatement(case, t_eff):
         assert torch.equal(fixed[0][:LIVE], tabs.kv_rows[:LIVE]) and torch.equal(fixed[1][:LIVE], tabs.sel_tiles[:LIVE])
 
 
+@pytest.mark.parametrize("t_eff", [0, 5])
+def test_share_and_fixed_count_are_one_order(t_eff):
+    """80 key tiles, a NaN on the diagonal of every score row: every prefix sum is NaN and never compares, so share keeps
+    n_sel tiles -- the n_sel first of its rank order, which must be vorta_sta_select_tiles' (phases 3) bit for bit"""
+    import test_hip_sta_select as W
+    from vorta_amd import ops
+    n_tiles, n_sel, tok = 80, W.WIDE_N_SEL, W.WIDE_TOK
+    score = R.planted_scores(W.WIDE_SLOTS, n_tiles)
+    score[:, np.arange(n_tiles), np.arange(n_tiles)] = np.nan
+    q_rows, tabs = W.wide_tables(n_tiles, t_eff, score)
+    kv, sel = W.wide_select(n_tiles, t_eff, q_rows, tabs)
+    ops.sta_select_tiles_share(W.WIDE[n_tiles], W.WIDE_TILE, W.WIDE_WINDOW, t_eff, q_rows, tabs, mass_share=0.5,
+                               n_heads=W.WIDE_SLOTS, rows_per_tile=tok, block_rows=128)
+    torch.cuda.synchronize()
+    assert R.straddles(sel.cpu().numpy()).all()  # (the kept tiles lie on both sides of tile 64)
+    assert torch.equal(tabs.sel_tiles, sel) and torch.equal(tabs.kv_rows, kv)
+    assert (tabs.sel_count == n_sel).all() and (tabs.kv_len == n_sel * tok + t_eff).all()
+
+
 @pytest.mark.parametrize("dtype", F.DTYPES, ids=F.dtype_name)
 def test_share_launch_against_float64_over_the_lists_it_chose(dtype):
     """head 0 local (its mass on a few tiles: 4 to 7 of 12 kept at p = 0.9 by the restatement on the float64 statistic), head 1

@@ -8,7 +8,9 @@ case first asserts, from the reference alone, that the last selected and the fir
 2 eps apart (the seeds are chosen so); then the lists must be EQUAL.
 
 One geometry: latent (10,6,8), tile (2,3,4): 20 tiles (not a multiple of 32 or of the 4 query tiles of a workgroup) of 24 rows
-(not a multiple of the 16 rows of a pass)."""
+(not a multiple of the 16 rows of a pass).  Then the selection tail alone over MORE than 64 key tiles (80 and 75), on score
+matrices written into ws, against the integer restatement of tests/_share_restate.py."""
+import numpy as np
 import pytest
 import torch
 
@@ -89,6 +91,69 @@ def test_row_map():
     row_map = torch.randperm(N_ROWS, generator=torch.Generator().manual_seed(4))[:S + 5].to(torch.int32).to(dev())
     q, k = _inputs(torch.float16, 1)
     _run(q, k, 6, 5, row_map=row_map)
+
+
+WIDE = {80: (10, 8, 8), 75: (10, 6, 10)}  # n_tiles -> latent at tile (2,2,2): a multiple of a workgroup's 4 tiles; one idle wave
+WIDE_TILE, WIDE_WINDOW, WIDE_TOK, WIDE_N_SEL, WIDE_SLOTS = (2, 2, 2), (3, 3, 3), 8, 27, 2
+
+
+def wide_tables(n_tiles, t_eff, score):
+    """(q_rows, the `sta_share_buffers` of the WIDE geometry with `score` written where the statistic leaves its matrix)"""
+    from vorta_amd import ops
+    q_rows, _ = ops.sta_build_tables(WIDE[n_tiles], WIDE_TILE, WIDE_WINDOW, t_eff, dev())
+    tabs = ops.sta_share_buffers(WIDE_SLOTS, n_tiles, WIDE_N_SEL, WIDE_N_SEL * WIDE_TOK + t_eff, dev(), WIDE_TOK, 1)
+    for x in tabs[:5]:
+        x.fill_(FILL)
+    tabs.ws[:score.size] = torch.as_tensor(score.reshape(-1), device=dev())
+    return q_rows, tabs
+
+
+def wide_select(n_tiles, t_eff, q_rows, tabs):
+    """`sta_select_tiles(phases=3)` over the matrix in tabs.ws, into tables of its own: (kv_rows, sel_tiles)"""
+    from vorta_amd import ops
+    n_kv = WIDE_N_SEL * WIDE_TOK + t_eff
+    kv, sel, ws = ops.sta_select_buffers(WIDE_SLOTS, n_tiles, WIDE_N_SEL, n_kv, dev(), "mass", WIDE_TOK)
+    for b in (kv, sel):
+        b.fill_(FILL)
+    ws[:WIDE_SLOTS * n_tiles * n_tiles] = tabs.ws[:WIDE_SLOTS * n_tiles * n_tiles]
+    dummy = torch.zeros((WIDE_SLOTS, 1, 128), dtype=torch.bfloat16, device=dev())  # (phases 3 reads neither q nor k)
+    ops.sta_select_tiles(dummy, dummy, WIDE[n_tiles], WIDE_TILE, WIDE_WINDOW, t_eff, q_rows, out=(kv, sel, ws), phases=3)
+    torch.cuda.synchronize()
+    return kv, sel
+
+
+@pytest.mark.parametrize("t_eff", [0, 5])
+@pytest.mark.parametrize("n_tiles", list(WIDE))
+def test_more_than_64_key_tiles(n_tiles, t_eff):
+    """both 64-lane passes of the rank and of the ascending list, and the count the list carries from one pass to the next:
+    80 and 75 key tiles of 8 rows, n_sel = 27, a score matrix written into ws (ties in every row, +0 / -0, a NaN), the fixed
+    count and the share selection (mass_share 0.5 of 8 sampled rows) against tests/_share_restate.py as integers"""
+    import _share_restate as R
+    from vorta_amd import ops
+    score = R.planted_scores(WIDE_SLOTS, n_tiles)
+    q_rows, tabs = wide_tables(n_tiles, t_eff, score)
+    rows = q_rows.cpu().numpy()
+    tiles, lists = R.select_fixed(score, WIDE_N_SEL, WIDE_TOK, t_eff, rows)
+    count, s_tiles, kv_len, s_lists = R.select_share(score, 0.5, WIDE_TOK, WIDE_N_SEL, WIDE_TOK, t_eff, rows)
+    # a condition on the inputs: in every slot some row keeps tiles on both sides of tile 64, under either selection
+    assert R.straddles(tiles).all() and R.straddles(s_tiles).all()
+    assert count.min() < WIDE_N_SEL and count.max() == WIDE_N_SEL  # (short lists, and the NaN row's full one)
+
+    kv, sel = wide_select(n_tiles, t_eff, q_rows, tabs)
+    assert (sel.cpu().numpy() == tiles).all(), "sel_tiles differs from the rank order"
+    assert (kv.cpu().numpy() == lists).all(), "kv_rows is not the kept tiles' rows through q_rows, then the text rows"
+
+    ops.sta_select_tiles_share(WIDE[n_tiles], WIDE_TILE, WIDE_WINDOW, t_eff, q_rows, tabs, mass_share=0.5, n_heads=WIDE_SLOTS,
+                               rows_per_tile=WIDE_TOK, block_rows=128)
+    torch.cuda.synchronize()
+    kv, sel, cnt, length, order, _ = (x.cpu().numpy() for x in tabs)
+    assert (cnt == count).all() and (sel == s_tiles).all() and (length == kv_len).all()
+    for y in range(WIDE_SLOTS):
+        for i in range(n_tiles):
+            assert (kv[y, i, :kv_len[y, i]] == s_lists[y][i]).all(), (y, i)
+            assert (kv[y, i, (kv_len[y, i] + 3) // 4 * 4:] == FILL).all(), "written behind the list's length rounded up to 4"
+    assert sorted(order.tolist()) == list(range(WIDE_SLOTS * n_tiles))
+    assert (np.diff(count.reshape(-1)[order]) <= 0).all(), "order: tile counts must not increase"
 
 
 def test_planted_far_tile_is_selected():

@@ -49,7 +49,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=None, suffix: s
         raise SystemExit("VORTA_EXTRA_FLAGS needs VORTA_BUILD_SUFFIX: experimental flags are never built into "
                          "libvorta_hip.so itself")
     lib = LIB if not suffix else os.path.join(CSRC, f"libvorta_hip{suffix}.so")
-    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "attn_bwd_kmajor.h"), os.path.join(CSRC, "attn_i8_body.h"), os.path.join(CSRC, "route_rel_error.h"), os.path.join(CSRC, "sta_geometry.h"),
+    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "attn_bwd_kmajor.h"), os.path.join(CSRC, "attn_i8_body.h"), os.path.join(CSRC, "route_rel_error.h"), os.path.join(CSRC, "sta_geometry.h"), os.path.join(CSRC, "sta_rank.h"),
             os.path.join(CSRC, "attn_fwd_fp8_diag.inc"),
             os.path.join(CSRC, "attn_fwd_i8_diag.inc"), os.path.join(CSRC, "attn_fwd_diag.inc"), os.path.join(INCLUDE, "vorta_hip.h")]
     if extra:  # vorta_build_info() of a variant library names its flags

@@ -73,6 +73,35 @@ __device__ __forceinline__ int live_order(const Params& p, int b, int n, bool re
   return (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (b >> 3);
 }
 
+// ---- the entry frame of the variable-length launches (attn_fwd_varlen.hip, attn_fwd_i8_varlen.hip) ----
+// What vorta_attn_varlen_ext adds to a family's parameter block
+struct VarTables {
+  const int32_t* kv_len; int64_t kv_len_sh;  // [slot][group]
+  const int32_t* order;                      // [grid] or null
+};
+
+// Logical workgroup of the calling physical block: order[block] (clamped into the grid: an entry that is no workgroup id
+// computes some workgroup twice, it reaches no other memory), or the family's XCD-aware index order
+__device__ __forceinline__ int varlen_workgroup(const VarTables& t, const Params& p) {
+  if (t.order) return min(max(__builtin_amdgcn_readfirstlane(t.order[blockIdx.x]), 0), (int)gridDim.x - 1);
+  return live_order(p, blockIdx.x, gridDim.x, p.xcd_remap);
+}
+
+// host.  An entry point checks the ext's size FIRST, then runs its parent's fill_* (with that parent's return codes), then this
+inline bool varlen_ext_sized(const vorta_attn_varlen_ext* ext) { return ext && ext->struct_size == sizeof(vorta_attn_varlen_ext); }
+// p: the parent's filled block.  An empty launch is VORTA_OK with t untouched (the entry point returns before launching)
+inline int fill_var_tables(const vorta_attn_args* a, const vorta_attn_varlen_ext* ext, const Params& p, VarTables& t) {
+  if (p.n_heads == 0 || p.n_groups == 0) return VORTA_OK;
+  // one body per family (not the plain variant 1), no split keys (the lengths differ per group, a split of n_kv does not
+  // divide them) and no duplicate rows
+  if (a->variant == 1 || a->n_splits != 1 || a->dup_rows) return VORTA_EUNSUPPORTED;
+  if (!a->kv_rows || !ext->kv_len || ((uintptr_t)ext->kv_len & 3) || ((uintptr_t)ext->order & 3)) return VORTA_EINVAL;
+  // (with a q_block_table the number of key lists is the caller's: the stride is checked against q_group_len's groups only)
+  if (ext->kv_len_stride_h < (a->q_block_table ? 1 : p.n_groups)) return VORTA_EINVAL;
+  t.kv_len = ext->kv_len; t.kv_len_sh = ext->kv_len_stride_h; t.order = ext->order;
+  return VORTA_OK;
+}
+
 // What logical workgroup wg of a launch works on: split sp of the key blocks [blk0, blk1) of head slot y (tensor head
 // `head`), for the query positions [p0, pend) of group grp (its key list); n_kv and q_valid with their device-resident
 // values applied (no host sync)
@@ -289,6 +318,17 @@ int launch_single(void (*kernel)(PP), int block_rows, const PP& pp, hipStream_t 
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return vorta_set_hip_error(e);
   return launch_combine<T>(pp, st);
+}
+
+// the variable-length launches: the family's kernel of 8 waves (256 query rows a workgroup) or of 4; no splits, so no merge
+template <class PV>
+int launch_varlen(void (*k256)(PV), void (*k128)(PV), const Params& p, const PV& pv, int block_rows, hipStream_t st) {
+  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads;
+  if (total > 0x7fffffff) return VORTA_EINVAL;
+  if (block_rows == 256) hipLaunchKernelGGL(k256, dim3((unsigned)total), dim3(512), 0, st, pv);
+  else hipLaunchKernelGGL(k128, dim3((unsigned)total), dim3(256), 0, st, pv);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
 }
 
 // vorta_attn_fwd and its siblings: one launch of the family's kernel, then the split-key merge

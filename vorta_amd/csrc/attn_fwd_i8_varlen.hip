@@ -23,7 +23,8 @@
 //     4-way unrolled loop are the parent's for every nblk mod 4: a skipped request leaves a slot stale, and a stale slot is
 //     read only into the scores of a block past the end, which feed no P V;
 //   * the logical workgroup comes through `order` (sta_share.hip writes the longest key loops first), clamped into the grid;
-//     NULL: the family's XCD-aware index order.
+//     NULL: the family's XCD-aware index order.  (attn_common.h varlen_workgroup; the tables and the host checks of
+//     vorta_attn_varlen_ext are its VarTables / fill_var_tables, shared with attn_fwd_varlen.hip.)
 // Two further entries for short lists were built and taken out again, both for registers (the loop runs at the VGPR budget):
 // a list of one block going from block 0's scores straight to the drain (no step 0, one barrier instead of three) spilled
 // 21-38 VGPRs, 88-156 B of scratch, with the drain shared or with a drain of its own; the query conversion moved behind the
@@ -48,63 +49,35 @@ using namespace vorta_attn;
 
 struct ParamsI8Var {
   ParamsI8 pi;
-  const int32_t* kv_len; int64_t kv_len_sh;  // [slot][group]
-  const int32_t* order;                      // [grid] or null
+  VarTables t;
 };
 
 template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attn_i8_varlen_kernel(const ParamsI8Var pv) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub
   __shared__ __attribute__((aligned(16))) char smem[SMEM_I8];
-  int wg;
-  if (pv.order) {
-    // (clamped into the grid: an entry that is no workgroup id computes some workgroup twice, it reaches no other memory)
-    wg = min(max(__builtin_amdgcn_readfirstlane(pv.order[blockIdx.x]), 0), (int)gridDim.x - 1);
-  } else {
-    wg = live_order(pv.pi.p, blockIdx.x, gridDim.x, pv.pi.p.xcd_remap);
-  }
-  attn_i8_body<T, NW, true, NSI8, true>(pv.pi, smem, wg, pv.kv_len, pv.kv_len_sh);
+  attn_i8_body<T, NW, true, NSI8, true>(pv.pi, smem, varlen_workgroup(pv.t, pv.pi.p), pv.t.kv_len, pv.t.kv_len_sh);
 #endif
 }
 
-// the int8 entry point's checks (fill_i8), then the variable-length entry point's (attn_fwd_varlen.hip fill_varlen), each
-// with the return code its parent gives
-int fill_i8_varlen(const vorta_attn_args* a, const vorta_attn_i8_ext* i8, const vorta_attn_varlen_ext* ext, ParamsI8Var& pv,
-                   int& block_rows) {
-  if (!ext || ext->struct_size != sizeof(vorta_attn_varlen_ext)) return VORTA_EINVAL;
-  const int rc = fill_i8(a, i8, pv.pi, block_rows);
-  if (rc != VORTA_OK) return rc;
-  const Params& p = pv.pi.p;
-  if (p.n_heads == 0 || p.n_groups == 0) return VORTA_OK;
-  // no split keys (the lengths differ per group, a split of n_kv does not divide them) and no duplicate rows
-  if (a->variant == 1 || a->n_splits != 1 || a->dup_rows) return VORTA_EUNSUPPORTED;
-  if (!a->kv_rows || !ext->kv_len || ((uintptr_t)ext->kv_len & 3) || ((uintptr_t)ext->order & 3)) return VORTA_EINVAL;
-  // (with a q_block_table the number of key lists is the caller's: the stride is checked against q_group_len's groups only)
-  if (ext->kv_len_stride_h < (a->q_block_table ? 1 : p.n_groups)) return VORTA_EINVAL;
-  pv.kv_len = ext->kv_len; pv.kv_len_sh = ext->kv_len_stride_h; pv.order = ext->order;
-  return VORTA_OK;
-}
-
 template <typename T>
-int launch_i8_varlen(const ParamsI8Var& pv, int block_rows, hipStream_t st) {
-  const Params& p = pv.pi.p;
-  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  if (block_rows == 256) hipLaunchKernelGGL((attn_i8_varlen_kernel<T, 8>), dim3((unsigned)total), dim3(512), 0, st, pv);
-  else hipLaunchKernelGGL((attn_i8_varlen_kernel<T, 4>), dim3((unsigned)total), dim3(256), 0, st, pv);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+int launch(const ParamsI8Var& pv, int block_rows, hipStream_t st) {
+  return launch_varlen(attn_i8_varlen_kernel<T, 8>, attn_i8_varlen_kernel<T, 4>, pv.pi.p, pv, block_rows, st);
 }
 
 }  // namespace
 
 extern "C" int vorta_attn_fwd_varlen_i8(const vorta_attn_args* a, const vorta_attn_i8_ext* i8, const vorta_attn_varlen_ext* ext,
                                         void* hip_stream) {
+  // the ext's size, the int8 entry point's checks (fill_i8), then the variable-length entry point's: each with the return
+  // code its parent gives
+  if (!varlen_ext_sized(ext)) return VORTA_EINVAL;
   ParamsI8Var pv{};
   int block_rows = 0;
-  const int rc = fill_i8_varlen(a, i8, ext, pv, block_rows);
+  int rc = fill_i8(a, i8, pv.pi, block_rows);
+  if (rc == VORTA_OK) rc = fill_var_tables(a, ext, pv.pi.p, pv.t);
   if (rc != VORTA_OK) return rc;
   if (pv.pi.p.n_heads == 0 || pv.pi.p.n_groups == 0) return VORTA_OK;
   hipStream_t st = (hipStream_t)hip_stream;
-  return a->dtype == VORTA_BF16 ? launch_i8_varlen<__bf16>(pv, block_rows, st) : launch_i8_varlen<_Float16>(pv, block_rows, st);
+  return a->dtype == VORTA_BF16 ? launch<__bf16>(pv, block_rows, st) : launch<_Float16>(pv, block_rows, st);
 }

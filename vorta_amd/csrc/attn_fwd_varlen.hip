@@ -19,7 +19,8 @@
 //   * a tail block (len not a multiple of 64) is masked as the table body masks it: -inf into the scores past len;
 //   * the logical workgroup comes through `order` (physical block b computes order[b]): key loops of one launch differ by up
 //     to n_sel x, and a grid dealt in index order ends with whichever long loops came last.  sta_share.hip writes the order
-//     longest first.  NULL: the XCD-aware index order of the family.
+//     longest first.  NULL: the XCD-aware index order of the family.  (attn_common.h varlen_workgroup; the tables and the
+//     host checks of vorta_attn_varlen_ext are its VarTables / fill_var_tables, shared with attn_fwd_i8_varlen.hip.)
 // The step is simpler than attn_pipe_dma_body's: scores, softmax and P V of block j in step j (no scores one block ahead),
 // K(j+1) and V(j+1) requested at the top of step j into the slots step j-1 read.
 #include <hip/hip_runtime.h>
@@ -35,8 +36,7 @@ using namespace vorta_attn;
 
 struct ParamsVar {
   Params p;
-  const int32_t* kv_len; int64_t kv_len_sh;  // [slot][group]
-  const int32_t* order;                      // [grid] or null
+  VarTables t;
 };
 
 constexpr int NSV = 2;  // ring depth of the K and of the V tiles: 64 KiB of LDS
@@ -53,7 +53,7 @@ __device__ __forceinline__ void attn_varlen_body(const ParamsVar& pp, char* __re
   if (!decode_work<QB>(p, wg, w)) return;
   const int y = w.y, head = w.head, grp = w.grp;
   // the group's own length: uniform, so it lives in a scalar register and the loop bound is one
-  const int len = max(1, min(__builtin_amdgcn_readfirstlane(pp.kv_len[(int64_t)y * pp.kv_len_sh + grp]), w.n_kv));
+  const int len = max(1, min(__builtin_amdgcn_readfirstlane(pp.t.kv_len[(int64_t)y * pp.t.kv_len_sh + grp]), w.n_kv));
   // a workgroup whose rows are all past q_valid has no key loop: its rows are zero bits whatever the keys hold
   const int nblk = w.p0 >= w.q_valid ? 0 : (len + KVB - 1) / KVB;
 
@@ -244,42 +244,13 @@ template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attn_varlen_kernel(const ParamsVar pp) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the host pass only needs the launch stub
   __shared__ __attribute__((aligned(16))) char smem[2 * NSV * TILE_BYTES];
-  int wg;
-  if (pp.order) {
-    // (clamped into the grid: an entry that is no workgroup id computes some workgroup twice, it reaches no other memory)
-    wg = min(max(__builtin_amdgcn_readfirstlane(pp.order[blockIdx.x]), 0), (int)gridDim.x - 1);
-  } else {
-    wg = live_order(pp.p, blockIdx.x, gridDim.x, pp.p.xcd_remap);
-  }
-  attn_varlen_body<T, NW>(pp, smem, wg);
+  attn_varlen_body<T, NW>(pp, smem, varlen_workgroup(pp.t, pp.p));
 #endif
 }
 
-int fill_varlen(const vorta_attn_args* a, const vorta_attn_varlen_ext* ext, ParamsVar& pp, int& block_rows) {
-  if (!ext || ext->struct_size != sizeof(vorta_attn_varlen_ext)) return VORTA_EINVAL;
-  const int rc = fill_params(a, pp.p, block_rows, 2);  // (a dtype other than bf16 / fp16: VORTA_EUNSUPPORTED there)
-  if (rc != VORTA_OK) return rc;
-  const Params& p = pp.p;
-  if (p.n_heads == 0 || p.n_groups == 0) return VORTA_OK;
-  // one body: the LDS-DMA one; no split keys (the lengths differ per group, a split of n_kv does not divide them) and no
-  // duplicate rows
-  if (a->variant == 1 || a->n_splits != 1 || a->dup_rows) return VORTA_EUNSUPPORTED;
-  if (!a->kv_rows || !ext->kv_len || ((uintptr_t)ext->kv_len & 3) || ((uintptr_t)ext->order & 3)) return VORTA_EINVAL;
-  // (with a q_block_table the number of key lists is the caller's: the stride is checked against q_group_len's groups only)
-  if (ext->kv_len_stride_h < (a->q_block_table ? 1 : p.n_groups)) return VORTA_EINVAL;
-  pp.kv_len = ext->kv_len; pp.kv_len_sh = ext->kv_len_stride_h; pp.order = ext->order;
-  return VORTA_OK;
-}
-
 template <typename T>
-int launch_varlen(const ParamsVar& pp, int block_rows, hipStream_t st) {
-  const Params& p = pp.p;
-  const int64_t total = (int64_t)p.n_groups * p.blocks_per_group * p.n_heads;
-  if (total > 0x7fffffff) return VORTA_EINVAL;
-  if (block_rows == 256) hipLaunchKernelGGL((attn_varlen_kernel<T, 8>), dim3((unsigned)total), dim3(512), 0, st, pp);
-  else hipLaunchKernelGGL((attn_varlen_kernel<T, 4>), dim3((unsigned)total), dim3(256), 0, st, pp);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VORTA_OK : vorta_set_hip_error(e);
+int launch(const ParamsVar& pp, int block_rows, hipStream_t st) {
+  return launch_varlen(attn_varlen_kernel<T, 8>, attn_varlen_kernel<T, 4>, pp.p, pp, block_rows, st);
 }
 
 }  // namespace
@@ -287,11 +258,13 @@ int launch_varlen(const ParamsVar& pp, int block_rows, hipStream_t st) {
 extern "C" int vorta_attn_varlen_ext_size(void) { return (int)sizeof(vorta_attn_varlen_ext); }
 
 extern "C" int vorta_attn_fwd_varlen(const vorta_attn_args* a, const vorta_attn_varlen_ext* ext, void* hip_stream) {
+  if (!varlen_ext_sized(ext)) return VORTA_EINVAL;
   ParamsVar pp{};
   int block_rows = 0;
-  const int rc = fill_varlen(a, ext, pp, block_rows);
+  int rc = fill_params(a, pp.p, block_rows, 2);  // (a dtype other than bf16 / fp16: VORTA_EUNSUPPORTED there)
+  if (rc == VORTA_OK) rc = fill_var_tables(a, ext, pp.p, pp.t);  // (one body: the LDS-DMA one)
   if (rc != VORTA_OK) return rc;
   if (pp.p.n_heads == 0 || pp.p.n_groups == 0) return VORTA_OK;
   hipStream_t st = (hipStream_t)hip_stream;
-  return a->dtype == VORTA_BF16 ? launch_varlen<__bf16>(pp, block_rows, st) : launch_varlen<_Float16>(pp, block_rows, st);
+  return a->dtype == VORTA_BF16 ? launch<__bf16>(pp, block_rows, st) : launch<_Float16>(pp, block_rows, st);
 }

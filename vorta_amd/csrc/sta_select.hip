@@ -11,21 +11,23 @@
 //                             reduction over the 16 row lanes through LDS in a fixed order (the result repeats bit for bit)
 //   sta_select_expand_kernel  one workgroup per (slot, 4 query tiles), a wave per query tile: the slot's k means pass through
 //                             LDS in chunks of 64 tiles (a lane per key tile, rows padded to 129 floats against bank
-//                             conflicts), scores in fp32 on the vector units, kept as order-preserving integer keys; rank
-//                             by counting, ascending list by ballot + prefix count, then the wave writes its tile's key
-//                             list with 16-byte stores
-// phases = 3 ranks a score matrix another statistic left in ws (sta_mass.hip) with the same rank, ballot and stores: the
-// wave's keys come from its row of the matrix in place of the staged means.
+//                             conflicts), scores in fp32 on the vector units, kept as order-preserving integer keys; then
+//                             the tail of sta_rank.h, which sta_share.hip runs too: rank by counting, the ranks below n_sel
+//                             as an ascending list, the tile's key list in 16-byte stores
+// phases = 3 ranks a score matrix another statistic left in ws (sta_mass.hip) with the same tail: the wave's keys come from
+// its row of the matrix in place of the staged means.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vorta_hip.h"
 #include "common.h"
 #include "sta_geometry.h"
+#include "sta_rank.h"
 
 namespace {
 using vorta_sta::Geometry;
 using vorta_sta::MAX_TILES;
+using vorta_sta::order_key;
 
 constexpr int D = 128;          // head_dim: 16 lanes x 8 elements
 constexpr int ROW_LANES = 16;   // rows of a tile in flight per pass (256 threads / 16 lanes a row)
@@ -46,7 +48,7 @@ struct MParams {
 struct EParams {
   const int32_t* n_heads_dev; int n_heads;
   const int32_t* q_rows; const int32_t* row_map;
-  int tok, n_tiles, n_sel, S, t_eff, n_kv;
+  int tok, n_tiles, n_sel, S, t_eff;
   const float* ws;
   const float* scores;  // phases 3: score[y][i][j] of another statistic (sta_mass.hip), ranked in place of <mean q, mean k>
   int32_t* sel_tiles;
@@ -105,13 +107,6 @@ __global__ __launch_bounds__(256) void sta_tile_means_kernel(const MParams p) {
   }
 }
 
-// a float as an unsigned key of the same order (-0 first made +0: the two compare equal, so they must tie); a total order,
-// NaNs included, so every query tile selects EXACTLY n_sel tiles whatever the data holds
-__device__ __forceinline__ uint32_t order_key(float s) {
-  const uint32_t b = __float_as_uint(s + 0.f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void sta_select_expand_kernel(const EParams p) {
   __shared__ float ks[KT][KPAD];
   __shared__ __attribute__((aligned(16))) float qs[QB][D];
@@ -156,64 +151,13 @@ __global__ __launch_bounds__(256) void sta_select_expand_kernel(const EParams p)
     }
   }
   if (!active) return;  // (no barrier below: every wave works on rows of its own)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  vorta_sta::wave_sync();  // (the keys are written)
 
-  // ---- selection: rank among j != i by counting, ascending list by ballot + prefix count ----
-  int32_t* sel_out = p.sel_tiles + ((int64_t)y * p.n_tiles + i) * p.n_sel;
-  int n_out = 0;
-  for (int j0 = 0; j0 < p.n_tiles; j0 += 64) {
-    const int j = j0 + lane;
-    bool take = false;
-    if (j < p.n_tiles) {
-      const uint32_t mine = keys[w][j];
-      int rank = 0;
-      for (int o = 0; o < p.n_tiles; ++o) {
-        const uint32_t other = keys[w][o];  // a broadcast
-        rank += (o != i && (other > mine || (other == mine && o < j))) ? 1 : 0;
-      }
-      take = j == i || rank < p.n_sel - 1;
-    }
-    const uint64_t m = __ballot(take);
-    if (take) {
-      const int pos = n_out + __popcll(m & ((1ull << lane) - 1));
-      if (pos < p.n_sel) {  // (always: the order is total, so exactly n_sel tiles are taken)
-        sel[w][pos] = j;
-        sel_out[pos] = j;
-      }
-    }
-    n_out += __popcll(m);
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-  // ---- expansion: entry e < n_sel tok is q_rows[sel[e / tok] tok + e % tok], then the text rows; 4 entries a lane, one
-  // 16-byte store (the strides are multiples of 4 entries).  Entries between n_kv and the next multiple of 4 repeat entry 0
-  int32_t* dst = p.kv_rows + (int64_t)y * p.kv_sh + (int64_t)i * p.kv_sg;
-  const int n_vid = p.n_sel * p.tok;
-  const int first = n_vid ? p.q_rows[(int64_t)sel[w][0] * p.tok] : 0;
-  for (int e0 = lane * 4; e0 < p.n_kv; e0 += 64 * 4) {
-    int t = e0 / p.tok, within = e0 - t * p.tok;
-    int32_t r[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = e0 + u;
-      if (e < n_vid) {
-        r[u] = p.q_rows[(int64_t)sel[w][t] * p.tok + within];
-      } else if (e < p.n_kv) {
-        const int x = p.S + (e - n_vid);
-        r[u] = p.row_map ? p.row_map[x] : x;
-      } else {
-        r[u] = first;
-      }
-      if (++within == p.tok) { within = 0; ++t; }
-    }
-    u32x4 out;
-    out[0] = (uint32_t)r[0]; out[1] = (uint32_t)r[1]; out[2] = (uint32_t)r[2]; out[3] = (uint32_t)r[3];
-    *(u32x4*)(dst + e0) = out;
-  }
+  // ---- selection and expansion (sta_rank.h): tile i and the n_sel - 1 others of highest key are the ranks below n_sel ----
+  for (int j = lane; j < p.n_tiles; j += 64) sel[w][j] = vorta_sta::tile_rank(keys[w], p.n_tiles, i, j);
+  vorta_sta::ascending_list(sel[w], p.n_tiles, p.n_sel, p.sel_tiles + ((int64_t)y * p.n_tiles + i) * p.n_sel);
+  vorta_sta::expand_key_list(p.kv_rows + (int64_t)y * p.kv_sh + (int64_t)i * p.kv_sg, sel[w], p.n_sel, p.tok, p.t_eff, p.S,
+                             p.q_rows, p.row_map);
 }
 
 int geometry(const vorta_sta_select_args* a, Geometry& g) { return vorta_sta::geometry(a->latent, a->tile, a->window, a->t_eff, g); }
@@ -247,11 +191,9 @@ extern "C" int vorta_sta_select_tiles(const vorta_sta_select_args* a, void* hip_
       if (!x->ptr || ((uintptr_t)x->ptr & 15) || (x->stride_s % 8) || (x->stride_h % 8) || x->stride_s < D) return VORTA_EINVAL;
   }
   if (select) {
-    if (!a->sel_tiles || !a->kv_rows || ((uintptr_t)a->kv_rows & 15)) return VORTA_EINVAL;
-    // 16-byte stores: both strides in whole groups of 4 entries, a tile's row long enough for its list rounded up to 4
-    if ((a->kv_rows_stride_g % 4) || (a->kv_rows_stride_h % 4) || a->kv_rows_stride_g < n_kv ||
-        a->kv_rows_stride_h < (int64_t)g.n_tiles * a->kv_rows_stride_g)
-      return VORTA_EINVAL;
+    if (!a->sel_tiles) return VORTA_EINVAL;
+    rc = vorta_sta::check_key_list_table(a->kv_rows, a->kv_rows_stride_h, a->kv_rows_stride_g, g.n_tiles, n_kv);
+    if (rc != VORTA_OK) return rc;
   }
   hipStream_t st = (hipStream_t)hip_stream;
   if (means) {
@@ -271,7 +213,7 @@ extern "C" int vorta_sta_select_tiles(const vorta_sta_select_args* a, void* hip_
     EParams e{};
     e.n_heads_dev = a->n_heads_dev; e.n_heads = a->n_heads;
     e.q_rows = a->q_rows; e.row_map = a->row_map;
-    e.tok = g.tok; e.n_tiles = g.n_tiles; e.n_sel = g.n_sel; e.S = g.S; e.t_eff = a->t_eff; e.n_kv = n_kv;
+    e.tok = g.tok; e.n_tiles = g.n_tiles; e.n_sel = g.n_sel; e.S = g.S; e.t_eff = a->t_eff;
     e.ws = a->ws; e.scores = a->phases == 3 ? a->ws : nullptr; e.sel_tiles = a->sel_tiles;
     e.kv_rows = a->kv_rows; e.kv_sh = a->kv_rows_stride_h; e.kv_sg = a->kv_rows_stride_g;
     hipLaunchKernelGGL(sta_select_expand_kernel, dim3((unsigned)((g.n_tiles + QB - 1) / QB), (unsigned)a->n_heads), dim3(256),

@@ -6,10 +6,11 @@
 // tile put on the key tiles (sta_mass.hip left score[y][i][j] at the start of ws; a row sums to rows_per_tile) -- at least 1,
 // at most n_sel.  Two launches:
 //   sta_share_select_kernel  one workgroup per (slot, 4 query tiles), a wave per query tile: order-preserving integer keys of
-//                            the wave's row of the matrix in LDS, rank by counting, the scores of ranks < n_sel scattered to
-//                            their rank, ONE lane sums them in rank order in fp32 (a serial chain: the order is the source's),
-//                            the count is broadcast, then ascending list by ballot + prefix count and the key list with
-//                            16-byte stores (the kept tiles' rows, then the text rows), the count and the list's length
+//                            the wave's row of the matrix in LDS, the rank of sta_rank.h (the one sta_select.hip keeps
+//                            n_sel tiles by), the scores of ranks < n_sel scattered to their rank, ONE lane sums them in rank
+//                            order in fp32 (a serial chain: the order is the source's), the count is broadcast, then
+//                            sta_rank.h's ascending list and key list (the kept tiles' rows, then the text rows; 16-byte
+//                            stores), the count and the list's length
 //   sta_share_order_kernel   one workgroup: `order`, the (slot, query block) pairs of the variable-length attention launch by
 //                            tile count, descending, equal counts in index order -- a counting sort (at most n_sel + 1 distinct
 //                            counts; a dead slot counts 0): every wave histograms a contiguous span of the pairs, the spans'
@@ -21,10 +22,13 @@
 #include "vorta_hip.h"
 #include "common.h"
 #include "sta_geometry.h"
+#include "sta_rank.h"
 
 namespace {
 using vorta_sta::Geometry;
 using vorta_sta::MAX_TILES;
+using vorta_sta::order_key;
+using vorta_sta::wave_sync;
 
 constexpr int QB = 4;        // query tiles per selection workgroup: one per wave
 constexpr int OW = 8;        // waves of the ordering workgroup
@@ -48,18 +52,6 @@ struct OParams {
   int32_t* order;
 };
 
-// a float as an unsigned key of the same order (sta_select.hip: -0 first made +0; a total order, NaNs included)
-__device__ __forceinline__ uint32_t order_key(float s) {
-  const uint32_t b = __float_as_uint(s + 0.f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(256) void sta_share_select_kernel(const SParams p) {
   __shared__ uint32_t keys[QB][MAX_TILES];
   __shared__ float ranked[QB][MAX_TILES];  // ranked[r] = the score of the tile of rank r, r < n_sel
@@ -73,22 +65,11 @@ __global__ __launch_bounds__(256) void sta_share_select_kernel(const SParams p) 
   for (int j = lane; j < p.n_tiles; j += 64) keys[w][j] = order_key(row[j]);
   wave_sync();
 
-  // ---- rank: tile i is rank 0, a tile j != i follows the tiles of higher key and the equal ones of lower index ----
-  for (int j0 = 0; j0 < p.n_tiles; j0 += 64) {
-    const int j = j0 + lane;
-    if (j < p.n_tiles) {
-      const uint32_t mine = keys[w][j];
-      int rank = 0;
-      if (j != i) {
-        rank = 1;
-        for (int o = 0; o < p.n_tiles; ++o) {
-          const uint32_t other = keys[w][o];  // a broadcast
-          rank += (o != i && (other > mine || (other == mine && o < j))) ? 1 : 0;
-        }
-      }
-      if (rank < p.n_sel) ranked[w][rank] = row[j];
-      sel[w][j] = rank;  // (the tile's rank for now; the list overwrites entries below the ones it still reads)
-    }
+  // ---- rank (sta_rank.h), the scores of the ranks below n_sel scattered to their rank ----
+  for (int j = lane; j < p.n_tiles; j += 64) {
+    const int rank = vorta_sta::tile_rank(keys[w], p.n_tiles, i, j);
+    if (rank < p.n_sel) ranked[w][rank] = row[j];
+    sel[w][j] = rank;  // (the tile's rank for now: ascending_list turns the ranks into the list)
   }
   wave_sync();
 
@@ -103,50 +84,15 @@ __global__ __launch_bounds__(256) void sta_share_select_kernel(const SParams p) 
   }
   count = __shfl(count, 0);
 
-  // ---- ascending list by ballot + prefix count; unused entries -1 ----
+  // ---- the ranks below count as an ascending list (unused entries -1), expanded into the key list (sta_rank.h) ----
   int32_t* sel_out = p.sel_tiles + ((int64_t)y * p.n_tiles + i) * p.n_sel;
-  int n_out = 0;
-  for (int j0 = 0; j0 < p.n_tiles; j0 += 64) {
-    const int j = j0 + lane;
-    const bool take = j < p.n_tiles && sel[w][j] < count;
-    const uint64_t m = __ballot(take);
-    wave_sync();  // every lane has read its rank before the list is written over the ranks of lower tiles
-    if (take) {
-      const int pos = n_out + __popcll(m & ((1ull << lane) - 1));  // pos <= j: below every rank still to be read
-      sel[w][pos] = j;
-      sel_out[pos] = j;
-    }
-    n_out += __popcll(m);
-  }
+  vorta_sta::ascending_list(sel[w], p.n_tiles, count, sel_out);
   for (int e = count + lane; e < p.n_sel; e += 64) sel_out[e] = -1;
-  wave_sync();
-
-  // ---- expansion: entry e < count tok is q_rows[sel[e / tok] tok + e % tok], then the text rows; 4 entries a lane, one
-  // 16-byte store.  Entries between the length and the next multiple of 4 repeat entry 0; none is written behind that
-  const int n_vid = count * p.tok, n_kv = n_vid + p.t_eff;
-  int32_t* dst = p.kv_rows + (int64_t)y * p.kv_sh + (int64_t)i * p.kv_sg;
-  const int first = p.q_rows[(int64_t)sel[w][0] * p.tok];
-  for (int e0 = lane * 4; e0 < n_kv; e0 += 64 * 4) {
-    int t = e0 / p.tok, within = e0 - t * p.tok;
-    u32x4 out;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = e0 + u;
-      int r = first;
-      if (e < n_vid) {
-        r = p.q_rows[(int64_t)sel[w][t] * p.tok + within];
-      } else if (e < n_kv) {
-        const int x = p.S + (e - n_vid);
-        r = p.row_map ? p.row_map[x] : x;
-      }
-      out[u] = (uint32_t)r;
-      if (++within == p.tok) { within = 0; ++t; }
-    }
-    *(u32x4*)(dst + e0) = out;
-  }
+  vorta_sta::expand_key_list(p.kv_rows + (int64_t)y * p.kv_sh + (int64_t)i * p.kv_sg, sel[w], count, p.tok, p.t_eff, p.S,
+                             p.q_rows, p.row_map);
   if (lane == 0) {
     p.sel_count[(int64_t)y * p.n_tiles + i] = count;
-    p.kv_len[(int64_t)y * p.n_tiles + i] = n_kv;
+    p.kv_len[(int64_t)y * p.n_tiles + i] = count * p.tok + p.t_eff;
   }
 }
 
@@ -237,12 +183,8 @@ extern "C" int vorta_sta_select_tiles_share(const vorta_sta_share_args* a, void*
   if ((r != 8 && r != 16 && r != 32) || r > g.tok || a->blocks_per_group < 1) return VORTA_EINVAL;
   if (a->n_heads == 0) return VORTA_OK;
   const int n_kv = g.n_sel * g.tok + a->t_eff;
-  if (!a->q_rows || !a->ws || ((uintptr_t)a->ws & 15) || !a->sel_count || !a->sel_tiles || !a->kv_len || !a->kv_rows ||
-      ((uintptr_t)a->kv_rows & 15))
-    return VORTA_EINVAL;
-  // 16-byte stores: both strides in whole groups of 4 entries, a tile's row long enough for its longest list rounded up to 4
-  if ((a->kv_rows_stride_g % 4) || (a->kv_rows_stride_h % 4) || a->kv_rows_stride_g < n_kv ||
-      a->kv_rows_stride_h < (int64_t)g.n_tiles * a->kv_rows_stride_g)
+  if (!a->q_rows || !a->ws || ((uintptr_t)a->ws & 15) || !a->sel_count || !a->sel_tiles || !a->kv_len) return VORTA_EINVAL;
+  if (vorta_sta::check_key_list_table(a->kv_rows, a->kv_rows_stride_h, a->kv_rows_stride_g, g.n_tiles, n_kv) != VORTA_OK)
     return VORTA_EINVAL;
   if ((int64_t)a->n_heads * g.n_tiles * a->blocks_per_group > 0x7fffffff) return VORTA_EINVAL;
   hipStream_t st = (hipStream_t)hip_stream;

@@ -754,10 +754,7 @@ def coreset_select(x: torch.Tensor, latent: Sequence[int], group: Sequence[int],
 
 def sta_table_sizes(latent, tile, window, t_eff: int = 0) -> Tuple[int, int, int]:
     """(n_tiles, tokens_per_tile, n_kv) -- host-only geometry query (works without a GPU)."""
-    a = _C.StaArgs()
-    a.struct_size = C.sizeof(_C.StaArgs)
-    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
-    a.t_eff = t_eff
+    a = _sta_args(latent, tile, window, t_eff)
     nt, tok, nkv = C.c_int32(), C.c_int32(), C.c_int32()
     _C.check(_C.lib().vorta_sta_table_sizes(C.byref(a), C.byref(nt), C.byref(tok), C.byref(nkv)), "vorta_sta_table_sizes")
     return nt.value, tok.value, nkv.value
@@ -773,15 +770,45 @@ def sta_build_tables(latent, tile, window, t_eff: int, device, row_map: Optional
         raise _C.VortaHipError("sta_build_tables needs a cuda device")
     q_rows = torch.empty(S, dtype=torch.int32, device=dev)
     kv_rows = torch.empty((n_tiles, n_kv), dtype=torch.int32, device=dev)
-    a = _C.StaArgs()
-    a.struct_size = C.sizeof(_C.StaArgs)
-    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
-    a.t_eff = t_eff
-    a.row_map = _ptr(row_map)
-    a.q_rows, a.kv_rows = q_rows.data_ptr(), kv_rows.data_ptr()
+    a = _sta_args(latent, tile, window, t_eff, q_rows, row_map)
+    a.kv_rows = kv_rows.data_ptr()
     with torch.cuda.device(dev):
         _C.check(_C.lib().vorta_sta_build_tables(C.byref(a), _stream()), "vorta_sta_build_tables")
     return q_rows, kv_rows
+
+
+def _sta_args(latent, tile, window, t_eff: int, q_rows: Optional[torch.Tensor] = None, row_map: Optional[torch.Tensor] = None,
+              cls=_C.StaArgs):
+    """an argument struct of the sliding-tile family (StaArgs, StaSelectArgs, StaMassArgs, StaShareArgs) with its size, the
+    geometry and the two row tables filled"""
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
+    a.t_eff = t_eff
+    a.q_rows, a.row_map = _ptr(q_rows), _ptr(row_map)
+    return a
+
+
+def _sta_slots(n_heads: Optional[int], head_list: Optional[torch.Tensor], heads: int, n_tiles: int, tok: int, t_eff: int,
+               q_rows: torch.Tensor, row_map: Optional[torch.Tensor] = None) -> int:
+    """the head slots of a selection launch (`n_heads`, else head_list's, else the tensor's `heads`), with the lengths of
+    head_list, q_rows and row_map checked against them and the geometry"""
+    if n_heads is None:
+        n_heads = head_list.numel() if head_list is not None else heads
+    if head_list is not None and head_list.numel() < n_heads:
+        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
+    if q_rows.numel() < n_tiles * tok:
+        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
+    if row_map is not None and row_map.numel() < n_tiles * tok + t_eff:
+        raise ValueError(f"row_map holds {row_map.numel()} rows, video and text {n_tiles * tok + t_eff}")
+    return n_heads
+
+
+def _sta_tables_ok(kv: torch.Tensor, sel: torch.Tensor, ws: torch.Tensor, n_heads: int, n_tiles: int, n_sel: int, n_kv: int) -> bool:
+    """whether (kv_rows, sel_tiles, ws) are tables of `sta_select_buffers` for at least n_heads slots of this geometry"""
+    return (kv.dtype == torch.int32 and sel.dtype == torch.int32 and tuple(kv.shape) == (kv.shape[0], n_tiles, n_kv)
+            and kv.shape[0] >= n_heads and kv.stride(2) == 1 and tuple(sel.shape) == (kv.shape[0], n_tiles, n_sel)
+            and sel.is_contiguous() and ws.dtype == torch.float32)
 
 
 SELECT_SCORES = ("mean", "mass")  # the statistic `sta_select_tiles` ranks key tiles by
@@ -821,21 +848,14 @@ def sta_tile_mass(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_eff:
     if q.dtype not in _DT or q.dtype != k.dtype:
         raise _C.VortaHipError("sta_tile_mass failed: VORTA_EUNSUPPORTED (q, k of one dtype, bf16 or fp16)")
     n_tiles, tok, _ = sta_table_sizes(latent, tile, window, t_eff)
-    if n_heads is None:
-        n_heads = head_list.numel() if head_list is not None else q.shape[0]
-    if head_list is not None and head_list.numel() < n_heads:
-        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
-    if q_rows.numel() < n_tiles * tok:
-        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
-    a = _C.StaMassArgs()
-    a.struct_size = C.sizeof(_C.StaMassArgs)
+    n_heads = _sta_slots(n_heads, head_list, q.shape[0], n_tiles, tok, t_eff, q_rows)
+    a = _sta_args(latent, tile, window, t_eff, q_rows, cls=_C.StaMassArgs)
     a.dtype, a.head_dim, a.n_heads = _DT[q.dtype], q.shape[-1], n_heads
     a.q, a.k = _tensor(q), _tensor(k)
     a.head_list, a.n_heads_dev = _ptr(head_list), _ptr(n_heads_dev)
-    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
-    a.t_eff, a.rows_per_tile = t_eff, rows_per_tile
+    a.rows_per_tile = rows_per_tile
     a.scale = float(q.shape[-1]) ** -0.5 if scale is None else float(scale)
-    a.q_rows, a.ws = _ptr(q_rows), ws.data_ptr()
+    a.ws = ws.data_ptr()
     need = _C.lib().vorta_sta_tile_mass_ws_floats(C.byref(a))
     _C.check(min(need, 0), "vorta_sta_tile_mass_ws_floats")
     if ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() < need:
@@ -868,32 +888,19 @@ def sta_select_tiles(q: torch.Tensor, k: torch.Tensor, latent, tile, window, t_e
         raise _C.VortaHipError("sta_select_tiles failed: VORTA_EUNSUPPORTED (q, k of one dtype, bf16 or fp16)")
     n_tiles, tok, n_kv = sta_table_sizes(latent, tile, window, t_eff)
     n_sel = (n_kv - t_eff) // tok
-    if n_heads is None:
-        n_heads = head_list.numel() if head_list is not None else q.shape[0]
-    if head_list is not None and head_list.numel() < n_heads:
-        raise ValueError(f"head_list holds {head_list.numel()} heads, n_heads = {n_heads}")
-    if q_rows.numel() < n_tiles * tok:
-        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
-    if row_map is not None and row_map.numel() < n_tiles * tok + t_eff:
-        raise ValueError(f"row_map holds {row_map.numel()} rows, video and text {n_tiles * tok + t_eff}")
+    n_heads = _sta_slots(n_heads, head_list, q.shape[0], n_tiles, tok, t_eff, q_rows, row_map)
     kv, sel, ws = out if out is not None else sta_select_buffers(n_heads, n_tiles, n_sel, n_kv, q.device, scores, rows_per_tile)
     ws_floats = n_heads * n_tiles * n_tiles if phases == 3 else n_heads * 2 * n_tiles * 128
-    if kv.dtype != torch.int32 or sel.dtype != torch.int32 or tuple(kv.shape) != (kv.shape[0], n_tiles, n_kv) \
-            or kv.shape[0] < n_heads or kv.stride(2) != 1 or tuple(sel.shape) != (kv.shape[0], n_tiles, n_sel) \
-            or not sel.is_contiguous() or ws.dtype != torch.float32 or (scores == "mean" and ws.numel() < ws_floats):
+    if not _sta_tables_ok(kv, sel, ws, n_heads, n_tiles, n_sel, n_kv) or (scores == "mean" and ws.numel() < ws_floats):
         raise ValueError("sta_select_tiles: out= the buffers of sta_select_buffers for at least n_heads slots of this geometry")
-    a = _C.StaSelectArgs()
-    a.struct_size = C.sizeof(_C.StaSelectArgs)
-    a.dtype, a.head_dim, a.n_heads = _DT[q.dtype], q.shape[-1], n_heads
-    a.q, a.k = _tensor(q), _tensor(k)
-    a.head_list, a.n_heads_dev = _ptr(head_list), _ptr(n_heads_dev)
-    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
-    if scores == "mass":  # (checks ws against the statistic's own size)
+    if scores == "mass":  # the statistic (it checks ws against its own size), then the selection from its matrix
         sta_tile_mass(q, k, latent, tile, window, t_eff, q_rows, ws, scale=scale, rows_per_tile=rows_per_tile,
                       head_list=head_list, n_heads=n_heads, n_heads_dev=n_heads_dev)
         phases = 3
-    a.t_eff, a.phases = t_eff, phases
-    a.row_map, a.q_rows = _ptr(row_map), _ptr(q_rows)
+    a = _sta_args(latent, tile, window, t_eff, q_rows, row_map, cls=_C.StaSelectArgs)
+    a.dtype, a.head_dim, a.n_heads, a.phases = _DT[q.dtype], q.shape[-1], n_heads, phases
+    a.q, a.k = _tensor(q), _tensor(k)
+    a.head_list, a.n_heads_dev = _ptr(head_list), _ptr(n_heads_dev)
     a.sel_tiles, a.kv_rows = sel.data_ptr(), kv.data_ptr()
     a.kv_rows_stride_h, a.kv_rows_stride_g = kv.stride(0), kv.stride(1)
     a.ws = ws.data_ptr()
@@ -935,23 +942,16 @@ def sta_select_tiles_share(latent, tile, window, t_eff: int, q_rows: torch.Tenso
         raise ValueError("sta_select_tiles_share: block_rows is the variable-length launch's, 128 or 256")
     bpg = -(-tok // block_rows)
     kv, sel, cnt, kv_len, order, ws = out
-    if any(t.dtype != torch.int32 for t in (kv, sel, cnt, kv_len, order)) or tuple(kv.shape) != (kv.shape[0], n_tiles, n_kv) \
-            or kv.shape[0] < n_heads or kv.stride(2) != 1 or tuple(sel.shape) != (kv.shape[0], n_tiles, n_sel) \
-            or not (sel.is_contiguous() and cnt.is_contiguous() and kv_len.is_contiguous() and order.is_contiguous()) \
+    if not _sta_tables_ok(kv, sel, ws, n_heads, n_tiles, n_sel, n_kv) or not ws.is_contiguous() \
+            or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (cnt, kv_len, order)) \
             or tuple(cnt.shape) != (n_heads, n_tiles) or tuple(kv_len.shape) != (n_heads, n_tiles) \
-            or order.numel() != n_heads * n_tiles * bpg or ws.dtype != torch.float32 or not ws.is_contiguous():
+            or order.numel() != n_heads * n_tiles * bpg:
         raise ValueError("sta_select_tiles_share: out= the tables of sta_share_buffers for exactly n_heads slots of this geometry "
                          "and ceil(tok / block_rows) blocks a tile")
-    if q_rows.numel() < n_tiles * tok:
-        raise ValueError(f"q_rows holds {q_rows.numel()} rows, the latent grid {n_tiles * tok}")
-    if row_map is not None and row_map.numel() < n_tiles * tok + t_eff:
-        raise ValueError(f"row_map holds {row_map.numel()} rows, video and text {n_tiles * tok + t_eff}")
-    a = _C.StaShareArgs()
-    a.struct_size = C.sizeof(_C.StaShareArgs)
+    _sta_slots(n_heads, None, n_heads, n_tiles, tok, t_eff, q_rows, row_map)
+    a = _sta_args(latent, tile, window, t_eff, q_rows, row_map, cls=_C.StaShareArgs)
     a.n_heads, a.n_heads_dev = n_heads, _ptr(n_heads_dev)
-    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
-    a.t_eff, a.rows_per_tile, a.mass_share, a.blocks_per_group = t_eff, rows_per_tile, float(mass_share), bpg
-    a.row_map, a.q_rows = _ptr(row_map), _ptr(q_rows)
+    a.rows_per_tile, a.mass_share, a.blocks_per_group = rows_per_tile, float(mass_share), bpg
     a.sel_count, a.sel_tiles, a.kv_rows = cnt.data_ptr(), sel.data_ptr(), kv.data_ptr()
     a.kv_rows_stride_h, a.kv_rows_stride_g = kv.stride(0), kv.stride(1)
     a.kv_len, a.order, a.ws = kv_len.data_ptr(), order.data_ptr(), ws.data_ptr()
@@ -961,14 +961,6 @@ def sta_select_tiles_share(latent, tile, window, t_eff: int, q_rows: torch.Tenso
         raise ValueError(f"sta_select_tiles_share: ws holds {ws.numel()} float32, the score matrices {need}")
     _C.check(_C.lib().vorta_sta_select_tiles_share(C.byref(a), _stream()), "vorta_sta_select_tiles_share")
     return out
-
-
-def _sta_args(latent, tile, window, t_eff: int):
-    a = _C.StaArgs()
-    a.struct_size = C.sizeof(_C.StaArgs)
-    a.latent, a.tile, a.window = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), (C.c_int32 * 3)(*window)
-    a.t_eff = t_eff
-    return a
 
 
 def sta_partial_sizes(latent, tile, window, t_eff: int = 0) -> Tuple[int, int, int, list]:
@@ -994,9 +986,8 @@ def sta_build_tables_partial(latent, tile, window, t_eff: int, device, row_map: 
         raise _C.VortaHipError("sta_build_tables_partial needs a cuda device")
     q_rows = torch.empty(S, dtype=torch.int32, device=dev)
     kv_rows = torch.empty((n_lists, stride), dtype=torch.int32, device=dev)
-    a = _sta_args(latent, tile, window, t_eff)
-    a.row_map = _ptr(row_map)
-    a.q_rows, a.kv_rows = q_rows.data_ptr(), kv_rows.data_ptr()
+    a = _sta_args(latent, tile, window, t_eff, q_rows, row_map)
+    a.kv_rows = kv_rows.data_ptr()
     with torch.cuda.device(dev):
         _C.check(_C.lib().vorta_sta_build_tables_partial(C.byref(a), _stream()), "vorta_sta_build_tables_partial")
     return q_rows, kv_rows, lens

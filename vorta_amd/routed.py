@@ -327,31 +327,35 @@ class RoutedGeometry:
             self._sta[t_eff] = (q_rows, kv_rows, kv_rows.shape[1])
         return self._sta[t_eff]
 
-    def content_buffers(self, t_eff: int, n_slots: int, own: bool = False):
-        """the (kv_rows, sel_tiles, ws) a content- or mass-keyed sliding call of `n_slots` head slots selects into
-        (`ops.sta_select_buffers`): allocated once per (text length, slot count) and kept with the other lazily built tables,
-        so a call allocates nothing after its first (a captured graph's replay writes the buffers its capture wrote).  Every
-        call overwrites them, in stream order.  own=True: buffers of the caller's own -- for a call whose recorded launches a
-        backward reads later, after other calls have selected."""
+    def selection_buffers(self, t_eff: int, n_slots: int, block_rows: int = 0, own: bool = False):
+        """the tables a content-, mass- or share-keyed sliding call of `n_slots` head slots selects into: the (kv_rows,
+        sel_tiles, ws) of `ops.sta_select_buffers`, or under "share" the `ops.ShareTiles` of `ops.sta_share_buffers` for a launch
+        of `block_rows` (128 / 256, else 256) rows a workgroup.  Allocated once per (text length, slot count, blocks a tile) and
+        kept with the other lazily built tables, so a call allocates nothing after its first (a captured graph's replay writes
+        the buffers its capture wrote).  Every call overwrites them, in stream order.  own=True: buffers of the caller's own --
+        for a call whose recorded launches a backward reads later, after other calls have selected."""
         n_tiles, tok, n_kv = ops.sta_table_sizes(self.latent, self.tile, self.window, t_eff)
-        scores = _SELECT_SCORES[self.sliding_keys]
+        sizes = (n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device)
+        if self.sliding_keys == "share":
+            bpg = -(-tok // (block_rows if block_rows in (128, 256) else 256))
+            build = lambda: ops.sta_share_buffers(*sizes, MASS_ROWS_PER_TILE, bpg)  # noqa: E731
+        else:
+            bpg = 0
+            build = lambda: ops.sta_select_buffers(*sizes, _SELECT_SCORES[self.sliding_keys], MASS_ROWS_PER_TILE)  # noqa: E731
         if own:
-            return ops.sta_select_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device, scores, MASS_ROWS_PER_TILE)
-        key = ("content", t_eff, n_slots)
+            return build()
+        key = ("selection", t_eff, n_slots, bpg)
         if key not in self._sta:
-            self._sta[key] = ops.sta_select_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device, scores,
-                                                    MASS_ROWS_PER_TILE)
+            self._sta[key] = build()
         return self._sta[key]
 
+    def content_buffers(self, t_eff: int, n_slots: int, own: bool = False):
+        """`selection_buffers` of a content- or mass-keyed geometry"""
+        return self.selection_buffers(t_eff, n_slots, own=own)
+
     def share_buffers(self, t_eff: int, n_slots: int, block_rows: int) -> "ops.ShareTiles":
-        """the tables a share-keyed sliding call of `n_slots` head slots and `block_rows` rows a workgroup selects into
-        (`ops.sta_share_buffers`), allocated once and kept as `content_buffers` keeps its own"""
-        key = ("share", t_eff, n_slots, block_rows)
-        if key not in self._sta:
-            n_tiles, tok, n_kv = ops.sta_table_sizes(self.latent, self.tile, self.window, t_eff)
-            self._sta[key] = ops.sta_share_buffers(n_slots, n_tiles, (n_kv - t_eff) // tok, n_kv, self.device, MASS_ROWS_PER_TILE,
-                                                   -(-tok // block_rows))
-        return self._sta[key]
+        """`selection_buffers` of a share-keyed geometry"""
+        return self.selection_buffers(t_eff, n_slots, block_rows)
 
     def prebuild(self, t_eff: int, block_rows: int = 256, content_slots: int = 0) -> None:
         """Build (on the CURRENT stream) every lazily cached device table a routed call with this text length may touch.
@@ -364,10 +368,8 @@ class RoutedGeometry:
             return
         self.sta_tables(t_eff)
         if self.sliding_keys in _SELECT_SCORES:
-            if content_slots > 0 and self.sliding_keys == "share":
-                self.share_buffers(t_eff, content_slots, block_rows if block_rows in (128, 256) else 256)
-            elif content_slots > 0:
-                self.content_buffers(t_eff, content_slots)
+            if content_slots > 0:
+                self.selection_buffers(t_eff, content_slots, block_rows)
             return
         if STA_MERGE and block_rows in (128, 256):
             self.sta_launch_tables(t_eff, block_rows)
@@ -1148,29 +1150,31 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     # ---- expert 2: sliding-tile attention (hunyuan.py:459-507 / wan.py:272-294) ----
     def expert_sliding(base, slot_of, slot_part):
         sl = slot_of(2, H)
+        br = sliding_block_rows if sliding_block_rows in (128, 256) else 256  # of the forms that need one of the two
+
+        def call(n_q, n_kv, **tables):  # one sliding launch; a form brings its tables (and, where it needs `br`, block_rows)
+            return dict(dict(base, out=o_e[2], n_q=n_q, n_kv=n_kv, tag="sliding", flops=nheads(2) * 4.0 * D * n_q * n_kv,
+                             block_rows=sliding_block_rows, **sl), **tables)
+
         if geom.is_partial:
             # always the merged form, one launch per key-list length (RoutedGeometry.sta_partial_launches)
-            br = sliding_block_rows if sliding_block_rows in (128, 256) else 256
-            calls = [dict(base, out=o_e[2], n_q=q_rows.numel(), n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows,
-                          kv_rows_stride_g=stride, q_block_table=table, n_key_lists=n_lists, tag="sliding",
-                          flops=nheads(2) * 4.0 * D * q_rows.numel() * n_kv, block_rows=br, **sl)
+            calls = [call(q_rows.numel(), n_kv, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=stride, q_block_table=table,
+                          n_key_lists=n_lists, block_rows=br)
                      for q_rows, kv_rows, stride, n_kv, table, n_lists in geom.sta_partial_launches(te, br)]
         elif geom.sliding_keys == "share":
             # the fewest key tiles that hold geom.mass_share of the sampled mass: the tile-mass launches at the call's softmax
             # scale, the share selection, then ONE launch whose groups (a tile each) walk key lists of their own lengths, its
             # workgroups ordered longest first.  No fused grid takes it: ops.attn_fwd_batch runs it behind the other experts'
-            br = sliding_block_rows if sliding_block_rows in (128, 256) else 256
             q_rows, _, n_kv = geom.sta_tables(te)
-            tabs = geom.share_buffers(te, sl["n_heads"], br)
+            tabs = geom.selection_buffers(te, sl["n_heads"], br)
             ops.sta_tile_mass(q3, k3, geom.latent, geom.tile, geom.window, te, q_rows, tabs.ws, scale=scale,
                               rows_per_tile=MASS_ROWS_PER_TILE, **sl)
             ops.sta_select_tiles_share(geom.latent, geom.tile, geom.window, te, q_rows, tabs, mass_share=geom.mass_share,
                                        n_heads=sl["n_heads"], rows_per_tile=MASS_ROWS_PER_TILE, block_rows=br,
                                        n_heads_dev=sl.get("n_heads_dev"))
             # (flops: the window's count, an upper bound -- the kept counts live on the device)
-            calls = [dict(base, out=o_e[2], n_q=S, q_group_len=geom.tok, n_kv=n_kv, q_rows=q_rows, kv_rows=tabs.kv_rows,
-                          kv_rows_stride_g=tabs.kv_rows.stride(1), kv_len=tabs.kv_len, order=tabs.order, tag="sliding",
-                          flops=nheads(2) * 4.0 * D * S * n_kv, block_rows=br, **sl)]
+            calls = [call(S, n_kv, q_group_len=geom.tok, q_rows=q_rows, kv_rows=tabs.kv_rows,
+                          kv_rows_stride_g=tabs.kv_rows.stride(1), kv_len=tabs.kv_len, order=tabs.order, block_rows=br)]
         elif geom.sliding_keys in _SELECT_SCORES:
             # key tiles chosen per head and query tile from this call's 16-bit q, k (ops.sta_select_tiles: two launches on
             # this stream by the tile means, three by the sampled attention mass at the call's softmax scale), then the
@@ -1178,22 +1182,17 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
             # keeps lists of its own (its backward reads them after later calls have selected into the shared buffers)
             q_rows, _, n_kv = geom.sta_tables(te)
             kv_rows, _, _ = ops.sta_select_tiles(q3, k3, geom.latent, geom.tile, geom.window, te, q_rows,
-                                                 out=geom.content_buffers(te, sl["n_heads"], own=record is not None),
+                                                 out=geom.selection_buffers(te, sl["n_heads"], own=record is not None),
                                                  scores=_SELECT_SCORES[geom.sliding_keys], scale=scale,
                                                  rows_per_tile=MASS_ROWS_PER_TILE, **sl)
-            calls = [dict(base, out=o_e[2], n_q=S, q_group_len=geom.tok, n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows,
-                          kv_rows_stride_g=kv_rows.stride(1), tag="sliding", flops=nheads(2) * 4.0 * D * S * n_kv,
-                          block_rows=sliding_block_rows, **sl)]
+            calls = [call(S, n_kv, q_group_len=geom.tok, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=kv_rows.stride(1))]
         elif STA_MERGE and sliding_block_rows in (128, 256):
             q_rows, kv_rows, n_kv, table, n_lists = geom.sta_launch_tables(te, sliding_block_rows)
-            calls = [dict(base, out=o_e[2], n_q=S, n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=n_kv,
-                          q_block_table=table, n_key_lists=n_lists, tag="sliding", flops=nheads(2) * 4.0 * D * S * n_kv,
-                          block_rows=sliding_block_rows, **sl)]
+            calls = [call(S, n_kv, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=n_kv, q_block_table=table,
+                          n_key_lists=n_lists)]
         else:
             q_rows, kv_rows, n_kv = geom.sta_tables(te)
-            calls = [dict(base, out=o_e[2], n_q=S, q_group_len=geom.tok, n_kv=n_kv, q_rows=q_rows, kv_rows=kv_rows,
-                          kv_rows_stride_g=n_kv, tag="sliding", flops=nheads(2) * 4.0 * D * S * n_kv,
-                          block_rows=sliding_block_rows, **sl)]
+            calls = [call(S, n_kv, q_group_len=geom.tok, q_rows=q_rows, kv_rows=kv_rows, kv_rows_stride_g=n_kv)]
         if T > 0:
             # text queries see every valid key (sliding_attn_flex.py:108); padded ones see nothing -> zeros
             txt = dict(base, out=o_e[2], n_q=T, q_valid=te, n_kv=S + te, n_splits=_auto_splits(sl["n_heads"], T, S + te),
