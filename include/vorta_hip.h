@@ -803,6 +803,84 @@ int vorta_attn_fwd_varlen_i8(const vorta_attn_args* args, const vorta_attn_i8_ex
                              void* hip_stream);
 
 /*
+ * vorta_sta_select_tiles_share_all -- vorta_sta_select_tiles_share for the FULL-ATTENTION expert: the fewest key tiles, out of
+ * ALL n_tiles, that hold a stated share of the sampled attention mass (a pure addition: the symbol and
+ * vorta_sta_select_tiles_share_all_args_size(); no reference counterpart).
+ *
+ * Geometry (latent, tile; no window: every tile is a candidate) and head slots as vorta_sta_select_tiles_share.  Reads the score
+ * matrix score[y][i][j] that vorta_sta_tile_mass left at the start of ws (vorta_sta_tile_mass_ws_floats() floats sized there;
+ * n_heads * n_tiles * n_tiles are read).  For every head slot y and query tile i:
+ *   rank        as vorta_sta_select_tiles: tile i first, then the tiles j != i by descending score, equal scores to the lower j,
+ *               a NaN by its bits
+ *   count       the length of the shortest prefix of that order whose scores, summed in fp32 in rank order, reach
+ *               mass_share * rows_per_tile (one fp32 product); at least 1, at most n_tiles (a prefix that never reaches it, or a
+ *               NaN sum: n_tiles)
+ * Writes, all caller-owned dense int32:
+ *   sel_count[y][i]          the count ([n_heads][n_tiles])
+ *   sel_tiles[y][i][n_tiles] the kept tiles in ascending tile index, the entries from `count` on -1: the tile lists of
+ *                            vorta_attn_fwd_tilelist
+ *   kv_len[y][i]             = count*tok + t_eff: the key positions of the list, its t_eff text keys included
+ *   order                    optional, [n_heads*n_tiles*blocks_per_group]: the logical workgroups of that launch by tile count,
+ *                            descending, as vorta_sta_select_tiles_share writes it
+ * NO row table is written: a list of up to n_tiles tiles expanded into rows is the whole sequence per (slot, query tile).
+ * Slots at or past *n_heads_dev are not written (order apart).  Two launches on the stream (sta_share_all.hip), no host read, no
+ * allocation, no atomics: graph-capturable, and the same scores give the same tables bit for bit.
+ * Error codes as vorta_sta_select_tiles_share (VORTA_EUNSUPPORTED: more than 1024 tiles).
+ */
+typedef struct vorta_sta_share_all_args {
+  uint32_t struct_size;
+  int32_t n_heads;
+  const int32_t* n_heads_dev;
+  int32_t latent[3], tile[3];
+  int32_t t_eff;
+  int32_t rows_per_tile;
+  float mass_share;
+  int32_t blocks_per_group;
+  int32_t* sel_count;
+  int32_t* sel_tiles;
+  int32_t* kv_len;
+  int32_t* order;
+  const float* ws;
+} vorta_sta_share_all_args;
+
+int vorta_sta_select_tiles_share_all(const vorta_sta_share_all_args* args, void* hip_stream);
+int vorta_sta_select_tiles_share_all_args_size(void);
+
+/*
+ * vorta_attn_fwd_tilelist -- vorta_attn_fwd_varlen whose key lists are TILE lists (a pure addition: the symbol and
+ * vorta_attn_tilelist_ext_size(); vorta_attn_args keeps its size and meaning).
+ *
+ * 16 bits (bf16 / fp16), head_dim 128; query groups, head slots, q_rows and q_valid as vorta_attn_fwd_varlen.  args->kv_rows is
+ * NULL and args->n_kv = n_tiles*tok + t_eff, the longest list.  Group g of head slot y attends, with
+ * count = count[y*count_stride_h + g] clamped into [1, n_tiles], the count*tok + t_eff key positions
+ *   e <  count*tok:  row tile_rows[tiles[y*tiles_stride_h + g*n_tiles + e/tok]*tok + e%tok]   (tile entries clamped into
+ *                    [0, n_tiles); entries behind `count` are not read)
+ *   e >= count*tok:  row S + (e - count*tok)   (a plain (H,S+T,D) layout: no row_map for the text rows)
+ * -- the list vorta_sta_select_tiles_share expands into kv_rows, read through two levels instead: tile_rows is the ONE
+ * tile-major table of vorta_sta_build_tables ([n_tiles*tok], shared by every slot and group), so the launch's tables are
+ * n_tiles ints per list, not n_tiles*tok.  The arithmetic is vorta_attn_fwd_varlen's: for equal lists, equal bits.
+ *   order      optional, as vorta_attn_varlen_ext's
+ * One launch (attn_fwd_tilelist.hip), 256- or 128-row workgroups (block_rows; 0 = the choice of vorta_attn_fwd).
+ * VORTA_EUNSUPPORTED: split keys (n_splits != 1), duplicates (dup_rows), variant 1, a device-resident n_kv, a dtype other than
+ * bf16 / fp16, more than 1024 tiles; VORTA_EINVAL: a kv_rows table, an n_kv other than n_tiles*tok + t_eff, null or misaligned
+ * tables, strides below the groups they cover, and what vorta_attn_fwd refuses -- all before any launch.  No fused grid takes it.
+ */
+typedef struct vorta_attn_tilelist_ext {
+  uint32_t struct_size;
+  int32_t tok, n_tiles, S, t_eff;
+  int32_t reserved;
+  const int32_t* tile_rows;
+  const int32_t* tiles;
+  int64_t tiles_stride_h;
+  const int32_t* count;
+  int64_t count_stride_h;
+  const int32_t* order;
+} vorta_attn_tilelist_ext;
+
+int vorta_attn_fwd_tilelist(const vorta_attn_args* args, const vorta_attn_tilelist_ext* ext, void* hip_stream);
+int vorta_attn_tilelist_ext_size(void);
+
+/*
  * vorta_router_route -- vorta/patch/router.py:33-43 (Router.forward) + the top-1 / tau rule of
  * `_get_routed_qkv` (hunyuan.py:620-624, wan.py:396-400), without the host sync of torch.nonzero.
  *

@@ -95,6 +95,23 @@ class AttnVarlenExt(C.Structure):
     _fields_ = [("struct_size", _u32), ("reserved", _i32), ("kv_len", _vp), ("kv_len_stride_h", _i64), ("order", _vp)]
 
 
+class StaShareAllArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("n_heads", _i32), ("n_heads_dev", _vp),
+        ("latent", _i32 * 3), ("tile", _i32 * 3), ("t_eff", _i32), ("rows_per_tile", _i32),
+        ("mass_share", C.c_float), ("blocks_per_group", _i32),
+        ("sel_count", _vp), ("sel_tiles", _vp), ("kv_len", _vp), ("order", _vp), ("ws", _vp),
+    ]
+
+
+class AttnTilelistExt(C.Structure):
+    _fields_ = [
+        ("struct_size", _u32), ("tok", _i32), ("n_tiles", _i32), ("S", _i32), ("t_eff", _i32), ("reserved", _i32),
+        ("tile_rows", _vp), ("tiles", _vp), ("tiles_stride_h", _i64), ("count", _vp), ("count_stride_h", _i64),
+        ("order", _vp),
+    ]
+
+
 class RouterArgs(C.Structure):
     _fields_ = [
         ("struct_size", _u32), ("dtype", _i32),
@@ -323,6 +340,10 @@ SYMBOLS = {
     "vorta_attn_fwd_varlen": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnVarlenExt), _vp]),
     "vorta_attn_fwd_varlen_i8": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnI8Ext), C.POINTER(AttnVarlenExt), _vp]),
     "vorta_attn_varlen_ext_size": (C.c_int, []),
+    "vorta_sta_select_tiles_share_all": (C.c_int, [C.POINTER(StaShareAllArgs), _vp]),
+    "vorta_sta_select_tiles_share_all_args_size": (C.c_int, []),
+    "vorta_attn_fwd_tilelist": (C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnTilelistExt), _vp]),
+    "vorta_attn_tilelist_ext_size": (C.c_int, []),
     "vorta_router_route": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_scores": (C.c_int, [C.POINTER(RouterArgs), _vp]),
     "vorta_route_plan": (C.c_int, [C.POINTER(RouterArgs), C.c_int32, _vp]),
@@ -439,6 +460,9 @@ def lib():
     if h.vorta_attn_varlen_ext_size() != C.sizeof(AttnVarlenExt):
         raise VortaHipError(f"struct layout mismatch for AttnVarlenExt: C {h.vorta_attn_varlen_ext_size()} "
                             f"vs ctypes {C.sizeof(AttnVarlenExt)}")
+    for name, cls in (("vorta_sta_select_tiles_share_all_args_size", StaShareAllArgs), ("vorta_attn_tilelist_ext_size", AttnTilelistExt)):
+        if getattr(h, name)() != C.sizeof(cls):
+            raise VortaHipError(f"struct layout mismatch for {cls.__name__}: C {getattr(h, name)()} vs ctypes {C.sizeof(cls)}")
     _lib = h
     return h
 

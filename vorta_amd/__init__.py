@@ -37,6 +37,19 @@ def set_sliding_keys(name: str, mass_share=None) -> None:
     _set(name, mass_share)
 
 
+def set_full_keys(name: str, mass_share=None) -> None:
+    """Which keys the full-attention expert attends: "all" (the default: dense attention, the reference's expert) or "share": per
+    head and query tile the FEWEST key tiles, in the ranking of sliding_keys="mass" but out of ALL tiles, that hold the share
+    `mass_share` (in (0, 1]) of the tile's sampled attention mass, the tile itself first, then the text keys; text queries stay
+    dense.  The heads run as one launch that walks tile lists of different lengths.  Also:
+    VORTA_FULL_KEYS=all|share; read when a geometry is built.  No default share: give `mass_share=` here, `full_mass_share=` to the
+    geometry, or VORTA_FULL_MASS_SHARE.  Inference only, 16 bits: refused by name on a partial geometry, under sequence
+    parallelism, in grad mode and the soft-mixture operators, in the per-expert sampled measurement and under every 8-bit
+    precision."""
+    from .routed import set_full_keys as _set
+    _set(name, mass_share)
+
+
 def set_partial_geometry(on: bool) -> None:
     """Accept tile and coreset windows that do not divide the latent grid (off by default; also VORTA_PARTIAL_GEOMETRY=0|1):
     thin last tiles for the sliding-tile expert, the reference's cropped windows plus full-resolution remainder tokens for the

@@ -135,7 +135,8 @@ def launch_routes(q, k, v, out, routes: EvalRoutes, geometry: dict, *, model: st
             if fidelity is not None:  # (the rows as they were BEFORE the repair: the record the repair was decided by)
                 fidelity.append(repaired.fidelity)
         elif repair_above is not None:
-            # the tables are repaired in place, so every other item launches item 0's repaired heads dense
+            # the tables are repaired in place, so every other item launches item 0's repaired heads dense (under
+            # full_keys="share" through the flags routed_attention_repaired keeps with the tables: routed.dense_heads_of)
             routed_attention_repaired(qb, kb, vb, repaired.routes, geom, repair_above=None, out=ob, **kw, **fkw)
         elif tier_routing is not None:
             routed_attention_tiers(qb, kb, vb, tier_routing, geom, out=ob, operands=operands, **kw, **fkw)

@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libvorta_hip.so")
-SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_bwd_dq.hip", "attn_bwd_dkv.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "attn_fwd_varlen.hip", "attn_fwd_i8_varlen.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
-           "sta_tables.hip", "sta_select.hip", "sta_mass.hip", "sta_share.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "expert_fidelity.hip", "sampled_fidelity.hip",
+SOURCES = ["api.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_stats.hip", "attn_bwd_kmajor.hip", "attn_bwd_dq.hip", "attn_bwd_dkv.hip", "attn_fwd_fp8.hip", "attn_fwd_mx.hip", "attn_fwd_i8.hip", "attn_fwd_varlen.hip", "attn_fwd_i8_varlen.hip", "attn_fwd_tilelist.hip", "fp8_quant.hip", "i8_quant.hip", "coreset.hip",
+           "sta_tables.hip", "sta_select.hip", "sta_mass.hip", "sta_share.hip", "sta_share_all.hip", "router.hip", "qk_norm_rope.hip", "qk_norm_rope_bwd.hip", "mix.hip", "expert_fidelity.hip", "sampled_fidelity.hip",
            "sampled_experts.hip", "route_fidelity.hip", "route_fidelity_tiers.hip", "route_budget_tiers.hip", "route_repair.hip", "permute.hip"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent fp32 adds of the softmax row sum into v_pk_add_f32 plus the
 # v_mov pairs to feed them -- more instructions on the VALU issue port that bounds the attention loop (+2 % without)
@@ -49,7 +49,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=None, suffix: s
         raise SystemExit("VORTA_EXTRA_FLAGS needs VORTA_BUILD_SUFFIX: experimental flags are never built into "
                          "libvorta_hip.so itself")
     lib = LIB if not suffix else os.path.join(CSRC, f"libvorta_hip{suffix}.so")
-    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "attn_bwd_kmajor.h"), os.path.join(CSRC, "attn_i8_body.h"), os.path.join(CSRC, "route_rel_error.h"), os.path.join(CSRC, "sta_geometry.h"), os.path.join(CSRC, "sta_rank.h"),
+    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "attn_bwd_kmajor.h"), os.path.join(CSRC, "attn_i8_body.h"), os.path.join(CSRC, "route_rel_error.h"), os.path.join(CSRC, "sta_geometry.h"), os.path.join(CSRC, "sta_rank.h"), os.path.join(CSRC, "sta_order.h"), os.path.join(CSRC, "attn_varlen_body.h"),
             os.path.join(CSRC, "attn_fwd_fp8_diag.inc"),
             os.path.join(CSRC, "attn_fwd_i8_diag.inc"), os.path.join(CSRC, "attn_fwd_diag.inc"), os.path.join(INCLUDE, "vorta_hip.h")]
     if extra:  # vorta_build_info() of a variant library names its flags

@@ -114,8 +114,11 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
                v_descale: Optional[torch.Tensor] = None, fp8_opts: Optional[dict] = None,
                q_block_table: Optional[torch.Tensor] = None, n_key_lists: int = 0,
                i8: Optional["I8Operands"] = None,
-               kv_len: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
+               kv_len: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+               tile_lists: Optional["TileLists"] = None):
     """Fill a vorta_attn_args; returns (args, workspace tensors to keep alive until the launch is enqueued).
+    tile_lists = key lists given as TILE lists (`attn_fwd_tilelist`): the args carry the vorta_attn_tilelist_ext as `_ext`, `n_kv`
+    is n_tiles * tok + the text keys, there is no kv_rows and `order` is the optional workgroup order.
     kv_len (slots, groups) int32 = key lists of different lengths (`attn_fwd_varlen`): the args carry the vorta_attn_varlen_ext
     of vorta_attn_fwd_varlen as `_ext`, `n_kv` is the longest list and `order` the optional workgroup order.
     q,k,v of dtype uint8 = e4m3 operands from `fp8_quantize_qkv` (then `v_descale` is required and `out` is 16-bit):
@@ -256,7 +259,39 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
     a.reserved = NO_XCD_REMAP
     if q_block_table is not None:
         a.q_block_table, a.n_q_blocks = _ptr(q_block_table), q_block_table.shape[0]
-    if kv_len is not None or order is not None:
+
+    def order_ptr():  # the workgroup order of the launches whose key loops differ in length
+        if order is None:
+            return None
+        n_blocks = q_block_table.shape[0] if q_block_table is not None else n_groups * -(-(q_group_len or n_q) // max(block_rows, 1))
+        if block_rows not in (128, 256) or order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous() \
+                or order.numel() != n_heads * n_blocks:
+            raise ValueError(f"order must be int32 ({n_heads} head slots x {n_blocks} query blocks,) with an explicit block_rows "
+                             "(128 / 256): one logical workgroup per physical block")
+        return order.data_ptr()
+
+    if tile_lists is not None:
+        tl = tile_lists
+        if fp8 or mixed or i8:
+            raise ValueError("key lists given as tile lists (tile_lists=) run in 16 bits: there is no 8-bit tile-list body")
+        if kv_rows is not None or kv_len is not None or dup_rows is not None or n_splits != 1:
+            raise ValueError("tile_lists= brings the key rows itself: no kv_rows / kv_len, no duplicate rows, no split keys")
+        n_tiles = tl.tiles.shape[-1] if tl.tiles.dim() == 3 else 0
+        if tl.tok < 1 or n_tiles < 1 or n_kv < n_tiles * tl.tok \
+                or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (tl.tile_rows, tl.tiles, tl.count)) \
+                or tl.tile_rows.numel() < n_tiles * tl.tok or tl.tiles.shape[0] < n_heads or tl.tiles.shape[1] < n_groups \
+                or tl.count.dim() != 2 or tuple(tl.count.shape) != tuple(tl.tiles.shape[:2]):
+            raise ValueError(f"tile_lists: int32 tile_rows (n_tiles*tok,), tiles (slots, groups, n_tiles) and count (slots, groups) "
+                             f"covering {n_heads} head slots x {n_groups} groups, with n_kv = n_tiles*tok + the text keys")
+        t_eff = n_kv - n_tiles * tl.tok
+        ext = _C.AttnTilelistExt()
+        ext.struct_size = C.sizeof(_C.AttnTilelistExt)
+        ext.tok, ext.n_tiles, ext.S, ext.t_eff = tl.tok, n_tiles, n_tiles * tl.tok, t_eff
+        ext.tile_rows, ext.tiles, ext.tiles_stride_h = tl.tile_rows.data_ptr(), tl.tiles.data_ptr(), tl.tiles.stride(0)
+        ext.count, ext.count_stride_h = tl.count.data_ptr(), tl.count.stride(0)
+        ext.order = order_ptr()
+        a._ext, a._family = ext, _FAMILIES["tilelist"]
+    elif kv_len is not None or order is not None:
         if fp8 or mixed:
             raise ValueError("key lists of different lengths (kv_len=) run in 16 bits and with int8 scores (int8 k, e4m3 v): there is no "
                              + ("all-e4m3 (e4m3 q, k)" if fp8 else "mixed-precision (16-bit k, e4m3 v)") + " variable-length body")
@@ -266,13 +301,7 @@ def _attn_args(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
         ext = _C.AttnVarlenExt()
         ext.struct_size = C.sizeof(_C.AttnVarlenExt)
         ext.kv_len, ext.kv_len_stride_h = kv_len.data_ptr(), kv_len.stride(0)
-        if order is not None:
-            n_blocks = q_block_table.shape[0] if q_block_table is not None else n_groups * -(-(q_group_len or n_q) // max(block_rows, 1))
-            if block_rows not in (128, 256) or order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous() \
-                    or order.numel() != n_heads * n_blocks:
-                raise ValueError(f"order must be int32 ({n_heads} head slots x {n_blocks} query blocks,) with an explicit block_rows "
-                                 "(128 / 256): one logical workgroup per physical block")
-            ext.order = order.data_ptr()
+        ext.order = order_ptr()
         if i8:  # csrc/attn_fwd_i8_varlen.hip: the int8 ext first, then the tables
             a._ext2, a._family = ext, _FAMILIES["varlen_i8"]
         else:
@@ -305,6 +334,8 @@ _FAMILIES = {
     "varlen": _Family("vorta_attn_fwd_varlen", None, "attn_varlen_kernel<{t},{nw}>", None),
     # ... with int8 scores (csrc/attn_fwd_i8_varlen.hip): the same, behind the int8 operands' ext
     "varlen_i8": _Family("vorta_attn_fwd_varlen_i8", None, "attn_i8_varlen_kernel<{t},{nw}>", None),
+    # key lists given as tile lists (csrc/attn_fwd_tilelist.hip): the 16-bit variable-length body behind two-level row ids
+    "tilelist": _Family("vorta_attn_fwd_tilelist", None, "attn_tilelist_kernel<{t},{nw}>", None),
 }
 
 
@@ -961,6 +992,73 @@ def sta_select_tiles_share(latent, tile, window, t_eff: int, q_rows: torch.Tenso
         raise ValueError(f"sta_select_tiles_share: ws holds {ws.numel()} float32, the score matrices {need}")
     _C.check(_C.lib().vorta_sta_select_tiles_share(C.byref(a), _stream()), "vorta_sta_select_tiles_share")
     return out
+
+
+class TileLists(NamedTuple):
+    """key lists given as tile lists, the `tile_lists=` of `attn_fwd_tilelist`; all int32 on the device"""
+    tile_rows: torch.Tensor  # (n_tiles * tok,): the tile-major row table of `sta_build_tables` (its q_rows)
+    tiles: torch.Tensor      # (slots, groups, n_tiles): a group's key tiles; entries behind its count are not read
+    count: torch.Tensor      # (slots, groups): listed tiles, clamped into [1, n_tiles] by the kernel
+    tok: int                 # rows of a tile
+
+
+class ShareAllTiles(NamedTuple):
+    """the tables of `sta_select_tiles_share_all`, all int32 on the device"""
+    sel_tiles: torch.Tensor  # (slots, n_tiles, n_tiles): the kept tiles ascending, then -1
+    sel_count: torch.Tensor  # (slots, n_tiles): kept tiles
+    kv_len: torch.Tensor     # (slots, n_tiles): sel_count * tok + t_eff
+    order: torch.Tensor      # (slots * n_tiles * blocks_per_group,): the launch's workgroups, longest key loops first
+    ws: torch.Tensor         # float32: the mass statistic's score matrix and pairs
+
+
+def sta_share_all_buffers(n_slots: int, n_tiles: int, device, rows_per_tile: int = 16, blocks_per_group: int = 1) -> ShareAllTiles:
+    """the caller-owned tables of `sta_select_tiles_share_all` for `n_slots` head slots: tile lists, no row lists"""
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)  # noqa: E731
+    ws = torch.empty(sta_mass_ws_floats(max(n_slots, 1), n_tiles, rows_per_tile), dtype=torch.float32, device=device)
+    return ShareAllTiles(i32(n_slots, n_tiles, n_tiles), i32(n_slots, n_tiles), i32(n_slots, n_tiles),
+                         i32(n_slots * n_tiles * blocks_per_group), ws)
+
+
+def sta_select_tiles_share_all(latent, tile, t_eff: int, out: ShareAllTiles, *, mass_share: float, n_heads: int,
+                               rows_per_tile: int = 16, block_rows: int = 256,
+                               n_heads_dev: Optional[torch.Tensor] = None) -> ShareAllTiles:
+    """vorta_sta_select_tiles_share_all: per head slot and query tile, the FEWEST key tiles out of ALL tiles -- in the rank order
+    of `sta_select_tiles` -- whose scores reach `mass_share` of the sampled mass, at least 1.  Reads the score matrix
+    `sta_tile_mass` left at the start of `out.ws` (at `rows_per_tile`) and writes the other tables of `out`
+    (`sta_share_all_buffers`): the tile lists `attn_fwd_tilelist` walks, their counts, `kv_len` and the workgroup `order` of that
+    launch with q_group_len = tok and `block_rows` (128 / 256) rows per workgroup.  No row list is written.  Two launches, no host
+    read, no allocation."""
+    _require_gpu(*out)
+    n_tiles, tok, _ = sta_table_sizes(latent, tile, (1, 1, 1), t_eff)
+    if block_rows not in (128, 256):
+        raise ValueError("sta_select_tiles_share_all: block_rows is the tile-list launch's, 128 or 256")
+    bpg = -(-tok // block_rows)
+    sel, cnt, kv_len, order, ws = out
+    if any(t.dtype != torch.int32 or not t.is_contiguous() for t in (sel, cnt, kv_len, order)) \
+            or tuple(sel.shape) != (n_heads, n_tiles, n_tiles) or tuple(cnt.shape) != (n_heads, n_tiles) \
+            or tuple(kv_len.shape) != (n_heads, n_tiles) or order.numel() != n_heads * n_tiles * bpg \
+            or ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() < n_heads * n_tiles * n_tiles:
+        raise ValueError("sta_select_tiles_share_all: out= the tables of sta_share_all_buffers for exactly n_heads slots of this "
+                         "geometry and ceil(tok / block_rows) blocks a tile")
+    a = _C.StaShareAllArgs()
+    a.struct_size = C.sizeof(_C.StaShareAllArgs)
+    a.latent, a.tile, a.t_eff = (C.c_int32 * 3)(*latent), (C.c_int32 * 3)(*tile), t_eff
+    a.n_heads, a.n_heads_dev = n_heads, _ptr(n_heads_dev)
+    a.rows_per_tile, a.mass_share, a.blocks_per_group = rows_per_tile, float(mass_share), bpg
+    a.sel_count, a.sel_tiles, a.kv_len = cnt.data_ptr(), sel.data_ptr(), kv_len.data_ptr()
+    a.order, a.ws = order.data_ptr(), ws.data_ptr()
+    _C.check(_C.lib().vorta_sta_select_tiles_share_all(C.byref(a), _stream()), "vorta_sta_select_tiles_share_all")
+    return out
+
+
+def attn_fwd_tilelist(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, tile_lists: TileLists,
+                      order: Optional[torch.Tensor] = None, tag: str = "", flops: float = 0.0, **kw) -> None:
+    """vorta_attn_fwd_tilelist: `attn_fwd_varlen` whose key lists are TILE lists.  16-bit q, k, v, out, D = 128, no `kv_rows`.
+    Group g of slot y attends the rows of its first `tile_lists.count[y, g]` tiles `tile_lists.tiles[y, g]` -- tile j's rows are
+    `tile_rows[j*tok : (j+1)*tok]` -- then the n_kv - n_tiles*tok text rows behind the video rows: the bits `attn_fwd_varlen`
+    writes for that list expanded into rows, without the expanded table.  `n_kv` = n_tiles*tok + the text keys.  order: as
+    `attn_fwd_varlen`'s (`sta_select_tiles_share_all` writes one).  No split keys, no duplicate rows, no 8-bit operands."""
+    attn_fwd(q, k, v, out, tag=tag, flops=flops, tile_lists=tile_lists, order=order, **kw)
 
 
 def sta_partial_sizes(latent, tile, window, t_eff: int = 0) -> Tuple[int, int, int, list]:

@@ -514,6 +514,8 @@ def measured_routes(model: nn.Module, *, max_rel_error: Optional[float] = None, 
     from .. import routed as _routed
     if _routed.sliding_keys_of(None) != "window":  # (the processors' geometries follow the process-wide switch)
         raise ValueError("measured_routes: " + _routed.no_sampled_measurement(_routed.sliding_keys_of(None)))
+    if _routed.full_keys_of(None) != "all":
+        raise ValueError("measured_routes: " + _routed.NO_SAMPLED_FULL_SHARE)
     bound = _check_repair_above("measured_routes", repair_above)
     if bound is not None:
         from ..routed import precision_of

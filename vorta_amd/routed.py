@@ -13,6 +13,8 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
+import weakref
+
 import torch
 
 from . import _partial, ops
@@ -96,6 +98,70 @@ def sliding_keys_of(name: Optional[str] = None) -> str:
         return _sliding_keys
     import os
     return _check_sliding_keys(os.environ.get("VORTA_SLIDING_KEYS") or "window", "VORTA_SLIDING_KEYS")
+
+
+FULL_KEYS = ("all", "share")
+_full_keys: Optional[str] = None  # the process-wide default; None = not set: VORTA_FULL_KEYS, else "all"
+_full_mass_share: Optional[float] = None  # the process-wide share of "share"; None = not set: VORTA_FULL_MASS_SHARE, else an error
+
+
+def _check_full_keys(name, where: str) -> str:
+    if name not in FULL_KEYS:
+        raise ValueError(f"{where}: unknown full keys {name!r} (one of {', '.join(FULL_KEYS)})")
+    return name
+
+
+def set_full_keys(name: str, mass_share: Optional[float] = None) -> None:
+    """the process-wide choice of the FULL-attention expert's keys: "all" (every key: dense attention, the reference's expert) or
+    "share" (per head and query tile the FEWEST key tiles, in the mass ranking of sliding_keys="mass" but out of ALL tiles, that
+    hold `mass_share` of the tile's sampled attention mass, the tile itself first, then the text keys: ops.sta_tile_mass,
+    ops.sta_select_tiles_share_all and the tile-list launch ops.attn_fwd_tilelist, in 16 bits; text queries stay dense;
+    DESIGN.md 6.13).  Overrides VORTA_FULL_KEYS; read when a geometry is built.  "share" takes its share here, from a geometry's
+    own `full_mass_share=` or from VORTA_FULL_MASS_SHARE; there is no default share."""
+    global _full_keys, _full_mass_share
+    name = _check_full_keys(name, "set_full_keys")
+    if mass_share is not None:
+        if name != "share":
+            raise ValueError(f"set_full_keys: mass_share= goes with 'share', not with {name!r}")
+        _full_mass_share = _check_mass_share(mass_share, "set_full_keys")
+    _full_keys = name
+
+
+def full_keys_of(name: Optional[str] = None) -> str:
+    """the choice a geometry built with `full_keys=name` makes: its own, else set_full_keys', else the environment's
+    VORTA_FULL_KEYS, else "all" """
+    if name is not None:
+        return _check_full_keys(name, "full_keys")
+    if _full_keys is not None:
+        return _full_keys
+    import os
+    return _check_full_keys(os.environ.get("VORTA_FULL_KEYS") or "all", "VORTA_FULL_KEYS")
+
+
+def full_mass_share_of(p: Optional[float] = None) -> float:
+    """the share a geometry built with full_keys="share" keeps: its own `full_mass_share=p`, else set_full_keys', else the
+    environment's VORTA_FULL_MASS_SHARE.  There is no default: the share is the user's bound on the mass a head may lose."""
+    if p is not None:
+        return _check_mass_share(p, "full_mass_share")
+    if _full_mass_share is not None:
+        return _full_mass_share
+    import os
+    env = os.environ.get("VORTA_FULL_MASS_SHARE")
+    if not env:
+        raise ValueError("full_keys='share' has no default share: give full_mass_share=p, p in (0, 1] (RoutedGeometry(..., "
+                         "full_mass_share=p), set_full_keys('share', mass_share=p) or VORTA_FULL_MASS_SHARE=p)")
+    return _check_mass_share(env, "VORTA_FULL_MASS_SHARE")
+
+
+def _no_full_share(what: str) -> str:
+    """the refusal of `what` under full_keys='share', by its name"""
+    return (f"full_keys='share' {what}: the full-attention expert's tile lists (ops.attn_fwd_tilelist) are a forward-only 16-bit "
+            "launch over whole tiles of one size, in a plain (H,S,D) layout -- run it under full_keys='all'")
+
+
+NO_SAMPLED_FULL_SHARE = ("full_keys='share': the per-expert sampled measurement takes dense attention as the reference AND as the "
+                         "full expert's candidate; a sampled form of the share-kept full expert is missing -- measure under "
+                         "'all', or verify what was launched (fidelity=, repair_above=)")
 
 
 def _fold(x: torch.Tensor) -> torch.Tensor:
@@ -236,6 +302,11 @@ class RoutedGeometry:
     # under sliding_keys="share": the share of a query tile's sampled attention mass its kept key tiles hold, in (0, 1]; None =
     # set_sliding_keys' / VORTA_SLIDING_MASS_SHARE (no default: an error without one).  Not read under the other choices
     mass_share: Optional[float] = None
+    # which keys the full-attention expert attends: "all" (dense) or "share" (the fewest key tiles, out of all, that hold
+    # `full_mass_share` of a query tile's sampled attention mass); None = set_full_keys / VORTA_FULL_KEYS.
+    # "all" builds and launches what it always did
+    full_keys: Optional[str] = None
+    full_mass_share: Optional[float] = None  # under full_keys="share", in (0, 1]; None = set_full_keys' / VORTA_FULL_MASS_SHARE
 
     def __post_init__(self):
         self.latent, self.tile, self.window, self.group = (tuple(int(v) for v in x) for x in
@@ -254,6 +325,13 @@ class RoutedGeometry:
             if self.row_map is not None:
                 raise ValueError(f"sliding_keys={self.sliding_keys!r} under sequence parallelism (a geometry with a row_map): the selection is "
                                  "not wired into the sequence-parallel engine's slot groups and their per-rank geometries")
+        self.full_keys = full_keys_of(self.full_keys)
+        self.full_mass_share = full_mass_share_of(self.full_mass_share) if self.full_keys == "share" else None
+        if self.full_keys == "share":
+            if self.is_partial:
+                raise ValueError(_no_full_share("on a partial geometry"))
+            if self.row_map is not None:
+                raise ValueError(_no_full_share("under sequence parallelism (a geometry with a row_map)"))
         self.n_keep = int(self.g * (1 - self.rate)) - 1  # coreset_select.py:54
         # the distinct VIDEO key counts of the sliding expert's key lists, longest first (one where the tile divides)
         self.sta_class_n_kv = _partial.sliding_key_counts(self.latent, self.tile, self.window)
@@ -357,6 +435,17 @@ class RoutedGeometry:
         """`selection_buffers` of a share-keyed geometry"""
         return self.selection_buffers(t_eff, n_slots, block_rows)
 
+    def full_share_buffers(self, n_slots: int) -> "ops.ShareAllTiles":
+        """the tile lists a full_keys="share" call of `n_slots` head slots selects into (`ops.sta_share_all_buffers`): allocated
+        once per slot count, for the launch's own rows a workgroup (`_tile_block_rows`), and kept with the other lazily built
+        tables; every call overwrites them, in stream order.  After a call they hold what it selected (`sel_tiles`, `sel_count`)."""
+        n_tiles = self.S // self.tok
+        bpg = -(-self.tok // _tile_block_rows(self.tok))
+        key = ("full_share", n_slots)
+        if key not in self._sta:
+            self._sta[key] = ops.sta_share_all_buffers(n_slots, n_tiles, self.device, MASS_ROWS_PER_TILE, bpg)
+        return self._sta[key]
+
     def prebuild(self, t_eff: int, block_rows: int = 256, content_slots: int = 0) -> None:
         """Build (on the CURRENT stream) every lazily cached device table a routed call with this text length may touch.
         Callers that enqueue routed_attention on several streams call this before they fork: a table built inside one
@@ -431,6 +520,13 @@ class RoutedGeometry:
             table = torch.tensor(rows, dtype=torch.int32).to(self.device)
             self._sta[key] = (q_m, lists, n_kv, table, len(groups))
         return self._sta[key]
+
+
+def _tile_block_rows(tok: int) -> int:
+    """rows a workgroup of the tile-list launch (a query tile is a group of `tok` rows): the library's own choice for
+    block_rows=0 (256-row workgroups run ~1.06x the rate of 128-row ones; padding costs in proportion), made here because the
+    selection's `order` table is sized by it"""
+    return 128 if -(-tok // 256) * 256 * 100 > -(-tok // 128) * 128 * 106 else 256
 
 
 def _auto_splits(n_heads: int, n_q: int, n_kv: int) -> int:
@@ -741,6 +837,8 @@ def sampled_expert_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, g
     hy = model == "hunyuan"
     if geom.sliding_keys in _SELECT_SCORES:
         raise ValueError("sampled_expert_fidelity: " + no_sampled_measurement(geom.sliding_keys))
+    if geom.full_keys == "share":
+        raise ValueError("sampled_expert_fidelity: " + NO_SAMPLED_FULL_SHARE)
     if precision is not None:
         if precision not in ("fp8pv", "i8pv"):
             raise ValueError(f"sampled_expert_fidelity: precision={precision!r} (None, 'fp8pv' or 'i8pv')")
@@ -933,6 +1031,8 @@ def route_by_fidelity(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, geom: R
                          "would meet any bound)")
     if geom.sliding_keys in _SELECT_SCORES:
         raise ValueError("route_by_fidelity: " + no_sampled_measurement(geom.sliding_keys))
+    if geom.full_keys == "share":
+        raise ValueError("route_by_fidelity: " + NO_SAMPLED_FULL_SHARE)
     from .patch.fidelity import expert_work
     fid = sampled_expert_fidelity(q, k, v, geom, model=model, text_len=text_len, text_valid=text_valid, scale=scale, rows=rows,
                                   seed=seed)
@@ -1039,7 +1139,8 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                      expert_outs: Optional[Sequence[torch.Tensor]] = None, fp8=None, fp8_operands=None,
                      operands: Optional[AttnOperands] = None, kv_splits: int = 1,
                      record: Optional[list] = None, fidelity: Optional[list] = None, fidelity_rows=None,
-                     fidelity_heads: str = "sparse", expert_fidelity: Optional[list] = None) -> torch.Tensor:
+                     fidelity_heads: str = "sparse", expert_fidelity: Optional[list] = None,
+                     full_dense_heads: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q,k,v: (1,H,S+T,D) [hunyuan: video then text] or (1,H,S,D) [wan].  Returns (1,H,S+T,D).
 
     hunyuan: hunyuan.py:556-605 (TripleEval.__call__ steps 5.1-5.4);  wan: wan.py:351-383.
@@ -1072,7 +1173,10 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     expert_fidelity: a list that receives one `ops.ExpertFidelity` of this call: `sampled_expert_fidelity` on the same
     `fidelity_rows`, for every head, after the routed launches and with `out=` this call's output -- what each expert WOULD
     have written on the sampled rows (columns 0 / 1) beside what the call did write (column 2), all against dense attention
-    in the input dtype.  None (default): nothing is allocated or launched for it."""
+    in the input dtype.  None (default): nothing is allocated or launched for it.
+    full_dense_heads: under full_keys="share", int32 (H,) device flags: an expert-0 head with flag 1 attends EVERY key, in the
+    dense launch of full_keys="all" (`RepairableRoutes.dense_heads`: the heads a repair moved to expert 0); the list is split
+    on the device (`ops.split_heads`).  Not read under "all"."""
     if q.dim() == 4 and q.shape[0] != 1:
         # hunyuan.py:168 asserts batch 1; Wan's CFG runs two batch-1 forwards (pipeline_wan.py:322-344)
         raise AssertionError(f"Batch size {q.shape[0]} is not supported by routed_attention.")
@@ -1108,6 +1212,21 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
                              + {"fp8pv": "mixed-precision one (16-bit k, e4m3 v)",
                                 "auto8": "mixed-precision one (16-bit k, e4m3 v), which 'auto8' needs for its heavy-tailed heads"
                                 }.get(prec, "all-e4m3 one") + " -- run it under 'native' or 'i8pv'")
+    full_share = geom.full_keys == "share" and live(0)
+    if full_share:
+        if record is not None or (torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v))):
+            raise ValueError(_no_full_share("in grad mode (no backward replays tile lists)"))
+        if expert_outs is not None:
+            raise ValueError(_no_full_share("in the soft-mixture operators (expert_outs=: every head through every expert, for "
+                                            "training)"))
+        if routing.partials:
+            raise ValueError(_no_full_share("with heads split by query range (sequence parallelism)"))
+        if expert_fidelity is not None:
+            raise ValueError("routed_attention(expert_fidelity=): " + NO_SAMPLED_FULL_SHARE)
+        prec = operands.precision if operands is not None else precision_of(fp8)
+        if prec != "native":
+            raise ValueError(f"full_keys='share' under the 8-bit precision {prec!r}: there is no int8-score or e4m3 tile-list body "
+                             "(ops.attn_fwd_tilelist is 16-bit) -- run it under 'native', or under full_keys='all'")
     if operands is None:
         # (video_tokens: the sample is summed in eighths of the video tokens + the text, as the sequence-parallel send side sums it)
         operands = prepare_operands(precision_of(fp8), q3, k3, v3, scale, fp8_operands,
@@ -1120,7 +1239,34 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     # ---- expert 0: full attention (hunyuan.py:136-189 / wan.py:142-145) ----
     def expert_full(base, slot_of, slot_part):
         calls = []
-        if routing.counts_host is None or routing.counts_host[0] > 0:
+        if full_share:
+            # the fewest key tiles, out of all, that hold geom.full_mass_share of the sampled mass: the tile-mass launches at the
+            # call's softmax scale over this expert's slots, the selection over all tiles, then ONE launch whose groups (a query
+            # tile each) walk their TILE lists through the tile-major row table, longest first.  No fused grid takes it:
+            # ops.attn_fwd_batch runs it behind the other experts'.  (flops: the dense count, an upper bound -- the kept counts
+            # live on the device)
+            sl = slot_of(0, H)
+            if full_dense_heads is not None:  # the flagged heads leave the share launches for the dense one
+                sl, dense_sl = ops.split_heads(full_dense_heads, sl.get("head_list"), sl["n_heads"], sl.get("n_heads_dev"))
+                calls.append(dict(base, out=o_e[0], tag="full", **_full_launch(geom, T, te, kv_splits),
+                                  flops=0.0, **dense_sl))
+            br = _tile_block_rows(geom.tok)
+            q_rows = geom.sta_tables(te)[0]
+            tabs = geom.full_share_buffers(sl["n_heads"])
+            ops.sta_tile_mass(q3, k3, geom.latent, geom.tile, geom.window, te, q_rows, tabs.ws, scale=scale,
+                              rows_per_tile=MASS_ROWS_PER_TILE, **sl)
+            ops.sta_select_tiles_share_all(geom.latent, geom.tile, te, tabs, mass_share=geom.full_mass_share,
+                                           n_heads=sl["n_heads"], rows_per_tile=MASS_ROWS_PER_TILE, block_rows=br,
+                                           n_heads_dev=sl.get("n_heads_dev"))
+            calls.append(dict(base, out=o_e[0], tag="full_share", n_q=S, n_kv=S + te, q_group_len=geom.tok, q_rows=q_rows,
+                              tile_lists=ops.TileLists(q_rows, tabs.sel_tiles, tabs.sel_count, geom.tok), order=tabs.order,
+                              block_rows=br, flops=nheads(0) * 4.0 * S * (S + te) * D, **sl))
+            if T > 0:  # text queries see every valid key, as the sliding expert's; padded ones see nothing -> zeros
+                calls.append(dict(base, out=o_e[0], n_q=T, q_valid=te, n_kv=S + te, q_row_offset=S, tag="full_text",
+                                  n_splits=_auto_splits(sl["n_heads"], T, S + te), flops=nheads(0) * 4.0 * D * te * (S + te), **sl))
+                if FUSED_TEXT_FIRST:  # (the hints of the sliding expert's text launch, below)
+                    calls[-1].update(fused_n_splits=FUSED_TEXT_SPLITS, fused_first=True)
+        elif routing.counts_host is None or routing.counts_host[0] > 0:
             calls.append(dict(base, out=o_e[0], tag="full", **_full_launch(geom, T, te, kv_splits),
                               flops=nheads(0) * 4.0 * (S + te) ** 2 * D, **slot_of(0, H)))
         for pi, (hl, t0, t1) in enumerate(routing.partials or ()):
@@ -1276,6 +1422,26 @@ def routed_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, routing:
     return measured(out)
 
 
+# head -> expert table (the int32 (H,) `expert_ids` a repair rewrites in place) -> int32 (H,) flags of the heads a repair moved
+# to expert 0.  Under full_keys="share" such a head keeps the DENSE launch it was repaired to, in every later call with the same
+# tables; the flags live as long as the table does.  Under "all" nothing is kept: expert 0 is the dense launch.
+_DENSE_HEADS: Dict[int, Tuple["weakref.ref", torch.Tensor]] = {}  # (keyed by identity: tensors compare elementwise)
+
+
+def dense_heads_of(expert_ids: torch.Tensor, create: bool = False) -> Optional[torch.Tensor]:
+    """the flags of the repaired heads of the route tables `expert_ids` belongs to (`routed_attention(full_dense_heads=)`); None
+    where no repair has run on them under full_keys="share" (create=True: zeros then)"""
+    entry = _DENSE_HEADS.get(id(expert_ids))
+    if entry is not None and entry[0]() is expert_ids:
+        return entry[1]
+    if not create:
+        return None
+    flags = torch.zeros_like(expert_ids, dtype=torch.int32)
+    key = id(expert_ids)
+    _DENSE_HEADS[key] = (weakref.ref(expert_ids, lambda _, key=key: _DENSE_HEADS.pop(key, None)), flags)
+    return flags
+
+
 @dataclass(eq=False)
 class RepairableRoutes:
     """The device route tables of one layer in the form `routed_attention_repaired` verifies and vorta_route_repair rewrites
@@ -1359,7 +1525,11 @@ def routed_attention_repaired(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     `rows`.  A head whose launch is the reference itself -- full attention in the input dtype -- is not measured: the native
     tier measures its sparse heads, an 8-bit tier every head.  (b) `ops.route_repair` on that record: a checked head with
     rel > repair_above (or NaN) becomes (expert 0, native) in the route tables, IN PLACE -- later calls with the same tables
-    launch it dense.  (c) One dense launch in the input dtype over the repaired heads, with the device count, writes them into
+    launch it dense.  (Under full_keys="share" expert 0 is the share launch, so the repaired heads are also flagged in
+    `dense_heads_of(expert_ids)`, and every call through this function with the same `expert_ids` table -- this one, later
+    ones, `repair_above=None` ones -- splits the flagged heads off the expert-0 list on the device and launches them dense:
+    `routed_attention(full_dense_heads=)`; a caller that launches views of the tables through `routed_attention` itself
+    passes `full_dense_heads=dense_heads_of(expert_ids)`.)  (c) One dense launch in the input dtype over the repaired heads, with the device count, writes them into
     the same `out`: the arguments of `routed_attention`'s expert 0, Hunyuan's text rows included; no coreset selection runs
     for it, and with a zero count its workgroups exit at once.
     Returns (out, RepairRecord).  On the sampled rows no head leaves the call further than `repair_above` from dense
@@ -1373,6 +1543,9 @@ def routed_attention_repaired(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if out is None:
         out = torch.empty_like(q)
     common = dict(model=model, text_len=text_len, text_valid=text_valid, out=out, scale=scale, record=record, **kw)
+    dense_heads = dense_heads_of(rr.expert_ids, create=repair_above is not None) if geom.full_keys == "share" else None
+    if dense_heads is not None:
+        common["full_dense_heads"] = dense_heads
     single = rr.tier_index is None
     if repair_above is None:
         if single:
@@ -1389,6 +1562,8 @@ def routed_attention_repaired(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                                              rr.counts, exact_tier=exact, repair_above=float(repair_above))
     if rr.tier_ids is not None:  # (a TierRoutes' global ids follow: every repaired head is in `native` now)
         rr.tier_ids.masked_fill_(state == 2, ops.TIER_NAMES.index("native"))
+    if dense_heads is not None:
+        dense_heads.masked_fill_(state == 2, 1)
     T, te = (text_len, text_valid) if model == "hunyuan" else (0, 0)
     dense = dict(q=_fold(q), k=_fold(k), v=_fold(v), scale=scale, out=_fold(out), tag="repair", flops=0.0,
                  head_list=repair_list, n_heads=q.shape[-3], n_heads_dev=repair_count,
@@ -1668,18 +1843,22 @@ _GEOMETRY_CACHE_MAX = 48
 
 def geometry_for(latent, tile, window, group, rate, device, row_map: Optional[torch.Tensor] = None,
                  partial: Optional[bool] = None, sliding_keys: Optional[str] = None,
-                 mass_share: Optional[float] = None) -> RoutedGeometry:
+                 mass_share: Optional[float] = None, full_keys: Optional[str] = None,
+                 full_mass_share: Optional[float] = None) -> RoutedGeometry:
     """Process-wide cache: the tables are built once per geometry, not once per layer call.
-    `partial`, `sliding_keys`, `mass_share`: as RoutedGeometry's (None = the process-wide switch, read here)."""
+    `partial`, `sliding_keys`, `mass_share`, `full_keys`, `full_mass_share`: as RoutedGeometry's (None = the process-wide switch,
+    read here)."""
     partial = partial_geometry() if partial is None else bool(partial)
     keys = sliding_keys_of(sliding_keys)
     share = mass_share_of(mass_share) if keys == "share" else None
+    fkeys = full_keys_of(full_keys)
+    fshare = full_mass_share_of(full_mass_share) if fkeys == "share" else None
     key = (tuple(latent), tuple(tile), tuple(window), tuple(group), float(rate), str(device),
-           None if row_map is None else (row_map.data_ptr(), row_map.numel()), partial, keys, share)
+           None if row_map is None else (row_map.data_ptr(), row_map.numel()), partial, keys, share, fkeys, fshare)
     g = _GEOMETRY_CACHE.pop(key, None)
     if g is None:
         g = RoutedGeometry(latent, tile, window, group, rate, torch.device(device), row_map=row_map, partial=partial,
-                           sliding_keys=keys, mass_share=share)
+                           sliding_keys=keys, mass_share=share, full_keys=fkeys, full_mass_share=fshare)
         # bounded: a geometry holds its sliding-tile tables (13 MB at Hunyuan-129f) and, under sequence parallelism, there is one
         # per distinct slot count of a rank (slot groups and uneven placements: up to ~2 H / P of them per resolution); the least
         # recently used one goes when a process has seen more than this many (the row maps they are keyed on are never freed)
